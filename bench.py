@@ -11,8 +11,17 @@ GEMM operands with fp32 statistics and accumulation, synthetic inputs and key-se
 Batch shards over ranks with NO data-path collective (independent trajectories) -> weak scaling.
 
 Prints ONE JSON line (rank 0).  `value` = video+audio pair denoising steps per second, whole job
-(= steps/s x global batch).  `roofline` = the dominant kernel (bf16 implicit-GEMM conv) timed live with HIP events
-on the launch stream; `cpu_baseline` = the oracle (CPU restatement, kind "port") timed on the host cores.
+(= steps/s x global batch); `ms_per_step` = milliseconds of one timed step (--steps of them are timed; --mode dpm / sr:
+one step = one whole sampling call, `ms_per_eval` = per network evaluation).
+
+A plain run sets up, warms up, times the steps and prints the line.  --full adds the side measurements:
+`roofline` = the dominant kernel (bf16 implicit-GEMM conv) timed live with HIP events on the launch stream, the
+per-kernel breakdown and the graded kernels; `cpu_baseline` = the oracle (CPU restatement, kind "port") timed on
+the host cores (--mode train: the conv weight-gradient roofline).
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32, 64 MB at most; an array
+that does not fit is replaced by a fixed seeded sample of its elements).  Inputs, weights and noise are seeded, so
+two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -32,6 +41,24 @@ MFMA_BF16_PEAK_TFLOPS = 2500.0     # dense bf16, /opt/skills/guides/MI355X_MICRO
 MFMA_F32_PEAK_TFLOPS = 157.3
 HBM_PEAK_GBS = 8000.0
 MODEL_FLOPS_PER_PAIR = 1328.8e9    # conv 1133.0 G + attention matmuls 195.8 G
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every tensor of `arrays` as <path>/<name>.npy in float32, in order.  One that does not fit in what is left of
+    the 64 MB budget is replaced by a fixed sample of its flattened elements (positions drawn from a CPU generator seeded with 0,
+    sorted), as many as fit."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() * 4 > left:
+            idx = torch.randint(t.numel(), (left // 4 // len(arrays),), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.float().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
 
 
 def build(dtype_flag, respacing, batch, device):
@@ -287,12 +314,16 @@ def train_bench(args, world, rank, device):
         from mm_diffusion.train_graph import GraphedTrainStep
         gstep = GraphedTrainStep(model, diff, opt, x0)
 
+    last = {}                     # the loss terms of the latest step (--dump-outputs)
+
     def one_step():
         t = torch.randint(0, diff.num_timesteps, (B,), generator=g).to(device)
         if gstep is not None:
-            return gstep.step(x0, t)["loss"].mean()
+            last["terms"] = gstep.step(x0, t)
+            return last["terms"]["loss"].mean()
         opt.zero_grad()
-        loss = diff.multimodal_training_losses(model, x0, t)["loss"].mean()
+        last["terms"] = diff.multimodal_training_losses(model, x0, t)
+        loss = last["terms"]["loss"].mean()
         opt.arm_overlap()             # world > 1: gradient buckets are all-reduced on a side stream while the backward is still running
         loss.backward()
         opt.all_reduce_grads()
@@ -318,8 +349,10 @@ def train_bench(args, world, rank, device):
         tt = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": last["terms"]["loss"], "params": opt.flat})
     roof = None
-    if rank == 0 and not args.no_breakdown:
+    if rank == 0 and args.full and not args.no_breakdown:
         roof = wgrad_roofline(B, device)
     if rank == 0:
         print(json.dumps({
@@ -379,11 +412,14 @@ def dpm_bench(args, world, rank, device):
         tt = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"video": out["video"], "audio": out["audio"]})
     if rank == 0:
         evals = args.steps * NFE
         print(json.dumps({
             "metric": "denoising steps/sec (video+audio pair), DPM-Solver++ multistep-2, 50 NFE", "value": evals * B * world / elapsed,
-            "unit": "pair-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1000 * elapsed / evals,
+            "unit": "pair-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1000 * elapsed / args.steps,
+            "ms_per_eval": 1000 * elapsed / evals,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic", "ranks_seen": args.ranks_seen,
             "config": {"workload": f"BASELINE configs[4] (base-model half): DPM-Solver++ 50 NFE, per-GPU batch {B}; one timed step = one full "
                                    f"{NFE}-evaluation sample() call", "global_batch": B * world, "seconds_per_sample_batch": elapsed / args.steps,
@@ -434,11 +470,14 @@ def sr_bench(args, world, rank, device):
         tt = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"frames": out})
     if rank == 0:
         evals = args.steps * diff.num_timesteps
         print(json.dumps({
             "metric": "SR denoising steps/sec (256x256 frames), DDIM-25", "value": evals * B * Fr * world / elapsed, "unit": "frame-steps/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1000 * elapsed / evals, "higher_is_better": True,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1000 * elapsed / args.steps,
+            "ms_per_eval": 1000 * elapsed / evals, "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic", "ranks_seen": args.ranks_seen,
             "config": {"workload": f"BASELINE configs[4] (SR half): ImageSuperResModel 64->256, {B} clip(s) x 16 frames per GPU, DDIM-25; one timed step "
                                    "= one full 25-evaluation ddim_sample_loop", "global_batch": B * world, "seconds_per_clip_batch": elapsed / args.steps,
@@ -483,11 +522,16 @@ def main():
     ap.add_argument("--respacing", default="250")
     ap.add_argument("--mode", default="sample", choices=["sample", "train", "dpm", "sr"],
                     help="sample = headline DDPM step (default); train = configs[3]; dpm = configs[4] base-model half (DPM-Solver++ 50 NFE); sr = configs[4] SR half (DDIM-25 on 256x256 frames)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements after the timed steps: per-kernel breakdown, roofline and graded kernels (sample mode), "
+                         "the CPU baseline (sample mode, one rank), the conv weight-gradient roofline (train mode)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--no-graph", action="store_true", help="eager launches from the host instead of the captured hipGraph (train mode; sample mode: an A/B switch)")
-    ap.add_argument("--no-breakdown", action="store_true")
+    ap.add_argument("--no-breakdown", action="store_true", help="with --full: leave out the breakdown / roofline")
     ap.add_argument("--lanes", type=int, default=0, help="batch lanes of the sampling step (0 = the sampler's default; sampler.GraphStepper)")
-    ap.add_argument("--breakdown-out", default="")
+    ap.add_argument("--breakdown-out", default="", help="with --full: file for the per-launch-shape HIP-event breakdown (sample mode)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all; rank 0)")
     ap.add_argument("--as-rank", type=int, default=0,
                     help="single-process run with the seeds of rank R of a multi-rank job (tests: rank r's trajectory is that of a lone process seeded 1234 + r)")
     ap.add_argument("--dump-final", default="", help="directory: every rank saves its final sample as rank<r>.pt (sample mode)")
@@ -495,6 +539,8 @@ def main():
                     help="only bring the ranks up, all-reduce a one per rank and print {n_gpus, ranks_seen, backend}: the self-launch / rendezvous "
                          "path without any GPU work (CPU test of `python bench.py --gpus N`)")
     args = ap.parse_args()
+    if args.breakdown_out and not args.full:
+        ap.error("--breakdown-out is part of the breakdown: it needs --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args.gpus)          # plain `python bench.py --gpus N`: spawn the N ranks ourselves
@@ -577,6 +623,12 @@ def main():
         fence()
         gather_ms = 1000.0 * (time.perf_counter() - tg)
         assert gv.shape[0] == args.batch * world and ga.shape[0] == args.batch * world
+    if args.dump_outputs:  # before anything replays the plan again: x_{t-1} of both streams and the U-Net's prediction of the last step
+        outs = {"video": cur["video"], "audio": cur["audio"],
+                "eps_video": torch.cat([e.out_video for e in stepper.engs]), "eps_audio": torch.cat([e.out_audio for e in stepper.engs])}
+        outs = {k: dist_util.all_gather_samples(v) for k, v in outs.items()}       # whole job (identity on one rank)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, outs)
 
     global_batch = args.batch * world
     steps_per_s = args.steps / elapsed
@@ -593,7 +645,7 @@ def main():
         "model_tflops": steps_per_s * args.batch * MODEL_FLOPS_PER_PAIR / 1e12,
     }
     timed_lanes = stepper.lanes
-    if rank == 0 and not args.no_breakdown:
+    if rank == 0 and args.full and not args.no_breakdown:
         if stepper.lanes > 1:      # per-kernel accounting on the unsplit batch-N plan (the shapes BASELINE.md grades), one stream, in order
             stepper = GraphStepper(diff, model, args.batch, device, clip_denoised=True, lanes=1)
         agg = kernel_breakdown(stepper)
@@ -689,7 +741,7 @@ def main():
             det = kernel_breakdown(stepper, reps=2, detail=True)
             with open(args.breakdown_out, "w") as f:
                 json.dump(dict(sorted(det.items(), key=lambda kv: -kv[1]["ms"])), f, indent=1)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(fl)
     if rank == 0:
         print(json.dumps(res))

@@ -100,3 +100,29 @@ def test_bench_refuses_a_mismatched_launcher():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--launch-check"], env=env, capture_output=True,
                          text=True, timeout=120)
     assert out.returncode != 0 and "WORLD_SIZE=1" in (out.stderr + out.stdout)
+
+
+def test_bench_breakdown_out_needs_full():
+    """The per-shape breakdown is a side measurement: it belongs to `--full`, and asking for its file without it is an error."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--breakdown-out", "x.json"], capture_output=True, text=True,
+                         timeout=120)
+    assert out.returncode == 2 and "--full" in out.stderr
+
+
+def test_bench_dump_outputs_float32_budget_and_fixed_sample(tmp_path):
+    """bench.dump_outputs (--dump-outputs): one float32 <name>.npy per array, shape kept, 64 MB at most in all; an array that does not
+    fit is replaced by a sample of its elements at sorted positions that are the same on every run."""
+    import numpy as np
+    import torch
+    import bench
+    small = torch.arange(10, dtype=torch.float64).reshape(2, 5)
+    big = torch.arange(20 << 20, dtype=torch.int32)                    # 80 MB as float32: over the budget
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "big": big})
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("small", "big")}
+    assert sorted(os.listdir(tmp_path / "a")) == ["big.npy", "small.npy"]
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert np.array_equal(a["small"], np.arange(10, dtype=np.float32).reshape(2, 5))
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_BUDGET_BYTES and a["big"].size >= 1 << 20
+    assert np.all(np.diff(a["big"]) >= 0) and a["big"][-1] < 20 << 20
+    assert np.array_equal(a["big"], np.load(tmp_path / "b" / "big.npy"))

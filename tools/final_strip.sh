@@ -22,10 +22,10 @@ echo $mode > $O/strip_mode.txt
 grep -n 'MMD_GEMM_STRIP", "' $OPS >> $O/strip_mode.txt
 tail -n 30 $O/pytest_strip_pin.log
 timeout 300 python tools/strip_probe.py > profiles/${TAG}_strip_probe.txt 2>&1
-MMD_GEMM_STRIP=0 timeout 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline > $O/bench_strip_off.log 2>&1
+MMD_GEMM_STRIP=0 timeout 300 python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline > $O/bench_strip_off.log 2>&1
 tail -1 $O/bench_strip_off.log > profiles/${TAG}_bench_line_strip_off.json
 if [ $mode = pin ]; then
-  MMD_GEMM_STRIP=base timeout 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline > $O/bench_strip_base.log 2>&1
+  MMD_GEMM_STRIP=base timeout 300 python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline > $O/bench_strip_base.log 2>&1
   tail -1 $O/bench_strip_base.log > profiles/${TAG}_bench_line_strip_base.json
 fi
 bash tools/round_profile.sh $TAG

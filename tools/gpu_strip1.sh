@@ -11,7 +11,7 @@ echo "strip tests rc=$?" | tee $O/rc.txt
 timeout 200 python tools/strip_probe.py > $O/probe.log 2>&1
 echo "probe rc=$?" | tee -a $O/rc.txt
 for mode in 0 pin 1x1 gn; do
-  MMD_GEMM_STRIP=$mode timeout 200 python bench.py --steps 20 --warmup 3 > $O/bench_$mode.json 2> $O/bench_$mode.err
+  MMD_GEMM_STRIP=$mode timeout 200 python bench.py --steps 20 --warmup 3 --full > $O/bench_$mode.json 2> $O/bench_$mode.err
   echo "bench $mode rc=$?" | tee -a $O/rc.txt
 done
 if grep -q "passed" $O/pytest_strip.log && ! grep -q "failed" $O/pytest_strip.log; then

@@ -33,11 +33,11 @@ python tools/rocprof_summary.py "$(find $O/kt -name '*.db' | head -1)" profiles/
 BTR="python bench.py --mode train --batch 8 --steps 4 --warmup 2"
 timeout 600 rocprofv3 --kernel-trace --stats -d $O/kt_train -o kt -- $BTR > $O/kt_train.log 2>&1
 python tools/rocprof_summary.py "$(find $O/kt_train -name '*.db' | head -1)" profiles/${TAG}_train_step_kernel_stats.txt profiles/kernel_stats_train.json "$BTR" > /dev/null
-timeout 600 python bench.py --breakdown-out profiles/${TAG}_bench_breakdown_hip_events.json > $O/bench_default.log 2>&1
+timeout 600 python bench.py --full --breakdown-out profiles/${TAG}_bench_breakdown_hip_events.json > $O/bench_default.log 2>&1
 tail -1 $O/bench_default.log > profiles/${TAG}_bench_line.json
 timeout 400 python bench.py --mode dpm --batch 2 --steps 2 --warmup 1 > $O/bench_dpm.log 2>&1; tail -1 $O/bench_dpm.log > profiles/${TAG}_bench_line_dpm.json
 timeout 400 python bench.py --mode sr --batch 1 --steps 1 --warmup 1 > $O/bench_sr.log 2>&1; tail -1 $O/bench_sr.log > profiles/${TAG}_bench_line_sr.json
-timeout 400 python bench.py --mode train --batch 8 --steps 5 --warmup 2 > $O/bench_train.log 2>&1; tail -1 $O/bench_train.log > profiles/${TAG}_bench_line_train.json
+timeout 400 python bench.py --mode train --batch 8 --steps 5 --warmup 2 --full > $O/bench_train.log 2>&1; tail -1 $O/bench_train.log > profiles/${TAG}_bench_line_train.json
 mkdir -p $O/profiles && cp profiles/${TAG}_* profiles/pmc_traffic.json profiles/kernel_stats.json profiles/kernel_stats_train.json $O/profiles/ 2>/dev/null
 rm -rf $O/kt $O/ktc $O/kt_train $O/pmc_fetch $O/pmc_write $O/pmc_sq1 $O/pmc_sq2      # raw traces stay on the box: only the summaries travel back
 tail -3 $O/pytest.txt 2>/dev/null; tail -1 $O/smoke.log 2>/dev/null; cat profiles/${TAG}_bench_line.json

@@ -10,7 +10,7 @@ mkdir -p $O
 MMD_TEST_EXPERIMENTAL=1 timeout 200 python -m pytest tests/test_ops_gpu.py -q -k "halo" 2>&1 | tail -15 > $O/pytest.txt
 timeout 200 python tools/gemm_bench.py > $O/gemm_bench.txt 2>&1
 timeout 120 python bench.py --no-cpu-baseline --no-breakdown > $O/bench_base.json 2> $O/bench_base.err
-MMD_GEMM_HALO=1 timeout 150 python bench.py --no-cpu-baseline --breakdown-out $O/breakdown_halo.json > $O/bench_halo.json 2> $O/bench_halo.err
+MMD_GEMM_HALO=1 timeout 150 python bench.py --full --no-cpu-baseline --breakdown-out $O/breakdown_halo.json > $O/bench_halo.json 2> $O/bench_halo.err
 tail -5 $O/pytest.txt
 grep -E "3x3|k3t" $O/gemm_bench.txt
 python - <<'PY'
