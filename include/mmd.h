@@ -304,7 +304,9 @@ int mmd_pack_conv_weights(int dtype, const void* descs_dev, int n, int total_blo
  * fp32 packed accumulation buffer [Cout][nt*Cin] that mmd_conv_wgrad filled with coalesced atomics) grad += packed, packed = 0. */
 int mmd_unpack_conv_grads(const void* descs_dev, int n, int total_blocks, void* stream);
 /* GroupNorm32(+FiLM)(+SiLU) backward; a, b, mr from the forward mmd_gn_stats; dgamma/dbeta accumulate; dfilm (nullable)
- * [S, >=2C] receives (dscale | dshift); workspace (S*C*2 + S*64) floats. */
+ * [S, >=2C] receives (dscale | dshift); workspace (S*C*2 + S*64) floats.  C a multiple of 32 and of the 16-byte vector, C <= 2048
+ * (the forward's limit; launch shapes for C <= 1024 are what they always were, fp32 rows above 1024 channels go in two column
+ * halves), S <= 65535. */
 int mmd_gn_bwd(int dtype, const void* x, int64_t ldx, const void* dy, int64_t lddy, void* dx, int64_t lddx, int64_t rows, int C, int S,
                int Tn, int inner, int64_t outer_stride, int64_t inner_stride, int64_t tstride, const float* a, const float* b,
                const float* mr, const float* gamma, const float* beta, const float* film, int64_t film_ld, int act, float* dgamma,
@@ -316,14 +318,17 @@ int mmd_gn_bwd_ws0(int dtype, const void* x, int64_t ldx, const void* dy, int64_
                    int Tn, int inner, int64_t outer_stride, int64_t inner_stride, int64_t tstride, const float* a, const float* b,
                    const float* mr, const float* gamma, const float* beta, const float* film, int64_t film_ld, int act, float* dgamma,
                    float* dbeta, float* dfilm, int64_t dfilm_ld, float* workspace, void* stream);
-/* Attention backward for every attention of the model (strided + windowed row descriptor, see mmd_attn_bwd.hip). */
+/* Attention backward for every attention of the model (strided + windowed row descriptor, see mmd_attn_bwd.hip).  Head width
+ * ch <= 192: 64-row LDS tiles up to 128, 32-row tiles above (the fp32 path and the bf16 path of widths off the MFMA list). */
 int mmd_attn_bwd(int dtype, const void* Q, int64_t ldq, int q_off, const void* KV, int64_t ldkv, int k_off, int v_off, const void* O,
                  int64_t ldo, const void* dO, int64_t lddo, void* dQ, int64_t lddq, int dq_off, void* dKV, int64_t lddkv, int dk_off,
                  int dv_off, float* lse_ws, float* dsum_ws, int heads, int ch, int nb, int G, int q_inner, int64_t q_outer,
                  int64_t q_istride, int64_t q_tstride, int q_total, int q_per_group, int k_inner, int64_t k_outer, int64_t k_istride,
                  int64_t k_tstride, int k_mod, int k_per_group, int win, const int* shift_dev, void* stream);
 /* bf16 MFMA pair for contiguous-row attention: the training forward also returns the log2-domain log-sum-exp per (query
- * row, head); the backward recomputes P from it (no stored probabilities).  Same row / window arguments as mmd_attn_fwd. */
+ * row, head); the backward recomputes P from it (no stored probabilities).  Same row / window arguments as mmd_attn_fwd.
+ * Head widths {16,32,48,64,96,128,192}; at 192 the dK / dV kernel runs as two workgroups per (key tile, head), each accumulating
+ * 96 of the 192 columns (the one-workgroup form needs 352 live registers and spills). */
 int mmd_attn_fwd_lse(int dtype, const void* Q, int64_t ldq, int q_off, const void* KV, int64_t ldkv, int k_off, int v_off, void* O,
                      int64_t ldo, int heads, int ch, int nb, int G, int64_t q_rows_per_batch, int q_per_group,
                      int64_t k_rows_per_batch, int k_per_group, int win, const int* shift_dev, float* lse2_out, void* stream);

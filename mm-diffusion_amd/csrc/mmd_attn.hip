@@ -1555,7 +1555,7 @@ static int attn_fwd_impl(int dtype, const void* Q, int64_t ldq, int q_off, const
       default: break;
     }
   }
-  if (lse2_out) return mmd_set_error(MMD_ERR_UNSUPPORTED, "attn_fwd_lse: needs the bf16 MFMA path (ch in {16,32,48,64,96,128}, aligned rows)");
+  if (lse2_out) return mmd_set_error(MMD_ERR_UNSUPPORTED, "attn_fwd_lse: needs the bf16 MFMA path (ch in {16,32,48,64,96,128,192}, aligned rows)");
   if (dtype == MMD_BF16) return launch_generic<__bf16>(p, qmax, st);
   return launch_generic<float>(p, qmax, st);
 }

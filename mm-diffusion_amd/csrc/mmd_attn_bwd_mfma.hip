@@ -229,9 +229,14 @@ __global__ __launch_bounds__(256, (D <= 64 ? 2 : 1)) void attn_bwd_dq_mfma_kerne
 }
 
 // ============================================================================= dK / dV
-template <int D>
+// NS = 1: the whole head width in one workgroup.  NS > 1 (head width 192): the workgroup still holds the key's full K / V fragments
+// and computes the full S / dP tiles, but accumulates only columns [split * D/NS, (split + 1) * D/NS) of dK / dV, so the accumulators
+// are 2 x DT/NS tiles instead of 2 x DT (at 192: 96 + 96 + 64 live registers instead of 352, which did not fit in 512 without scratch);
+// blockIdx.y carries (head, split).  Only the accumulated columns of Q / dO are staged transposed.
+template <int D, int NS = 1>
 __global__ __launch_bounds__(256, (D <= 64 ? 2 : 1)) void attn_bwd_dkv_mfma_kernel(const AttnBwdMParams p) {
-  constexpr int SK = D * 2 + 16, KST = D / 16, DT = (D + 31) / 32;
+  constexpr int SK = D * 2 + 16, KST = D / 16, DA = D / NS, DT = (DA + 31) / 32;
+  static_assert(D % NS == 0 && (NS == 1 || DA % 32 == 0), "split widths are whole 32-column accumulator tiles");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* sQ = smem;                                   // [64][SK]
   char* sdO = smem + 64 * SK;                        // [64][SK]
@@ -243,16 +248,18 @@ __global__ __launch_bounds__(256, (D <= 64 ? 2 : 1)) void attn_bwd_dkv_mfma_kern
   const int half = lane >> 5, l31 = lane & 31;
   int ktile, h, n;
   bm_block_coords(ktile, h, n);
+  const int split = NS > 1 ? h % NS : 0;
+  if (NS > 1) h /= NS;
   const int k_mod = (int)p.k_rows_per_batch, kcount = p.win * p.k_per_group;
   const int k0 = ktile * 128;
   if (k0 >= k_mod) return;
   const int kidx = k0 + wave * 32 + l31;
   const bool kok = kidx < k_mod;
   const int64_t krow = (int64_t)n * p.k_rows_per_batch + (kok ? kidx : 0);
-  if (D % 32 != 0)
-    for (int i = tid; i < (DT * 32 - D) * TSTRIDE / 4; i += 256) {
-      ((uint32_t*)(sQt + D * TSTRIDE))[i] = 0u;
-      ((uint32_t*)(sdOt + D * TSTRIDE))[i] = 0u;
+  if (DA % 32 != 0)
+    for (int i = tid; i < (DT * 32 - DA) * TSTRIDE / 4; i += 256) {
+      ((uint32_t*)(sQt + DA * TSTRIDE))[i] = 0u;
+      ((uint32_t*)(sdOt + DA * TSTRIDE))[i] = 0u;
     }
   u32x4 kfr[KST], vfr[KST];
   {
@@ -289,8 +296,17 @@ __global__ __launch_bounds__(256, (D <= 64 ? 2 : 1)) void attn_bwd_dkv_mfma_kern
       auto gptr = [&](int j) -> const char* {
         return q0 + j < qcount ? p.dO + ((q_row0 + q0 + j) * p.lddo + h * D) * 2 : nullptr;
       };
-      stage_tile<D, true, true>(sQ, sQt, tid, qptr);
-      stage_tile<D, true, true>(sdO, sdOt, tid, gptr);
+      if (NS == 1) {
+        stage_tile<D, true, true>(sQ, sQt, tid, qptr);
+        stage_tile<D, true, true>(sdO, sdOt, tid, gptr);
+      } else {
+        auto qptr_a = [&](int j) -> const char* { const char* r = qptr(j); return r ? r + split * DA * 2 : nullptr; };
+        auto gptr_a = [&](int j) -> const char* { const char* r = gptr(j); return r ? r + split * DA * 2 : nullptr; };
+        stage_tile<D, true, false>(sQ, nullptr, tid, qptr);
+        stage_tile<D, true, false>(sdO, nullptr, tid, gptr);
+        stage_tile<DA, false, true>(nullptr, sQt, tid, qptr_a);
+        stage_tile<DA, false, true>(nullptr, sdOt, tid, gptr_a);
+      }
       if (tid < 64) {
         const bool ok = q0 + tid < qcount;
         const int64_t r = q_row0 + q0 + (ok ? tid : 0);
@@ -311,6 +327,8 @@ __global__ __launch_bounds__(256, (D <= 64 ? 2 : 1)) void attn_bwd_dkv_mfma_kern
           const u32x4 gfr = *(const u32x4*)(sdO + (qt * 32 + l31) * SK + half * 16 + st * 32);
           s[qt] = MFMA_BF16(qfr, kfr[st], s[qt]);             // rows = queries, cols = keys (this lane's key)
           dp[qt] = MFMA_BF16(gfr, vfr[st], dp[qt]);
+          // split form: keep the scheduler from hoisting all 4 x KST fragment loads above the MFMAs (it then spills 13 registers)
+          if (NS > 1 && qt == 1 && (st & 1) == 1) __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt)
@@ -340,14 +358,14 @@ __global__ __launch_bounds__(256, (D <= 64 ? 2 : 1)) void attn_bwd_dkv_mfma_kern
     }
   }
   if (kok) {
-    char* kp = p.dKV + (krow * p.lddkv + p.dk_off + h * D) * 2;
-    char* vp = p.dKV + (krow * p.lddkv + p.dv_off + h * D) * 2;
+    char* kp = p.dKV + (krow * p.lddkv + p.dk_off + h * D + split * DA) * 2;
+    char* vp = p.dKV + (krow * p.lddkv + p.dv_off + h * D + split * DA) * 2;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
       for (int q4 = 0; q4 < 4; ++q4) {
         const int d = dt * 32 + 8 * q4 + 4 * half;
-        if (d < D) {
+        if (d < DA) {
           bf16x4 wk, wv;
 #pragma unroll
           for (int j = 0; j < 4; ++j) { wk[j] = (__bf16)(dk[dt][4 * q4 + j] * p.scale); wv[j] = (__bf16)dv[dt][4 * q4 + j]; }
@@ -358,25 +376,35 @@ __global__ __launch_bounds__(256, (D <= 64 ? 2 : 1)) void attn_bwd_dkv_mfma_kern
   }
 }
 
-template <int D>
+template <int D, int NS = 1>
 static int launch_bwd_mfma(const AttnBwdMParams& p, hipStream_t st) {
-  constexpr int SK = D * 2 + 16, DT = (D + 31) / 32;
+  constexpr int SK = D * 2 + 16, DT = (D + 31) / 32, DTA = (D / NS + 31) / 32;
   const size_t lds_q = 128 * SK + DT * 32 * TSTRIDE;
-  const size_t lds_kv = 128 * SK + 2 * DT * 32 * TSTRIDE + 128 * sizeof(float);
+  const size_t lds_kv = 128 * SK + 2 * DTA * 32 * TSTRIDE + 128 * sizeof(float);
   const int qmax = (int)(p.q_rows_per_batch - (int64_t)(p.G - 1) * p.q_per_group);
+  const void* fkv = (const void*)attn_bwd_dkv_mfma_kernel<D, NS>;
   if (lds_kv > 64 * 1024) {
     static bool attr_done[MMD_MAX_DEVICES] = {};
   bool& attr_set = attr_done[mmd_device_slot()];
     if (!attr_set) {
-      if (hipFuncSetAttribute((const void*)attn_bwd_dkv_mfma_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv) != hipSuccess)
+      if (hipFuncSetAttribute(fkv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv) != hipSuccess)
         return mmd_set_error(MMD_ERR_LAUNCH, "attn_bwd_mfma: set LDS attr failed");
+      attr_set = true;
+    }
+  }
+  if (lds_q > 64 * 1024) {                     // head width 192: 75.5 KB
+    static bool attr_done_q[MMD_MAX_DEVICES] = {};
+    bool& attr_set = attr_done_q[mmd_device_slot()];
+    if (!attr_set) {
+      if (hipFuncSetAttribute((const void*)attn_bwd_dq_mfma_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q) != hipSuccess)
+        return mmd_set_error(MMD_ERR_LAUNCH, "attn_bwd_mfma: set LDS attr failed (dQ)");
       attr_set = true;
     }
   }
   hipLaunchKernelGGL(attn_bwd_dq_mfma_kernel<D>, dim3(cdiv(qmax, 128), p.heads, p.nb * p.G), dim3(256), lds_q, st, p);
   int rc = mmd_check_launch("attn_bwd_dq_mfma");
   if (rc) return rc;
-  hipLaunchKernelGGL(attn_bwd_dkv_mfma_kernel<D>, dim3(cdiv(p.k_rows_per_batch, 128), p.heads, p.nb), dim3(256), lds_kv, st, p);
+  hipLaunchKernelGGL((attn_bwd_dkv_mfma_kernel<D, NS>), dim3(cdiv(p.k_rows_per_batch, 128), p.heads * NS, p.nb), dim3(256), lds_kv, st, p);
   return mmd_check_launch("attn_bwd_dkv_mfma");
 }
 
@@ -407,6 +435,7 @@ extern "C" int mmd_attn_bwd_mfma(const void* Q, int64_t ldq, int q_off, const vo
     case 64: return launch_bwd_mfma<64>(p, st);
     case 96: return launch_bwd_mfma<96>(p, st);
     case 128: return launch_bwd_mfma<128>(p, st);
-    default: return mmd_set_error(MMD_ERR_UNSUPPORTED, "attn_bwd_mfma: head width %d not in {16,32,48,64,96,128}", ch);
+    case 192: return launch_bwd_mfma<192, 2>(p, st);      // SR U-Net: 768 channels / 4 heads; dK / dV in two 96-column halves
+    default: return mmd_set_error(MMD_ERR_UNSUPPORTED, "attn_bwd_mfma: head width %d not in {16,32,48,64,96,128,192}", ch);
   }
 }

@@ -477,8 +477,10 @@ __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const char* __restri
   constexpr int ES = 16 / EPV;
   __shared__ float s_p[256 * EPV], s_q[256 * EPV];
   const int s = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
-  const int CV = C / EPV, RPP = 256 / CV;
-  const int col = tid % CV, rl = tid / CV;
+  // gridDim.z column chunks of CW channels each (1 chunk unless a row is more than 256 16-byte vectors: fp32 above 1024 channels)
+  const int CW = C / (int)gridDim.z, c0 = (int)blockIdx.z * CW;
+  const int CV = CW / EPV, RPP = 256 / CV;
+  const int col = c0 / EPV + tid % CV, rl = tid / CV;
   const int cpg = C / 32;
   const int64_t base = gnb_base(g, s);
   float P[EPV], Q[EPV], av[EPV], bv[EPV], mu[EPV], rs[EPV];
@@ -524,14 +526,14 @@ __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const char* __restri
       body(*(const u32x4*)(x + (r0 * ldx + col * EPV) * ES), *(const u32x4*)(dy + (r0 * lddy + col * EPV) * ES));
     }
 #pragma unroll
-    for (int e = 0; e < EPV; ++e) { s_p[rl * C + col * EPV + e] = P[e]; s_q[rl * C + col * EPV + e] = Q[e]; }
+    for (int e = 0; e < EPV; ++e) { s_p[rl * CW + col * EPV - c0 + e] = P[e]; s_q[rl * CW + col * EPV - c0 + e] = Q[e]; }
   }
   __syncthreads();
-  for (int c = tid; c < C; c += 256) {
+  for (int c = tid; c < CW; c += 256) {
     float pa = 0.f, qa = 0.f;
-    for (int r = 0; r < RPP; ++r) { pa += s_p[r * C + c]; qa += s_q[r * C + c]; }
-    atomicAdd(PQ + ((int64_t)s * C + c) * 2, pa);
-    atomicAdd(PQ + ((int64_t)s * C + c) * 2 + 1, qa);
+    for (int r = 0; r < RPP; ++r) { pa += s_p[r * CW + c]; qa += s_q[r * CW + c]; }
+    atomicAdd(PQ + ((int64_t)s * C + c0 + c) * 2, pa);
+    atomicAdd(PQ + ((int64_t)s * C + c0 + c) * 2 + 1, qa);
   }
 }
 
@@ -540,10 +542,12 @@ __global__ __launch_bounds__(256) void gn_bwd_params_kernel(float* __restrict__ 
                                                             const float* __restrict__ beta, const float* __restrict__ film, int64_t film_ld,
                                                             float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ dfilm,
                                                             int64_t dfilm_ld, float* __restrict__ m12, int rezero) {
-  // round 6: grid (4, S) - a block owns 8 groups = 8 cpg <= 256 channels, one per thread (it was one block per slice looping over C)
+  // round 6: grid (4, S) - a block owns 8 groups = 8 cpg <= 256 channels, one per thread (it was one block per slice looping over C);
+  // above 1024 channels grid (8, S): 4 groups = 4 cpg <= 256 channels per block
   __shared__ float s_g1[256], s_g2[256];
-  const int s = blockIdx.y, g0 = blockIdx.x * 8, tid = threadIdx.x;
-  const int cpg = C / 32, nch = 8 * cpg;
+  const int GPB = 32 / (int)gridDim.x;
+  const int s = blockIdx.y, g0 = blockIdx.x * GPB, tid = threadIdx.x;
+  const int cpg = C / 32, nch = GPB * cpg;
   if (tid < nch) {
     const int c = g0 * cpg + tid;
     const float P = PQ[((int64_t)s * C + c) * 2], Q = PQ[((int64_t)s * C + c) * 2 + 1];
@@ -563,7 +567,7 @@ __global__ __launch_bounds__(256) void gn_bwd_params_kernel(float* __restrict__ 
     }
   }
   __syncthreads();
-  if (tid < 8) {
+  if (tid < GPB) {
     float a1 = 0.f, a2 = 0.f;
     for (int c = tid * cpg; c < (tid + 1) * cpg; ++c) { a1 += s_g1[c]; a2 += s_g2[c]; }
     const float cnt = (float)Tn * (float)cpg;
@@ -583,8 +587,9 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const char* __restric
   constexpr int EPV = Elt<T>::EPV;
   constexpr int ES = 16 / EPV;
   const int s = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
-  const int CV = C / EPV, RPP = 256 / CV, cpg = C / 32;
-  const int col = tid % CV, rl = tid / CV;
+  const int CW = C / (int)gridDim.z;           // column chunks as in gn_bwd_reduce_kernel
+  const int CV = CW / EPV, RPP = 256 / CV, cpg = C / 32;
+  const int col = (int)blockIdx.z * CV + tid % CV, rl = tid / CV;
   if (rl >= RPP) return;
   const int64_t base = gnb_base(g, s);
   float av[EPV], bv[EPV], k1[EPV], k2[EPV], k3[EPV];
@@ -816,7 +821,12 @@ static int gn_bwd_impl(int dtype, const void* x, int64_t ldx, const void* dy, in
   const int epv = dtype == MMD_BF16 ? 8 : 4;
   MMD_REQUIRE(dtype == MMD_BF16 || dtype == MMD_F32, "gn_bwd: bad dtype");
   MMD_REQUIRE(x && dy && dx && a && b && mr && gamma && beta && dgamma && dbeta && workspace, "gn_bwd: null pointer");
-  MMD_REQUIRE(C % 32 == 0 && C % epv == 0 && C / epv <= 256 && C <= 1024, "gn_bwd: unsupported channel count %d", C);
+  MMD_REQUIRE(C > 0 && C % 32 == 0 && C % epv == 0 && C <= 2048, "gn_bwd: unsupported channel count %d (a multiple of 32 and of the 16-byte vector, at most 2048)", C);
+  MMD_REQUIRE(S > 0 && S <= 65535, "gn_bwd: %d slices (the slice index is a grid y coordinate: at most 65535)", S);
+  // column chunks: a block covers at most 256 16-byte vectors of a row, so fp32 rows above 1024 channels go in two halves (C % 32 == 0
+  // keeps a half a whole number of vectors); one chunk - today's launch shapes - for every C <= 1024 and every bf16 C <= 2048
+  const int NZ = C / epv <= 256 ? 1 : 2;
+  const int CW = C / NZ;
   GnBwdGeom g{S, Tn, inner, outer_stride, inner_stride, tstride};
   hipStream_t st = (hipStream_t)stream;
   float* PQ = workspace;
@@ -827,23 +837,23 @@ static int gn_bwd_impl(int dtype, const void* x, int64_t ldx, const void* dy, in
     hipLaunchKernelGGL(zero_f32_kernel, dim3(ew_grid_b((int64_t)S * C * 2)), dim3(256), 0, st, PQ, (int64_t)S * C * 2);
     if (int zrc = mmd_check_launch("gn_bwd_zero")) return zrc;
   }
-  const int rpp = max(1, 256 / (C / epv));
+  const int rpp = max(1, 256 / (CW / epv));
   int R = 4 * rpp;
   while ((int64_t)S * cdiv(Tn, R) > 1280 && R < 1024) R *= 2;
-  dim3 grid(cdiv(Tn, R), S);
+  dim3 grid(cdiv(Tn, R), S, NZ);
   if (dtype == MMD_BF16)
     hipLaunchKernelGGL(gn_bwd_reduce_kernel<__bf16>, grid, dim3(256), 0, st, (const char*)x, ldx, (const char*)dy, lddy, C, g, a, b, mr, act, R, PQ);
   else
     hipLaunchKernelGGL(gn_bwd_reduce_kernel<float>, grid, dim3(256), 0, st, (const char*)x, ldx, (const char*)dy, lddy, C, g, a, b, mr, act, R, PQ);
   int rc = mmd_check_launch("gn_bwd_reduce");
   if (rc) return rc;
-  hipLaunchKernelGGL(gn_bwd_params_kernel, dim3(4, S), dim3(256), 0, st, PQ, C, Tn, gamma, beta, film, film_ld, dgamma, dbeta, dfilm,
+  hipLaunchKernelGGL(gn_bwd_params_kernel, dim3(C <= 1024 ? 4 : 8, S), dim3(256), 0, st, PQ, C, Tn, gamma, beta, film, film_ld, dgamma, dbeta, dfilm,
                      dfilm_ld, m12, ws0 ? 1 : 0);
   rc = mmd_check_launch("gn_bwd_params");
   if (rc) return rc;
   int R3 = 4 * rpp;
   while ((int64_t)S * cdiv(Tn, R3) > 4096 && R3 < 1024) R3 *= 2;
-  dim3 grid3(cdiv(Tn, R3), S);
+  dim3 grid3(cdiv(Tn, R3), S, NZ);
   (void)rows;
   if (dtype == MMD_BF16)
     hipLaunchKernelGGL(gn_bwd_apply_kernel<__bf16>, grid3, dim3(256), 0, st, (const char*)x, ldx, (const char*)dy, lddy, (char*)dx, lddx, C, g,

@@ -9,8 +9,9 @@ repeated over the frames of a clip) and return the final sample tensor.
 Reference behaviours kept: `p_sample_loop` hands its `noise` argument down to `p_sample`, so when a start noise is given
 the SAME tensor is re-used as the per-step noise of every step (gd:547-556, 423-424); `ddim_sample` always draws fresh noise
 (gd:661); `ddim_sample_loop_progressive` defaults to eta = 0.5 while `ddim_sample_loop` defaults to 0.0 (gd:725,759).
-Not built: cond_fn (classifier guidance), training_losses / bpd loops of the SR model (training the SR stage is out of the
-hot path)."""
+`training_losses` (gd:850-927; py_scripts/image_sr_train.py through train_util.TrainLoop) runs q_sample, the model and the MSE /
+learned-range vb reductions in libmmd and is differentiable when the model output carries a grad_fn.
+Not built: cond_fn (classifier guidance), the KL / RESCALED_KL loss types and the bpd loops."""
 import torch as th
 
 from . import _hip as H
@@ -120,6 +121,46 @@ class GaussianDiffusion(_Base):
                 out = self.ddim_sample(model, img, t, clip_denoised=clip_denoised, cond_fn=cond_fn, model_kwargs=model_kwargs, eta=eta)
             yield out
             img = out["sample"]
+
+    def training_losses(self, model, x_start, t, model_kwargs=None, noise=None):
+        """gd:850-927 -> per-sample {"loss", "mse"[, "vb"]}: MSE / RESCALED_MSE with fixed or learned-range variance (the vb term sees the
+        mean prediction detached and clip_denoised=False, gd:887-901; RESCALED_MSE scales it by num_timesteps / 1000)."""
+        if self.loss_type not in (LossType.MSE, LossType.RESCALED_MSE):
+            raise NotImplementedError("training_losses: the KL / RESCALED_KL loss types are not built (the full-bound bpd walk has no "
+                                      "libmmd kernel; the SR stage trains with MSE + learned-range vb)")
+        H.require_cuda(x_start)
+        if noise is None:
+            noise = self._randn_like(x_start)
+        xt = self.q_sample(x_start, t, noise=noise)
+        mo = self._model_out(model, xt, t, model_kwargs)      # SpacedDiffusion maps the timesteps in there; fp32, keeps the grad_fn
+        tab, _ = self.device_tables(xt.device)
+        learned = self.model_var_type == ModelVarType.LEARNED_RANGE
+        flags = (2 if self.model_mean_type == ModelMeanType.START_X else 0) | (4 if learned else 0)
+        vb_scale = self.num_timesteps / 1000.0 if self.loss_type == LossType.RESCALED_MSE else 1.0
+        tgt = (x_start if self.model_mean_type == ModelMeanType.START_X else noise).float().contiguous()
+        x0 = x_start.float().contiguous()
+        t64 = t.to(th.int64).contiguous()
+        F, C, HW = _geom4(xt)
+        N = xt.shape[0]
+        terms = {}
+        if th.is_grad_enabled() and mo.requires_grad:
+            if learned:
+                from .train_ops import LossTermsFn
+                terms["mse"], terms["vb"] = LossTermsFn.apply(mo.reshape(N, 1, 2 * C, HW), tgt.reshape(N, 1, C, HW), x0.reshape(N, 1, C, HW),
+                                                              xt.reshape(N, 1, C, HW), tab, t64, (F, C, HW), flags, vb_scale)
+            else:
+                from .train_ops import MseLossFn
+                terms["mse"] = MseLossFn.apply(mo, tgt)
+        else:
+            mo = mo.float().contiguous()
+            mse, vb = ops.loss_terms(mo.reshape(N, 1, -1, HW), tgt.reshape(N, 1, C, HW), tab, t64, F, C, HW, flags,
+                                     x0=x0.reshape(N, 1, C, HW) if learned else None, xt=xt.reshape(N, 1, C, HW) if learned else None,
+                                     vb_scale=vb_scale)
+            terms["mse"] = mse
+            if learned:
+                terms["vb"] = vb
+        terms["loss"] = terms["mse"] + terms["vb"] if "vb" in terms else terms["mse"]
+        return terms
 
     # the multimodal dict-valued entry points do not apply to the tensor-valued process
     def multimodal_training_losses(self, *a, **kw):

@@ -14,8 +14,14 @@ kernels as the multimodal U-Net on channels-last rows `[(n h w), C]`:
   skip `th.cat`   column-slice copies into one pre-sized buffer (mmd_copy2d)
   SuperRes input  bilinear upsample of `low_res` + channel concat in one kernel (mmd_bilinear_concat) feeding the stem conv
 
-Inference only (the SR model is a sampling-time component of multimodal_sample_sr.py:186-253).  Not built:
-`resblock_updown=False` (strided-conv Downsample / conv Upsample - the shipped SR checkpoint uses resblock_updown),
+Training (py_scripts/image_sr_train.py): with autograd enabled and a parameter that requires grad, `forward` takes the differentiable
+walk of image_train_forward.py over the same plan (train_ops Functions: forward and backward are libmmd kernels); under no_grad, or
+with every parameter frozen, it is the inference walk above, untouched.  Gradients with respect to the INPUT images (`x` / `low_res`
+requiring grad while a parameter does too) are not built: that call raises NotImplementedError.  The packed operands of the inference
+walk are keyed on every parameter's (address, version), so a no_grad evaluation after an optimizer step or an EMA swap sees the new weights.  `use_checkpoint=True` is accepted and runs WITHOUT activation
+recompute - the gradients are the same, only the memory saving is absent.
+
+Not built: `resblock_updown=False` (strided-conv Downsample / conv Upsample - the shipped SR checkpoint uses resblock_updown),
 class conditioning, `use_new_attention_order` is accepted (it only changes the pack-time re-ordering).
 """
 import math
@@ -222,8 +228,17 @@ class ImageUnet(nn.Module):
         W["emb_all"] = (torch.cat(Ws).contiguous(), torch.cat(bs).contiguous(), offs, off)
         W["time_embed"] = tuple(f32(P[k]) for k in ("time_embed.0.weight", "time_embed.0.bias", "time_embed.2.weight", "time_embed.2.bias"))
         W["out"] = (f32(P["out.0.weight"]), f32(P["out.0.bias"]), ops.pack_edge_weight(P["out.2.weight"]), f32(P["out.2.bias"]))
-        self._packed = (str(device), dt, W)
+        self._packed = (str(device), dt, W, self._weights_sig())
         return W
+
+    def _weights_sig(self):
+        """(address, version) of every parameter, as the multimodal engine keys its plan (engine.py): an optimizer step or an EMA swap on
+        the flat buffer (optim.FlatAdamW.step, TrainLoop._params_changed) bumps the versions, and the packed operands are rebuilt."""
+        return tuple((p.data_ptr(), p._version) for p in self.parameters())
+
+    def _packed_current(self, dev):
+        pk = self._packed
+        return pk is not None and pk[0] == str(dev) and pk[1] == self.dtype and pk[3] == self._weights_sig()
 
     # ------------------------------------------------------------------ forward
     def _res(self, x, semb, N, Hh, L, W, out=None):
@@ -272,9 +287,9 @@ class ImageUnet(nn.Module):
         if not src.is_cuda:
             raise MMDError("ImageUnet runs on the MI355X HIP path only (GPU tensors); there is no CPU/torch fallback")
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()) and src.requires_grad:
-            raise NotImplementedError("ImageUnet: the SR model is inference-only on the HIP path")
+            raise NotImplementedError("ImageUnet: gradients with respect to the input images are not built (parameters only)")
         dev = src.device
-        if self._packed is None or self._packed[0] != str(dev) or self._packed[1] != self.dtype:
+        if not self._packed_current(dev):
             self._pack(dev)
         W = self._packed[2]
         dt = self.dtype
@@ -347,8 +362,21 @@ class ImageUnet(nn.Module):
         ops.head_conv(h, w_out, b_out, out, N, 1, Hh, Hh, ops.TAPS_SPATIAL)
         return out.view(N, self.out_channels, Hh, Hh)
 
+    def _differentiable(self, *inputs):
+        """The differentiable walk when autograd is on and a parameter requires grad; an input that requires grad as well is refused
+        (parameters only).  With every parameter frozen the inference walk runs whatever the inputs say, as it always did."""
+        if not torch.is_grad_enabled() or not any(p.requires_grad for p in self.parameters()):
+            return False
+        if any(t.requires_grad for t in inputs):
+            raise NotImplementedError("ImageUnet: gradients with respect to the input images are not built (parameters only)")
+        return True
+
     def forward(self, x, timesteps, y=None):
         assert (y is not None) == (self.num_classes is not None), "must specify y if and only if the model is class-conditional"
+        if self._differentiable(x):
+            from .image_train_forward import image_train_forward, input_rows
+            H.require_cuda(x)
+            return image_train_forward(self, input_rows(x, self.dtype), tuple(x.shape), timesteps)
         return self._replay((x,), timesteps, lambda xs, t: self._run(xs[0], t))
 
     # ------------------------------------------------------------------ graph replay of the no-grad forward
@@ -364,7 +392,7 @@ class ImageUnet(nn.Module):
         if torch.is_grad_enabled() or os.environ.get("MMD_SR_GRAPH", "0") != "1":
             return body(tuple(t.float().contiguous() for t in inputs), timesteps.contiguous())
         dev = inputs[0].device
-        if self._packed is None or self._packed[0] != str(dev) or self._packed[1] != self.dtype:
+        if not self._packed_current(dev):
             self._pack(dev)
             self._drop_graphs()
         key = (tuple(tuple(t.shape) for t in inputs), timesteps.dtype, self.dtype, str(dev))
@@ -421,4 +449,11 @@ class ImageSuperResModel(ImageUnet):
             rows = ops.alloc(N * Hh * Ww, cpad, dtype=self.dtype, device=xx.device)
             ops.bilinear_concat_rows(xx, low, rows)           # [x | bilinear(low) | 0] as channels-last rows: the stem is a K = 9 * cpad GEMM
             return self._run(None, t, rows=rows, shape=(N, 2 * C, Hh, Ww))
+        if self._differentiable(x, low_res):
+            from .image_train_forward import image_train_forward
+            H.require_cuda(x, low_res)
+            N, C, Hh, Ww = x.shape
+            rows = ops.alloc(N * Hh * Ww, (2 * C + 7) // 8 * 8, dtype=self.dtype, device=x.device)
+            ops.bilinear_concat_rows(x.float().contiguous(), low_res.float().contiguous(), rows)
+            return image_train_forward(self, rows, (N, 2 * C, Hh, Ww), timesteps)
         return self._replay((x, low_res), timesteps, body)

@@ -1087,7 +1087,7 @@ def attn_bwd(q, q_off, kv, k_off, v_off, o, do, dq, dq_off, dkv, dk_off, dv_off,
               meta=("attn_bwd", 10 * nb * q_total * win * k_per_group * heads * ch, 0))
 
 
-MFMA_HEADS = (16, 32, 48, 64, 96, 128)
+MFMA_HEADS = (16, 32, 48, 64, 96, 128, 192)
 
 
 def attn_mfma_ok(t, ch):

@@ -425,6 +425,51 @@ def gen_sr_dpm():
         save(tag, low=low, noise=noise, sample=out)
 
 
+SR_TRAIN = {
+    # name: (flag overrides on top of SR_TINY, batch, timesteps, subsample stride, seed); t = 0 is there for the decoder-NLL branch of the vb term
+    "sr_tiny": (dict(), 2, [0, 977], 97, 81),
+    # the shipped channel family on 64 x 64 images: every attention is (768, 4 heads, 192) on 64 tokens, GroupNorms over 192 ... 1536 channels
+    "sr_w192": (dict(sr_num_channels=192, sr_attention_resolutions="8", sr_num_heads=4), 2, [3, 977], 997, 82),
+    # the shipped SR model (ssh_scripts/image_sr_train.sh) at 256 x 256.  Stride 1499, not the 997 of full_train_grads: 311 M parameters / 997
+    # is 1.25 MB of incompressible floats, over the 1 MiB limit for a committed file
+    "sr_full": (dict(large_size=256, small_size=64, sr_num_channels=192, sr_num_res_blocks=2, sr_attention_resolutions="8,16,32",
+                     sr_num_heads=4, sr_use_scale_shift_norm=True), 1, [412], 1499, 83),
+    "sr_tiny_nofilm": (dict(sr_use_scale_shift_norm=False, sr_learn_sigma=False), 2, [0, 977], 97, 84),
+}
+
+
+def gen_sr_train(only=None):
+    """Training step of the SR model (py_scripts/image_sr_train.py): diffusion.training_losses(model, x0, t, model_kwargs={"low_res": low},
+    noise=noise) and .backward() of the reference in train() mode with synth weights (the zero-initialised convs are non-zero).  Per
+    fixture: the loss terms, the L2 norm of EVERY parameter's gradient and every stride-th gradient element, with the parameter names.
+    Inputs: torch.Generator().manual_seed(seed), draw order x0 (uniform [-1, 1]), low (uniform [-1, 1]), noise (normal)."""
+    for name, (over, B, ts, stride, seed) in SR_TRAIN.items():
+        if only and name not in only:
+            continue
+        d, model, diff = _sr_build(**over)
+        model.train()          # dropout p = 0 -> deterministic
+        L, S = d["large_size"], d["small_size"]
+        g = th.Generator().manual_seed(seed)
+        x0 = th.rand(B, 3, L, L, generator=g) * 2 - 1
+        low = th.rand(B, 3, S, S, generator=g) * 2 - 1
+        noise = th.randn(B, 3, L, L, generator=g)
+        t = th.tensor(ts, dtype=th.int64)
+        losses = diff.training_losses(model, x0, t, model_kwargs={"low_res": low}, noise=noise)
+        losses["loss"].mean().backward()
+        names, norms, subs, offs = [], [], [], [0]
+        for k, p in model.named_parameters():
+            gr = p.grad.detach().flatten()
+            names.append(k)
+            norms.append(float(gr.double().norm()))
+            subs.append(gr[::stride].clone())
+            offs.append(offs[-1] + subs[-1].numel())
+        nz = sum(1 for v in norms if v > 1e-4 * max(norms))
+        print(f"{name}: {len(names)} tensors, {sum(p.numel() for p in model.parameters()) / 1e6:.1f} M parameters, "
+              f"{100.0 * nz / len(names):.1f} % of the norms above 1e-4 of the largest ({min(norms):.3g} ... {max(norms):.3g})")
+        save(f"{name}_train_grads", seed=seed, B=B, t=t, stride=stride, names=np.asarray(names), norms=np.asarray(norms), sub=th.cat(subs),
+             sub_off=np.asarray(offs), **{k: v.detach() for k, v in losses.items()})
+
+
 def gen_helpers():
     """q_mean_variance / q_posterior_mean_variance / _predict_* (gd:170-229,345-366) on random inputs."""
     f = flags("tiny", timestep_respacing="")
@@ -501,6 +546,7 @@ ALL = {
     "full_dpmpp_multistep2": lambda: gen_dpm("full_dpmpp_multistep2", 67, True, True, config="full", steps=10, order=2, skip_type="logSNR",
                                              method="multistep"),
     "full_train_grads": gen_train_grads_full,
+    "sr_train": gen_sr_train,
     "tiny_train_loss": lambda: gen_train_loss("tiny", 2, 31),
     "tiny_ls_train_loss": lambda: gen_train_loss("tiny", 2, 32, learn_sigma=True),
     # non-FiLM ResBlocks (use_scale_shift_norm=False, unet:473-477): h + emb_out, then the plain norm
