@@ -13,6 +13,7 @@ Layout: video rows (n, f, h, w) x C, audio rows (n, l) x C; API-layout conversio
 stem (InitialBlock) and head kernels.
 """
 import os
+from types import SimpleNamespace
 
 import torch
 
@@ -21,16 +22,12 @@ from . import ops
 from .ops import Geom
 
 
-_EMB_ON_AUDIO_STREAM = os.environ.get("MMD_EMB_AUX", "1") != "0"
+# A/B and diagnostic switches, read once at import (INTEGRATION.md section 4 has the table; the comments are where each one acts)
+_EMB_ON_AUDIO_STREAM = ops._flag("MMD_EMB_AUX")           # _time_embed
 _POOL_NOREUSE = os.environ.get("MMD_POOL_NOREUSE") == "1"      # diagnostics (tools/determinism_graph.py): every tensor keeps its own buffer
-# round 5: the out layers of the up ResBlocks at the input resolution (one upsample of the block's result instead of two of its operands);
-# MMD_UP_LOWRES=0: the reference's order of operations (A/B)
-_UP_LOWRES = os.environ.get("MMD_UP_LOWRES", "1") != "0"
-# round 5: a cross-attention block's audio-side attention runs behind its video-side attention and the video stream does not wait for it;
-# MMD_CROSS_SERIAL=0: both start together and each stream waits for the other's (A/B)
-_CROSS_SERIAL = os.environ.get("MMD_CROSS_SERIAL", "1") != "0"
-# round 5: GroupNorm statistics of resampled tensors from the resample launch's epilogue (mmd_resample_stats); =0: statistics passes (A/B)
-_RESAMPLE_STATS = os.environ.get("MMD_RESAMPLE_STATS", "1") != "0"
+_UP_LOWRES = ops._flag("MMD_UP_LOWRES")                   # _res_side
+_CROSS_SERIAL = ops._flag("MMD_CROSS_SERIAL")             # _cross
+_RESAMPLE_STATS = ops._flag("MMD_RESAMPLE_STATS")         # _resample_stats
 
 
 class _Pool:
@@ -85,7 +82,7 @@ class UNetEngine:
         self._recs = {}
         # (Round 3's in-launch statistics + affine - "tails": integer accumulators in the producers, the last block of the last producer
         # finalises - measured slower in rounds 3 and 5 and were removed from the library in round 6; DESIGN.md section 5 has the numbers.)
-        self._gn_small = os.environ.get("MMD_GN_SMALL", "1") != "0"
+        self._gn_small = ops._flag("MMD_GN_SMALL")
         self._vconv_fused = self._tattn_fused = self._tconv = self._aconv = dtype == torch.bfloat16
         self._deferred = []           # video-stream buffers a launch of the AUDIO stream still reads (see _cross): released at the next sync
         H.reap()
@@ -149,9 +146,6 @@ class UNetEngine:
         ent["cover"].append((c0, c0 + out.shape[1]))
         return ent["view"][:, c0 // 4:(c0 + out.shape[1]) // 4, :]
 
-    def _has_stats(self, out):
-        return self._rec_slice(out)[0] is not None
-
     def _resample_stats(self, out):
         """The record view a resample writing `out` fills (None: no record buffer, or a column slice its 16-byte record stores cannot
         address; MMD_RESAMPLE_STATS=0: the statistics pass - A/B)."""
@@ -171,8 +165,7 @@ class UNetEngine:
         """The record view a GroupNorm over x can finalize from: every column of x written by a statistics-emitting GEMM, contiguous
         slices that are multiples of 64 rows.  None -> the classic statistics pass."""
         ent, c0 = self._rec_slice(x)
-        if (ent is None or geom.inner != 1 or geom.tstride != 1 or geom.outer_stride != geom.Tn or geom.Tn % 64 or geom.S * geom.Tn != x.shape[0]
-                or c0 % 4 or x.shape[1] % 128):                    # quad records: groups must be whole quads
+        if ent is None or not geom.covers(x.shape[0]) or geom.Tn % 64 or c0 % 4 or x.shape[1] % 128:      # quad records: groups must be whole quads
             return None
         if ent.get("perm_unit", 0) and geom.Tn % ent["perm_unit"]:
             return None
@@ -257,7 +250,7 @@ class UNetEngine:
         """GroupNorm32(+FiLM)(+SiLU) -> 1x1 conv with the normalisation applied inside the GEMM loader."""
         C = x.shape[1]
         Cout = self.params[wkey].shape[0]
-        will_emit = True if (out is not None and self._has_stats(out)) else None    # the launch below emits out's statistics
+        will_emit = True if (out is not None and self._rec_slice(out)[0] is not None) else None    # the launch below emits out's statistics
         if not ops.gn_fusable(geom, C, Cout, x, will_emit, act):
             # wide outputs (qkv, deep levels) outside the row-strip kernel's shapes: every column tile would redo the normalisation
             # in its loader (measured 2x slower than materialising once), so normalise once and run the plain GEMM; likewise a strip
@@ -325,152 +318,164 @@ class UNetEngine:
         self._release(att)
         return out
 
-    def _res(self, v, a, layer, Hh, L, out_v=None, out_a=None):
-        """ResBlock (unet:434-495).  v [N*F*H*H, cin], a [N*L, cin].  Returns (v', a', H', L')."""
-        N, F = self.N, self.F
-        p, cin, cout = layer["prefix"], layer["cin"], layer["cout"]
-        ss = self.model.use_scale_shift_norm
-        film = self.emb_all[:, layer["emb_off"]: layer["emb_off"] + (2 * cout if ss else cout)]
-        fh = 2 if (layer["up"] or layer["down"]) else 1
-        Ho = Hh // 2 if layer["down"] else (Hh * 2 if layer["up"] else Hh)
-        Lo = L // 4 if layer["down"] else (L * 4 if layer["up"] else L)
-        mode = 0 if layer["down"] else 1
+    _wb = staticmethod(lambda key: (key + ".weight", key + ".bias"))      # (weight key, bias key) of the conv layer `key`
 
-        def stream(x, mod, rows_in, rows_out, out):
-            vid = mod == "video"
-            gin = Geom.per_sample(N, rows_in // N)
+    def _res_side(self, layer, vid, Hh, L):
+        """What one modality's half of a ResBlock is planned from: row counts, slice geometry, resample arguments, parameter keys."""
+        N, F = self.N, self.F
+        p, cout, ss = layer["prefix"], layer["cout"], self.model.use_scale_shift_norm
+        mod, conv = ("video", "video_conv") if vid else ("audio", "audio_conv")
+        resampled = layer["up"] or layer["down"]
+        Ho, Lo = (Hh // 2, L // 4) if layer["down"] else ((Hh * 2, L * 4) if layer["up"] else (Hh, L))
+        mode = 0 if layer["down"] else 1      # of ops.resample: average pool / nearest upsample
+        # Up blocks (round 5): everything behind the nearest upsample is pointwise - the out_layers norm (the statistics of a tensor whose
+        # every element is repeated fh * fw times ARE the statistics of the tensor), FiLM, SiLU, the 1x1x1 out conv, the skip
+        # connection (identity or 1x1x1 conv) and their sum - so up(skip(x)) + out_conv(act(norm(up(h)))) == up(skip(x) + out_conv(act(norm(h)))):
+        # the out layers run at the INPUT resolution (a quarter of the rows, h's producer statistics instead of a statistics pass) and ONE
+        # upsample writes the block's output (unet:441-448, 457-476; equal up to the rounding of the statistics sums)
+        low_out = layer["up"] and ss and _UP_LOWRES
+        if low_out and (layer["vattn"] or layer["aattn"]):
+            # (no shipped architecture builds one: it must fail loudly, not be computed without its attention)
+            raise H.MMDError(f"{p}: an upsampling ResBlock with self-attention is not supported by the low-resolution out layers")
+        rows_in, rows_out = (N * F * Hh * Hh, N * F * Ho * Ho) if vid else (N * L, N * Lo)
+        return SimpleNamespace(
+            vid=vid, p=p, layer=layer, cin=layer["cin"], cout=cout, ss=ss, Hh=Hh, L=L, Ho=Ho, Lo=Lo, rows_in=rows_in, rows_out=rows_out,
+            gin=Geom.per_sample(N, rows_in // N), rs=(N * F, Hh, Hh, 2, 2, mode) if vid else (N, 1, L, 1, 4, mode),
+            film=self.emb_all[:, layer["emb_off"]: layer["emb_off"] + (2 * cout if ss else cout)], resampled=resampled, low_out=low_out,
             # h feeds the out_layers GroupNorm directly unless it is resampled first (up / down blocks) or shifted by the embedding
             # (non-FiLM blocks): then its producer's epilogue statistics would describe a different tensor
-            # Up blocks (round 5): everything behind the nearest upsample is pointwise - the out_layers norm (the statistics of a tensor whose
-            # every element is repeated fh * fw times ARE the statistics of the tensor), FiLM, SiLU, the 1x1x1 out conv, the skip
-            # connection (identity or 1x1x1 conv) and their sum - so up(skip(x)) + out_conv(act(norm(up(h)))) == up(skip(x) + out_conv(act(norm(h)))):
-            # the out layers run at the INPUT resolution (a quarter of the rows, h's producer statistics instead of a statistics pass) and ONE
-            # upsample writes the block's output (unet:441-448, 457-476; equal up to the rounding of the statistics sums)
-            low_out = layer["up"] and ss and _UP_LOWRES
-            if low_out and (layer["vattn"] or layer["aattn"]):
-                # the low-resolution form returns before the attention branch below: an up block WITH attention (no shipped architecture
-                # builds one) must fail loudly, not be computed without its attention
-                raise H.MMDError(f"{p}: an upsampling ResBlock with self-attention is not supported by the low-resolution out layers")
-            hstats = (fh == 1 or low_out) and ss
-            t0 = t1 = h = None
-            if vid and self._vconv_fused and ops.vconv_fused_ok(x, cout, N, F, Hh, Hh):
-                # in_layers norm + SiLU, spatial 3x3 and temporal k=3 in ONE launch (ds1 level): the intermediate stays in LDS
-                ga, gb = self._gn_affine(x, f"{p}.{mod}_in_layers.0", gin, None)
-                h = self._alloc(rows_in, cout, stats=hstats, unit=rows_in // N)
-                wkey = f"{p}.video_in_layers.2.video_conv_spatial.weight"
-                wf = self._packed("vconv", wkey, lambda: ops.vconv_pack(
-                    self._gemm_w(wkey), self._gemm_w(f"{p}.video_in_layers.2.video_conv_temporal.weight")))
-                ops.vconv2d1d(x, wf, self._f32(f"{p}.video_in_layers.2.video_conv_spatial.bias"),
-                              self._f32(f"{p}.video_in_layers.2.video_conv_temporal.bias"), N, F, Hh, Hh, a=ga, b=gb, geom=gin, act=True,
-                              out=h, stats=self._stats_for(h, perm_unit=rows_in // N))
-                self._release(ga, gb)
-            elif vid and ops.halo_gn_ok(x, ops.TAPS_SPATIAL, (N * F, Hh, Hh), gin):
-                # in_layers norm + SiLU inside the 3x3 conv's halo stage: no normalised tensor in HBM (ds1 / ds2 levels)
-                ga, gb = self._gn_affine(x, f"{p}.{mod}_in_layers.0", gin, None)
-                t1 = ops.gn_conv_gemm(x, ga, gb, gin, True, self._gemm_w(f"{p}.video_in_layers.2.video_conv_spatial.weight"),
-                                      self._f32(f"{p}.video_in_layers.2.video_conv_spatial.bias"), ops.TAPS_SPATIAL, (N * F, Hh, Hh),
-                                      out=self._alloc(rows_in, cout))
-                self._release(ga, gb)
-                t0 = None
-            elif not vid and self._aconv and ops.aconv_ok(x, cout, N, L):
-                # in_layers norm + SiLU + dilated k = 3 conv in ONE launch (round 6): no normalised tensor, no gn_apply launch
-                ga, gb = self._gn_affine(x, f"{p}.{mod}_in_layers.0", gin, None)
-                h = self._alloc(rows_in, cout, stats=hstats, unit=rows_in // N)
-                ops.aconv(x, ga, gb, self._gemm_w(f"{p}.audio_in_layers.2.audio_conv.weight"), self._f32(f"{p}.audio_in_layers.2.audio_conv.bias"),
-                          N, L, layer["dilation"], act=True, out=h, stats=self._stats_for(h))
-                self._release(ga, gb)
-            else:
-                t0 = self._gn(x, f"{p}.{mod}_in_layers.0", gin, act=True)
-            if h is not None:
-                pass
-            elif vid:
-                if t0 is not None:
-                    t1 = ops.conv_gemm(t0, self._gemm_w(f"{p}.video_in_layers.2.video_conv_spatial.weight"),
-                                       self._f32(f"{p}.video_in_layers.2.video_conv_spatial.bias"), taps=ops.TAPS_SPATIAL,
-                                       dims=(N * F, Hh, Hh), out=self._alloc(rows_in, cout))
-                    self._release(t0)
-                h = self._alloc(rows_in, cout, stats=hstats, unit=rows_in // N)
-                wtk = f"{p}.video_in_layers.2.video_conv_temporal.weight"
-                if self._tconv and ops.tconv_ok(t1, cout, N, F, Hh * Hh):
-                    # the k = 3 conv along the frames with stationary activations (tap shift = DPP lane shift): bitwise the GEMM below
-                    ops.tconv(t1, self._packed("tconv", wtk, lambda: ops.tconv_pack(self._gemm_w(wtk))),
-                              self._f32(f"{p}.video_in_layers.2.video_conv_temporal.bias"), cout, N, F, Hh * Hh, out=h,
-                              stats=self._stats_for(h, perm_unit=rows_in // N))
-                else:
-                    ops.conv_gemm(t1, self._gemm_w(wtk), self._f32(f"{p}.video_in_layers.2.video_conv_temporal.bias"), **self._temporal(Hh),
-                                  out=h, **self._stats_kw(h))
-                self._release(t1)
-            else:
-                h = self._alloc(rows_in, cout, stats=hstats, unit=rows_in // N)
-                ops.conv_gemm(t0, self._gemm_w(f"{p}.audio_in_layers.2.audio_conv.weight"),
-                              self._f32(f"{p}.audio_in_layers.2.audio_conv.bias"), taps=ops.taps_audio(layer["dilation"]),
-                              dims=(L, 1, 1), out=h, **self._stats_kw(h))
-                self._release(t0)
-            xs = x
-            rs = (N * F, Hh, Hh, 2, 2, mode) if vid else (N, 1, L, 1, 4, mode)
-            conv = "video_conv" if vid else "audio_conv"
-            if low_out:
-                sk = x if cin == cout else self._pw(x, f"{p}.{mod}_skip_connection.{conv}.weight", f"{p}.{mod}_skip_connection.{conv}.bias")
-                ylow = self._alloc(rows_in, cout)
-                self._gn_pw(h, f"{p}.{mod}_out_layers.0", gin, True, f"{p}.{mod}_out_layers.3.{conv}.weight",
-                            f"{p}.{mod}_out_layers.3.{conv}.bias", film=film, residual=sk, out=ylow)
-                self._release(h)
-                if sk is not x:
-                    self._release(sk)
-                dest = self._alloc(rows_out, cout, stats=True, unit=rows_out // N) if out is None else out
-                ops.resample(ylow, dest, *rs, stats=self._resample_stats(dest))
-                self._release(ylow)
-                return dest
-            if fh != 1:        # conv at the input resolution, THEN resample both h and x (unet:441-448)
-                hp, xp = self._alloc(rows_out, cout, stats=ss, unit=rows_out // N), self._alloc(rows_out, cin)
-                ops.resample(h, hp, *rs, stats=self._resample_stats(hp))     # (the out_layers norm finalizes from the resample's records)
-                ops.resample(x, xp, *rs)
-                self._release(h)
-                h, xs = hp, xp
-            geom = Geom.per_sample(N, rows_out // N)
-            if not ss:
-                ops.add_rowbias(h, film, rows_out // N)
-            if cin != cout:
-                sk = self._pw(xs, f"{p}.{mod}_skip_connection.{conv}.weight", f"{p}.{mod}_skip_connection.{conv}.bias")
-            else:
-                sk = xs
-            attn_here = layer["vattn"] if vid else layer["aattn"]
-            # consumer of dest: the spatial-attention norm (per-frame slices), the audio-attention norm or the next block's norm (per sample)
-            dest = self._alloc(rows_out, cout, stats=True, unit=(Ho * Ho if (attn_here and vid) else rows_out // N)) \
-                if (attn_here or out is None) else out
-            self._gn_pw(h, f"{p}.{mod}_out_layers.0", geom, True, f"{p}.{mod}_out_layers.3.{conv}.weight",
-                        f"{p}.{mod}_out_layers.3.{conv}.bias", film=film if ss else None, residual=sk, out=dest)
-            self._release(h)
-            if sk is not xs:
-                self._release(sk)
-            if xs is not x:
-                self._release(xs)
-            if attn_here:
-                if vid and self._tattn_fused and ops._TATTN_PRE and ops.tattn_fused_ok(dest, self.model.num_heads, N, F, Ho * Ho):
-                    # spatial block up to its attention; its proj_out + residual ride in the fused temporal block's launch
-                    att = self._self_attn(dest, p + ".spatial_attention_block", "spatial", Ho, None, no_proj=True)
-                    fin = out if out is not None else self._alloc(rows_out, cout, stats=True, unit=rows_out // N)
-                    self._self_attn(dest, p + ".temporal_attention_block", "temporal", Ho, fin, pre=(att, p + ".spatial_attention_block"))
-                    self._release(att, dest)
-                elif vid:
-                    mid = self._self_attn(dest, p + ".spatial_attention_block", "spatial", Ho, self._alloc(rows_out, cout))
-                    self._release(dest)
-                    fin = out if out is not None else self._alloc(rows_out, cout, stats=True, unit=rows_out // N)
-                    self._self_attn(mid, p + ".temporal_attention_block", "temporal", Ho, fin)
-                    self._release(mid)
-                else:
-                    fin = out if out is not None else self._alloc(rows_out, cout, stats=True, unit=rows_out // N)
-                    self._self_attn(dest, p + ".audio_attention_block", "audio", Ho, fin)
-                    self._release(dest)
-                dest = fin
-            return dest
+            hstats=(not resampled or low_out) and ss, attn=layer["vattn"] if vid else layer["aattn"],
+            in_norm=f"{p}.{mod}_in_layers.0", in_conv=f"{p}.{mod}_in_layers.2.{conv}", out_norm=f"{p}.{mod}_out_layers.0",
+            out_conv=f"{p}.{mod}_out_layers.3.{conv}", skip=f"{p}.{mod}_skip_connection.{conv}")
 
-        ops.cur_sid, ops.cur_tag = 0, p + ":video"
-        vo = stream(v, "video", N * F * Hh * Hh, N * F * Ho * Ho, out_v)
-        ops.cur_sid, ops.cur_tag = 1, p + ":audio"
-        ao = stream(a, "audio", N * L, N * Lo, out_a)
-        ops.cur_sid, ops.cur_tag = 0, ""
-        return vo, ao, Ho, Lo
+    def _res(self, v, a, layer, Hh, L, out_v=None, out_a=None):
+        """ResBlock (unet:434-495).  v [N*F*H*H, cin], a [N*L, cin].  Returns (v', a', H', L')."""
+        sv, sa = self._res_side(layer, True, Hh, L), self._res_side(layer, False, Hh, L)
+        with ops.on_stream(0, tag=sv.p + ":video"):
+            vo = self._res_out(sv, v, self._res_video_in(sv, v), out_v)
+        with ops.on_stream(1, tag=sa.p + ":audio"):
+            ao = self._res_out(sa, a, self._res_audio_in(sa, a), out_a)
+        return vo, ao, sv.Ho, sv.Lo
+
+    def _res_video_in(self, s, x):
+        """in_layers of the video half: GroupNorm + SiLU, then VideoConv = spatial 3x3 and k = 3 along the frames.  Returns h."""
+        N, F, Hh = self.N, self.F, s.Hh
+        (ws, bs), (wt, bt) = self._wb(s.in_conv + "_spatial"), self._wb(s.in_conv + "_temporal")
+        if self._vconv_fused and ops.vconv_fused_ok(x, s.cout, N, F, Hh, Hh):
+            # in_layers norm + SiLU, spatial 3x3 and temporal k=3 in ONE launch (ds1 level): the intermediate stays in LDS
+            ga, gb = self._gn_affine(x, s.in_norm, s.gin, None)
+            h = self._alloc(s.rows_in, s.cout, stats=s.hstats, unit=s.rows_in // N)
+            wf = self._packed("vconv", ws, lambda: ops.vconv_pack(self._gemm_w(ws), self._gemm_w(wt)))
+            ops.vconv2d1d(x, wf, self._f32(bs), self._f32(bt), N, F, Hh, Hh, a=ga, b=gb, geom=s.gin, act=True, out=h,
+                          stats=self._stats_for(h, perm_unit=s.rows_in // N))
+            self._release(ga, gb)
+            return h
+        t1 = self._res_spatial(s, x, ws, bs)
+        h = self._alloc(s.rows_in, s.cout, stats=s.hstats, unit=s.rows_in // N)
+        if self._tconv and ops.tconv_ok(t1, s.cout, N, F, Hh * Hh):
+            # the k = 3 conv along the frames with stationary activations (tap shift = DPP lane shift): bitwise the GEMM below
+            ops.tconv(t1, self._packed("tconv", wt, lambda: ops.tconv_pack(self._gemm_w(wt))), self._f32(bt), s.cout, N, F, Hh * Hh, out=h,
+                      stats=self._stats_for(h, perm_unit=s.rows_in // N))
+        else:
+            ops.conv_gemm(t1, self._gemm_w(wt), self._f32(bt), **self._temporal(Hh), out=h, **self._stats_kw(h))
+        self._release(t1)
+        return h
+
+    def _res_spatial(self, s, x, ws, bs):
+        """GroupNorm + SiLU + the spatial 3x3 conv of the video in_layers where the fused VideoConv does not run."""
+        dims = (self.N * self.F, s.Hh, s.Hh)
+        if ops.halo_gn_ok(x, ops.TAPS_SPATIAL, dims, s.gin):
+            # in_layers norm + SiLU inside the 3x3 conv's halo stage: no normalised tensor in HBM (ds1 / ds2 levels)
+            ga, gb = self._gn_affine(x, s.in_norm, s.gin, None)
+            t1 = ops.gn_conv_gemm(x, ga, gb, s.gin, True, self._gemm_w(ws), self._f32(bs), ops.TAPS_SPATIAL, dims,
+                                  out=self._alloc(s.rows_in, s.cout))
+            self._release(ga, gb)
+            return t1
+        t0 = self._gn(x, s.in_norm, s.gin, act=True)
+        t1 = ops.conv_gemm(t0, self._gemm_w(ws), self._f32(bs), taps=ops.TAPS_SPATIAL, dims=dims, out=self._alloc(s.rows_in, s.cout))
+        self._release(t0)
+        return t1
+
+    def _res_audio_in(self, s, x):
+        """in_layers of the audio half: GroupNorm + SiLU + dilated k = 3 conv.  Returns h."""
+        N, L, dilation = self.N, s.L, s.layer["dilation"]
+        w, b = self._wb(s.in_conv)
+        if self._aconv and ops.aconv_ok(x, s.cout, N, L):
+            # norm + SiLU + conv in ONE launch (round 6): no normalised tensor, no gn_apply launch
+            ga, gb = self._gn_affine(x, s.in_norm, s.gin, None)
+            h = self._alloc(s.rows_in, s.cout, stats=s.hstats, unit=s.rows_in // N)
+            ops.aconv(x, ga, gb, self._gemm_w(w), self._f32(b), N, L, dilation, act=True, out=h, stats=self._stats_for(h))
+            self._release(ga, gb)
+            return h
+        t0 = self._gn(x, s.in_norm, s.gin, act=True)
+        h = self._alloc(s.rows_in, s.cout, stats=s.hstats, unit=s.rows_in // N)
+        ops.conv_gemm(t0, self._gemm_w(w), self._f32(b), taps=ops.taps_audio(dilation), dims=(L, 1, 1), out=h, **self._stats_kw(h))
+        self._release(t0)
+        return h
+
+    def _res_out_low(self, s, x, h, out):
+        """Up blocks: skip connection + out_layers at the INPUT resolution, then one upsample writes the result (see _res_side)."""
+        sk = x if s.cin == s.cout else self._pw(x, *self._wb(s.skip))
+        ylow = self._alloc(s.rows_in, s.cout)
+        self._gn_pw(h, s.out_norm, s.gin, True, *self._wb(s.out_conv), film=s.film, residual=sk, out=ylow)
+        self._release(h)
+        if sk is not x:
+            self._release(sk)
+        dest = self._alloc(s.rows_out, s.cout, stats=True, unit=s.rows_out // self.N) if out is None else out
+        ops.resample(ylow, dest, *s.rs, stats=self._resample_stats(dest))
+        self._release(ylow)
+        return dest
+
+    def _res_out(self, s, x, h, out):
+        """Behind the in_layers of one half: resample h and x (up / down blocks), skip connection + out_layers, self-attention."""
+        if s.low_out:
+            return self._res_out_low(s, x, h, out)
+        per = s.rows_out // self.N
+        xs = x
+        if s.resampled:        # conv at the input resolution, THEN resample both h and x (unet:441-448)
+            hp, xp = self._alloc(s.rows_out, s.cout, stats=s.ss, unit=per), self._alloc(s.rows_out, s.cin)
+            ops.resample(h, hp, *s.rs, stats=self._resample_stats(hp))     # (the out_layers norm finalizes from the resample's records)
+            ops.resample(x, xp, *s.rs)
+            self._release(h)
+            h, xs = hp, xp
+        if not s.ss:
+            ops.add_rowbias(h, s.film, per)
+        sk = self._pw(xs, *self._wb(s.skip)) if s.cin != s.cout else xs
+        # consumer of dest: the spatial-attention norm (per-frame slices), the audio-attention norm or the next block's norm (per sample)
+        dest = self._alloc(s.rows_out, s.cout, stats=True, unit=s.Ho * s.Ho if (s.attn and s.vid) else per) \
+            if (s.attn or out is None) else out
+        self._gn_pw(h, s.out_norm, Geom.per_sample(self.N, per), True, *self._wb(s.out_conv), film=s.film if s.ss else None,
+                    residual=sk, out=dest)
+        self._release(h)
+        if sk is not xs:
+            self._release(sk)
+        if xs is not x:
+            self._release(xs)
+        return self._res_attn(s, dest, out) if s.attn else dest
+
+    def _res_fin(self, s, out):
+        return out if out is not None else self._alloc(s.rows_out, s.cout, stats=True, unit=s.rows_out // self.N)
+
+    def _res_attn(self, s, dest, out):
+        """Self-attention behind a ResBlock half: spatial then temporal (video) or audio.  Consumes dest, returns the block's output."""
+        p, Ho = s.p, s.Ho
+        if not s.vid:
+            fin = self._res_fin(s, out)
+            self._self_attn(dest, p + ".audio_attention_block", "audio", Ho, fin)
+            self._release(dest)
+        elif self._tattn_fused and ops.tattn_pre_ok(dest, self.model.num_heads, self.N, self.F, Ho * Ho):
+            # spatial block up to its attention; its proj_out + residual ride in the fused temporal block's launch
+            att = self._self_attn(dest, p + ".spatial_attention_block", "spatial", Ho, None, no_proj=True)
+            fin = self._res_fin(s, out)
+            self._self_attn(dest, p + ".temporal_attention_block", "temporal", Ho, fin, pre=(att, p + ".spatial_attention_block"))
+            self._release(att, dest)
+        else:
+            mid = self._self_attn(dest, p + ".spatial_attention_block", "spatial", Ho, self._alloc(s.rows_out, s.cout))
+            self._release(dest)
+            fin = self._res_fin(s, out)
+            self._self_attn(mid, p + ".temporal_attention_block", "temporal", Ho, fin)
+            self._release(mid)
+        return fin
 
     def _cross(self, v, a, layer, Hh, L, out_v=None, out_a=None):
         """CrossAttentionBlock (unet:655-678) with arithmetic random-shift windows."""
@@ -480,49 +485,40 @@ class UNetEngine:
         HW, apf = Hh * Hh, int(L / F)
         if apf < 1:
             raise H.MMDError(f"cross attention needs at least one audio token per frame (L={L}, F={F})")
-        ops.cur_tag = p + ":cross"
-        ops.cur_sid = 0
-        vqkv = self._gn_pw(v, p + ".v_norm", Geom.per_sample(N, F * HW), False, p + ".v_qkv.weight", p + ".v_qkv.bias")
-        ops.cur_sid = 1
-        aqkv = self._gn_pw(a, p + ".a_norm", Geom.per_sample(N, L), False, p + ".a_qkv.weight", p + ".a_qkv.bias")
-        ops.record_sync(1, 0)      # video queries need the audio k/v ...
-        ops.record_sync(0, 1)      # ... and vice versa
-        # the video stream has now waited for everything recorded on the audio stream (the record_sync(1, 0) two lines up - the releases
-        # below depend on it): the video qkv buffers that earlier blocks' AUDIO attentions were still reading go back to the video pool
-        self._release(*self._deferred)
-        self._deferred = []
         sh = self.shift_dev[layer["shift_idx"]: layer["shift_idx"] + 1] if layer["shift"] else None
-        ops.cur_sid = 0
-        vatt = self._alloc(N * F * HW, C)
-        ops.attn(vqkv, aqkv, vatt, heads, ch, N, F, F * HW, HW, L, apf, win, shift_dev=sh)
-        if _CROSS_SERIAL:
-            # Round 5.  The two attentions of a block used to start together and each stream then waited for the OTHER's (buffer recycling):
-            # two MFMA-bound kernels shared the chip and the video chain - the critical path - paid for both.  Now the audio stream's
-            # attention starts BEHIND the video stream's (the audio chain has ~6 ms of slack per step), the video stream never waits for it
-            # (its proj_out follows its own attention at once), and the video qkv buffer the audio attention reads is parked until the
-            # next point where the video stream has waited for the audio stream anyway (the next block's first sync)
-            ops.record_sync(0, 1)
-            ops.cur_sid = 1
-            aatt = self._alloc(N * L, C)
-            ops.attn(aqkv, vqkv, aatt, heads, ch, N, F, L, apf, F * HW, HW, win, shift_dev=sh)
-            self._release(aqkv)    # audio pool: its readers are audio-stream launches and the video attention this stream has waited for
-            self._deferred.append(vqkv)
-        else:
-            ops.cur_sid = 1
-            aatt = self._alloc(N * L, C)
-            ops.attn(aqkv, vqkv, aatt, heads, ch, N, F, L, apf, F * HW, HW, win, shift_dev=sh)
-            ops.record_sync(0, 1)      # both attentions retired before either stream recycles the other's qkv buffer
-            ops.record_sync(1, 0)
-            self._release(vqkv, aqkv)
-        ops.cur_sid = 0
-        vo = out_v if out_v is not None else self._alloc(N * F * HW, C, stats=True, unit=F * HW)
-        self._pw(vatt, p + ".video_proj_out.video_conv.weight", p + ".video_proj_out.video_conv.bias", residual=v, out=vo)
-        self._release(vatt)
-        ops.cur_sid = 1
-        ao = out_a if out_a is not None else self._alloc(N * L, C, stats=True, unit=L)
-        self._pw(aatt, p + ".audio_proj_out.audio_conv.weight", p + ".audio_proj_out.audio_conv.bias", residual=a, out=ao)
-        self._release(aatt)
-        ops.cur_sid, ops.cur_tag = 0, ""
+        with ops.on_stream(0, tag=p + ":cross"):
+            vqkv = self._gn_pw(v, p + ".v_norm", Geom.per_sample(N, F * HW), False, *self._wb(p + ".v_qkv"))
+            with ops.on_stream(1):
+                aqkv = self._gn_pw(a, p + ".a_norm", Geom.per_sample(N, L), False, *self._wb(p + ".a_qkv"))
+            ops.record_sync(1, 0)      # video queries need the audio k/v ...
+            ops.record_sync(0, 1)      # ... and vice versa
+            # (the releases depend on the record_sync(1, 0) above) the video qkv buffers earlier blocks' AUDIO attentions read go back
+            self._release(*self._deferred)
+            self._deferred = []
+            vatt = self._alloc(N * F * HW, C)
+            ops.attn(vqkv, aqkv, vatt, heads, ch, N, F, F * HW, HW, L, apf, win, shift_dev=sh)
+            if _CROSS_SERIAL:
+                # Round 5.  The two attentions of a block used to start together and each stream then waited for the OTHER's: two
+                # MFMA-bound kernels shared the chip and the video chain - the critical path - paid for both.  Now the audio stream's
+                # starts BEHIND the video stream's (the audio chain has ~6 ms of slack per step) and the video stream never waits for it
+                ops.record_sync(0, 1)
+            with ops.on_stream(1):
+                aatt = self._alloc(N * L, C)
+                ops.attn(aqkv, vqkv, aatt, heads, ch, N, F, L, apf, F * HW, HW, win, shift_dev=sh)
+            if _CROSS_SERIAL:
+                self._release(aqkv)    # audio pool: its readers are audio-stream launches and the video attention this stream has waited for
+                self._deferred.append(vqkv)    # parked until the video stream has next waited for the audio stream (the next block's first sync)
+            else:
+                ops.record_sync(0, 1)      # both attentions retired before either stream recycles the other's qkv buffer
+                ops.record_sync(1, 0)
+                self._release(vqkv, aqkv)
+            vo = out_v if out_v is not None else self._alloc(N * F * HW, C, stats=True, unit=F * HW)
+            self._pw(vatt, *self._wb(p + ".video_proj_out.video_conv"), residual=v, out=vo)
+            self._release(vatt)
+            with ops.on_stream(1):
+                ao = out_a if out_a is not None else self._alloc(N * L, C, stats=True, unit=L)
+                self._pw(aatt, *self._wb(p + ".audio_proj_out.audio_conv"), residual=a, out=ao)
+                self._release(aatt)
         return vo, ao
 
     # ------------------------------------------------------------------ plan
@@ -573,141 +569,113 @@ class UNetEngine:
                          else (fn, args, name, meta, sid, tag) for fn, args, name, meta, sid, tag in self.plan]
 
     def _record(self, t_tensor, arch_in, arch_mid, arch_out):
-        m, N, F, dt = self.model, self.N, self.F, self.dtype
-        mc = self.mc
-        # fork first: the audio stream (which has ~3x less work per step than the video stream) computes the timestep embedding and the
-        # FiLM table of every ResBlock, while the video stream starts on its stem convs at once; the video stream picks the table up
-        # behind its stem (the first consumer is the first ResBlock's out-norm) - ~30 us off the step's critical path
-        ops.cur_sid = 0
-        ops.record_sync(0, 1)      # the audio stream starts behind the host-side input copies
-        ops.cur_sid = 1 if _EMB_ON_AUDIO_STREAM else 0
-        ops.temb(t_tensor, mc, self._f32("time_embed.0.weight"), self._f32("time_embed.0.bias"),
-                 self._f32("time_embed.2.weight"), self._f32("time_embed.2.bias"), self.emb_silu)
-        ops.linear(self.emb_silu, self.emb_W, self.emb_b, self.emb_all)
-        ops.cur_sid = 0
-        film_joined = not _EMB_ON_AUDIO_STREAM
-        if not _EMB_ON_AUDIO_STREAM:
-            ops.record_sync(0, 1)  # (A/B switch: embedding on the video stream, the audio stream waits for the table)
-
+        N, F = self.N, self.F
         # consumer channel split of every skip: output block k reads [h (ch_prev) | skip (ich)]
         skip_cols = []
         ch = arch_mid[-1]["cout"]
         for layers in arch_out:
-            ich = layers[0]["skip_ch"]
-            skip_cols.append((ch, ich))
+            skip_cols.append((ch, layers[0]["skip_ch"]))
             ch = layers[-1]["cout"] if layers[-1]["kind"] == "res" else layers[-1]["ch"]
+        with ops.on_stream(0):
+            self._time_embed(t_tensor)
+            Hh, L = self.H0, self.L0
+            cat_bufs = []   # per input block: (video cat buffer, audio cat buffer) for its consumer
+            v = a = None
+            nin = len(arch_in)
+            for i, layers in enumerate(arch_in):
+                chp, ich = skip_cols[nin - 1 - i]
+                down = any(layer["kind"] == "res" and layer["down"] for layer in layers)
+                Ho, Lo = (Hh // 2, L // 4) if down else (Hh, L)      # geometry of this block's OUTPUT
+                vcat = self._alloc(N * F * Ho * Ho, chp + ich, stats=True, unit=F * Ho * Ho)
+                with ops.on_stream(1):
+                    acat = self._alloc(N * Lo, chp + ich, stats=True, unit=Lo)
+                cat_bufs.append((vcat, acat))
+                v, a, Hh, L = self._run_block(layers, v, a, Hh, L, vcat[:, chp:], acat[:, chp:])
+            # the middle block and every output block but the last write the left slice of the next output block's concat buffers
+            left = [(vc[:, :chp], ac[:, :chp]) for (vc, ac), (chp, _) in zip(reversed(cat_bufs), skip_cols)] + [(None, None)]
+            v, a, Hh, L = self._run_block(arch_mid, v, a, Hh, L, *left[0])
+            for k, layers in enumerate(arch_out):
+                vcat, acat = cat_bufs[nin - 1 - k]
+                v, a, Hh, L = self._run_block(layers, vcat, acat, Hh, L, *left[k + 1])
+                self._release(vcat, acat)
+            self._heads(v, a, Hh, L)
+            if self._deferred:
+                # the last cross block's video qkv buffer (parked while the AUDIO stream's attention read it, see _cross): back to the
+                # video pool behind an explicit audio -> video sync, so that no release depends on the caller's join
+                ops.record_sync(1, 0)
+                self._release(*self._deferred)
+                self._deferred = []
+        # NOTE: no join here - the caller appends per-stream work (DDPM update) and then joins (join_plan)
 
-        Hh, L = self.H0, self.L0
-        cat_bufs = []   # per input block: (video cat buffer, audio cat buffer) for its consumer
-        v = a = None
-        nin = len(arch_in)
-        for i, layers in enumerate(arch_in):
-            chp, ich = skip_cols[nin - 1 - i]
-            # geometry of this block's OUTPUT
-            Ho, Lo = Hh, L
-            for layer in layers:
-                if layer["kind"] == "res" and layer["down"]:
-                    Ho, Lo = Hh // 2, L // 4
-            ops.cur_sid = 0
-            vcat = self._alloc(N * F * Ho * Ho, chp + ich, stats=True, unit=F * Ho * Ho)
-            ops.cur_sid = 1
-            acat = self._alloc(N * Lo, chp + ich, stats=True, unit=Lo)
-            ops.cur_sid = 0
-            cat_bufs.append((vcat, acat))
-            ov, oa = vcat[:, chp:], acat[:, chp:]
-            for j, layer in enumerate(layers):
-                last = j == len(layers) - 1
-                tv, ta = (ov, oa) if last else (None, None)
-                if layer["kind"] == "init":
-                    C0 = layer["cout"]
-                    p = layer["prefix"]
-                    s1 = self._alloc(N * F * Hh * Hh, C0)
-                    ops.stem_conv(self.x_video, self._edge_w(p + ".video_conv.video_conv_spatial.weight"),
-                                  self._f32(p + ".video_conv.video_conv_spatial.bias"), s1, N, F, self.Cv_in, Hh, Hh,
-                                  ops.TAPS_SPATIAL)
-                    nv = tv if tv is not None else self._alloc(N * F * Hh * Hh, C0, stats=True, unit=F * Hh * Hh)
-                    ops.conv_gemm(s1, self._gemm_w(p + ".video_conv.video_conv_temporal.weight"),
-                                  self._f32(p + ".video_conv.video_conv_temporal.bias"), **self._temporal(Hh), out=nv,
-                                  **self._stats_kw(nv))
-                    self._release(s1)
-                    ops.record_sync(1, 0)      # the FiLM table is ready (recorded behind the two embedding launches only)
-                    film_joined = True
-                    ops.cur_sid = 1
-                    na = ta if ta is not None else self._alloc(N * L, C0)
-                    ops.stem_conv(self.x_audio, self._edge_w(p + ".audio_conv.audio_conv.weight"),
-                                  self._f32(p + ".audio_conv.audio_conv.bias"), na, N, 1, self.Ca_in, 1, L,
-                                  [(0, 0, -1), (0, 0, 0), (0, 0, 1)])
-                    ops.cur_sid = 0
-                elif layer["kind"] == "res":
-                    if not film_joined:        # (an architecture without an init layer in front of its first ResBlock)
-                        ops.record_sync(1, 0)
-                        film_joined = True
-                    nv, na, Hh, L = self._res(v, a, layer, Hh, L, tv, ta)
-                else:
-                    nv, na = self._cross(v, a, layer, Hh, L, tv, ta)
-                if j > 0:            # intermediates inside a block are ours; block inputs belong to the skip stack
-                    self._release(v, a)
-                v, a = nv, na
+    def _time_embed(self, t_tensor):
+        """Fork first: the audio stream (which has ~3x less work per step than the video stream) computes the timestep embedding and the
+        FiLM table of every ResBlock, while the video stream starts on its stem convs at once; the video stream picks the table up
+        behind its stem (the first consumer is the first ResBlock's out-norm) - ~30 us off the step's critical path."""
+        ops.record_sync(0, 1)      # the audio stream starts behind the host-side input copies
+        with ops.on_stream(1 if _EMB_ON_AUDIO_STREAM else 0):
+            ops.temb(t_tensor, self.mc, *(self._f32(f"time_embed.{i}.{wb}") for i in (0, 2) for wb in ("weight", "bias")), self.emb_silu)
+            ops.linear(self.emb_silu, self.emb_W, self.emb_b, self.emb_all)
+        self._film_joined = not _EMB_ON_AUDIO_STREAM
+        if not _EMB_ON_AUDIO_STREAM:
+            ops.record_sync(0, 1)  # (MMD_EMB_AUX=0: embedding on the video stream, the audio stream waits for the table)
 
-        # ---- middle: last layer writes the left slice of the first output block's concat buffer
-        def run_block(layers, v, a, Hh, L, ov, oa, own_input):
-            for j, layer in enumerate(layers):
-                last = j == len(layers) - 1
-                tv, ta = (ov, oa) if last else (None, None)
-                if layer["kind"] == "res":
-                    nv, na, Hh, L = self._res(v, a, layer, Hh, L, tv, ta)
-                else:
-                    nv, na = self._cross(v, a, layer, Hh, L, tv, ta)
-                if j > 0 or own_input:
-                    self._release(v, a)
-                v, a = nv, na
-            return v, a, Hh, L
-
-        vcat, acat = cat_bufs[-1]
-        chp, _ = skip_cols[0]
-        v, a, Hh, L = run_block(arch_mid, v, a, Hh, L, vcat[:, :chp], acat[:, :chp], own_input=False)
-
-        # ---- output blocks
-        for k, layers in enumerate(arch_out):
-            vcat, acat = cat_bufs[nin - 1 - k]
-            if k + 1 < len(arch_out):
-                nvcat, nacat = cat_bufs[nin - 2 - k]
-                chn, _ = skip_cols[k + 1]
-                ov, oa = nvcat[:, :chn], nacat[:, :chn]
+    def _run_block(self, layers, v, a, Hh, L, ov, oa):
+        """One input / middle / output block; its last layer writes (ov, oa) where given.  The block's input stays its caller's."""
+        for j, layer in enumerate(layers):
+            tv, ta = (ov, oa) if j == len(layers) - 1 else (None, None)
+            if layer["kind"] == "init":
+                nv, na = self._init(layer, Hh, L, tv, ta)
+            elif layer["kind"] == "res":
+                if not self._film_joined:        # (an architecture without an init layer in front of its first ResBlock)
+                    ops.record_sync(1, 0)
+                    self._film_joined = True
+                nv, na, Hh, L = self._res(v, a, layer, Hh, L, tv, ta)
             else:
-                ov = oa = None
-            v, a, Hh, L = run_block(layers, vcat, acat, Hh, L, ov, oa, own_input=False)
-            self._release(vcat, acat)
+                nv, na = self._cross(v, a, layer, Hh, L, tv, ta)
+            if j > 0:
+                self._release(v, a)
+            v, a = nv, na
+        return v, a, Hh, L
 
-        # ---- heads: GN -> SiLU -> conv (unet:1003-1012), fp32 API-layout outputs
-        ops.cur_sid = 0
+    def _init(self, layer, Hh, L, tv, ta):
+        """InitialBlock: the stem convs from the fp32 API-layout inputs; the video stream joins the FiLM table behind its stem."""
+        N, F, C0, p = self.N, self.F, layer["cout"], layer["prefix"]
+        (ws, bs), (wt, bt), (wa, ba) = (self._wb(p + k) for k in (".video_conv.video_conv_spatial", ".video_conv.video_conv_temporal",
+                                                                  ".audio_conv.audio_conv"))
+        s1 = self._alloc(N * F * Hh * Hh, C0)
+        ops.stem_conv(self.x_video, self._edge_w(ws), self._f32(bs), s1, N, F, self.Cv_in, Hh, Hh, ops.TAPS_SPATIAL)
+        nv = tv if tv is not None else self._alloc(N * F * Hh * Hh, C0, stats=True, unit=F * Hh * Hh)
+        ops.conv_gemm(s1, self._gemm_w(wt), self._f32(bt), **self._temporal(Hh), out=nv, **self._stats_kw(nv))
+        self._release(s1)
+        ops.record_sync(1, 0)      # the FiLM table is ready (recorded behind the two embedding launches only)
+        self._film_joined = True
+        with ops.on_stream(1):
+            na = ta if ta is not None else self._alloc(N * L, C0)
+            ops.stem_conv(self.x_audio, self._edge_w(wa), self._f32(ba), na, N, 1, self.Ca_in, 1, L, [(0, 0, -1), (0, 0, 0), (0, 0, 1)])
+        return nv, na
+
+    def _heads(self, v, a, Hh, L):
+        """GN -> SiLU -> conv (unet:1003-1012) into the fp32 API-layout outputs; consumes v and a."""
+        N, F = self.N, self.F
         gh = Geom.per_sample(N, F * Hh * Hh)
-        hw = self._edge_w("video_out.2.video_conv.weight")
+        (wv, bv), (wa, ba) = self._wb("video_out.2.video_conv"), self._wb("audio_out.2.audio_conv")
+        hw = self._edge_w(wv)
         hv = None
         if ops.head_gemm_ok(v, hw, gh):
             # norm + SiLU in the operand registers of a GEMM over (tap, channel) outputs, then a gather over the taps (round 5)
             ga, gb = self._gn_affine(v, "video_out.0", gh, None)
             NO = hw.shape[0] * hw.shape[2]
             P = self._alloc(NO, v.shape[0], torch.float32)
-            ops.head_gemm(v, ga, gb, gh, True, self._packed("head_gemm", "video_out.2.video_conv.weight", lambda: ops.head_gemm_pack(hw)), P, NO)
-            ops.head_gather(P, self._f32("video_out.2.video_conv.bias"), self.out_video, N, F, Hh, Hh, hw.shape[2], ops.TAPS_3D)
+            ops.head_gemm(v, ga, gb, gh, True, self._packed("head_gemm", wv, lambda: ops.head_gemm_pack(hw)), P, NO)
+            ops.head_gather(P, self._f32(bv), self.out_video, N, F, Hh, Hh, hw.shape[2], ops.TAPS_3D)
             self._release(ga, gb, P)
         else:
             hv = self._gn(v, "video_out.0", gh, act=True)
-            ops.head_conv(hv, hw, self._f32("video_out.2.video_conv.bias"), self.out_video, N, F, Hh, Hh, ops.TAPS_3D)
-        ops.cur_sid = 1
-        ha = self._gn(a, "audio_out.0", Geom.per_sample(N, L), act=True)
-        ops.head_conv(ha, self._edge_w("audio_out.2.audio_conv.weight"), self._f32("audio_out.2.audio_conv.bias"),
-                      self.out_audio, N, 1, 1, L, [(0, 0, -1), (0, 0, 0), (0, 0, 1)])
-        ops.cur_sid = 0
+            ops.head_conv(hv, hw, self._f32(bv), self.out_video, N, F, Hh, Hh, ops.TAPS_3D)
+        with ops.on_stream(1):
+            ha = self._gn(a, "audio_out.0", Geom.per_sample(N, L), act=True)
+            ops.head_conv(ha, self._edge_w(wa), self._f32(ba), self.out_audio, N, 1, 1, L, [(0, 0, -1), (0, 0, 0), (0, 0, 1)])
         self._release(hv, ha, v, a)
-        if self._deferred:
-            # the last cross block's video qkv buffer (parked while the AUDIO stream's attention read it, see _cross): back to the video
-            # pool behind an explicit audio -> video sync, so that no release depends on the caller's join
-            ops.record_sync(1, 0)
-            self._release(*self._deferred)
-            self._deferred = []
-        # NOTE: no join here - the caller appends per-stream work (DDPM update) and then joins (join_plan)
 
     # ------------------------------------------------------------------ execution
     def set_inputs(self, video, audio, timesteps, shifts):

@@ -1,9 +1,9 @@
-"""Thin per-op Python wrappers over the C-ABI (one function per libmmd entry point).
+"""Per-op Python wrappers over the C-ABI (one function per libmmd entry point) and the routing predicates (`*_ok`, `*_pinned`) that
+say which kernel a launch may run on.  Every MMD_* switch read here is listed in INTEGRATION.md (section 4).
 
-Activations are 2-D torch tensors [rows, C] with stride(1) == 1 and any row stride (a column slice of a
-wider buffer is fine); torch is used for device memory and the current stream only - every arithmetic
-op runs in libmmd."""
-import math
+Activations are 2-D torch tensors [rows, C] with stride(1) == 1 and any row stride (a column slice of a wider buffer is fine); torch
+is used for device memory and the current stream only - every arithmetic op runs in libmmd."""
+import contextlib
 import os
 
 import torch
@@ -42,8 +42,24 @@ def alloc(*shape, dtype, device):
     return t
 
 
+def _flag(name):      # an on / off switch of the environment: on unless the variable is "0"
+    return os.environ.get(name, "1") != "0"
+
+
 cur_sid = 0      # launch stream of the ops being recorded: 0 = video/main stream, 1 = audio stream
 cur_tag = ""     # which reference module the recorded launches belong to (bench: per-block roofline accounting)
+
+
+@contextlib.contextmanager
+def on_stream(sid, tag=None):
+    """The ops recorded inside the block launch on stream `sid` (under `tag`; None keeps the current one).  Nothing else assigns these."""
+    global cur_sid, cur_tag
+    prev = cur_sid, cur_tag
+    cur_sid, cur_tag = sid, cur_tag if tag is None else tag
+    try:
+        yield
+    finally:
+        cur_sid, cur_tag = prev
 
 
 def _dispatch(name, *args, meta=None):
@@ -123,6 +139,13 @@ class Geom:
     def args(self):
         return (self.S, self.Tn, self.inner, self.outer_stride, self.inner_stride, self.tstride)
 
+    @property
+    def contiguous(self):          # slice s is rows [s * Tn, (s + 1) * Tn)
+        return self.inner == 1 and self.tstride == 1 and self.outer_stride == self.Tn
+
+    def covers(self, rows):        # contiguous slices that tile exactly `rows` rows
+        return self.contiguous and self.S * self.Tn == rows
+
 
 def _chk2d(t):
     if t.dim() != 2 or t.stride(1) != 1:
@@ -157,7 +180,7 @@ def gn_finalize_stats(rec, gamma, beta, geom: Geom, film=None, a=None, b=None, m
     C = rec.shape[1] * 4
     if C % 128:
         raise H.MMDError("gn_finalize_stats: the normalised channels must be a multiple of 128 (groups of whole quads)")
-    if geom.inner != 1 or geom.tstride != 1 or geom.outer_stride != geom.Tn or geom.Tn % 64 or rec.shape[0] * 64 != geom.S * geom.Tn:
+    if not geom.covers(rec.shape[0] * 64) or geom.Tn % 64:
         raise H.MMDError("gn_finalize_stats: needs contiguous slices that are multiples of 64 rows")
     a = alloc(geom.S, C, dtype=torch.float32, device=rec.device) if a is None else a
     b = alloc(geom.S, C, dtype=torch.float32, device=rec.device) if b is None else b
@@ -201,7 +224,7 @@ def gn_small(x, gamma, beta, geom: Geom, act=False, out=None):
 # One-launch GroupNorm for slices of a few hundred rows (mmd_gn_group): used where a norm has NO producer-side records to finalize from
 # and its (group, slice) fits a block's registers - the 400-row audio samples at ds8 (400 % 64 != 0: gn_stats there is a partial
 # launch + a finalize launch, then gn_apply).  MMD_GN_GROUP=0 switches it off (A/B).
-_GN_GROUP = os.environ.get("MMD_GN_GROUP", "1") != "0"
+_GN_GROUP = _flag("MMD_GN_GROUP")
 
 
 def gn_group_ok(x, geom: Geom):
@@ -338,7 +361,7 @@ def halo_tile_ok(x, taps, dims):
 # tile 133 = the halo-tile main loop on 16 x 16 patches (8 waves, one block per CU, three-slot weight ring): same K order as tile 130,
 # bitwise the same output, so wherever tile 130 is pinned and the frame sides are multiples of 16 the faster of the two may run
 # (MMD_HALO16=0: always tile 130).
-_HALO16 = os.environ.get("MMD_HALO16", "1") != "0"
+_HALO16 = _flag("MMD_HALO16")
 
 
 def halo_tile_code(x, taps, dims):
@@ -350,7 +373,10 @@ def halo_tile_code(x, taps, dims):
 
 
 def _stats_args(stats, M, Cout):
-    """stats: fp32 view [M / 64, Cout / 4, 2] (a quad-column slice of the output's record buffer) -> (pointer, row stride in float2)."""
+    """stats: fp32 view [M / 64, Cout / 4, 2] (a quad-column slice of the output's record buffer) -> (pointer, row stride in float2);
+    None (no statistics wanted) -> (None, 0)."""
+    if stats is None:
+        return None, 0
     if (stats.dtype != torch.float32 or Cout % 4 or tuple(stats.shape) != (M // 64, Cout // 4, 2) or M % 64 or stats.stride(1) != 2
             or stats.stride(2) != 1):
         raise H.MMDError(f"GEMM output statistics: expected an fp32 [M/64, Cout/4, 2] view, got {tuple(stats.shape)} strides {stats.stride()}")
@@ -396,8 +422,7 @@ def strip_tile_ok(x, Cout, taps=TAPS_1, stats=None, geom=None, base=False):
         return False
     if base and (len(taps) != 1 or K == 512 or (stats is not None and rf != 2)):
         return False
-    if geom is not None and not (len(taps) == 1 and geom.inner == 1 and geom.tstride == 1 and geom.outer_stride == geom.Tn
-                                 and geom.Tn >= 128 * rf and geom.S * geom.Tn == M):
+    if geom is not None and not (len(taps) == 1 and geom.covers(M) and geom.Tn >= 128 * rf):
         return False
     return True
 
@@ -425,14 +450,26 @@ def ring_tile_candidate(x, Cout, ntaps):
             and ((M + 127) // 128) * ((Cout + 127) // 128) <= 384)
 
 
+def _chk_conv_w(op, x, w, ntaps):
+    if w.dtype != x.dtype or w.shape[1] != ntaps * x.shape[1] or not w.is_contiguous():
+        raise H.MMDError(f"{op}: weight {tuple(w.shape)} {w.dtype} does not match input {tuple(x.shape)} {x.dtype} x {ntaps} taps")
+
+
+def _conv_meta(op, x, Cout, ntaps, tile, residual):
+    """(label, flops, HBM bytes) of a conv-as-GEMM launch: x and the weights read once, the output written (and the residual read)."""
+    M, Cin = x.shape
+    es = x.element_size()
+    nbytes = es * (M * Cin + M * Cout * (2 if residual is not None else 1) + Cout * Cin * ntaps) + 4 * Cout
+    return (f"{op}<{'bf16' if es == 2 else 'f32'},{_tile_name(tile)}>[M={M},K={Cin * ntaps},N={Cout}]", 2 * M * Cout * Cin * ntaps, nbytes)
+
+
 def conv_gemm(x, w, bias, taps=TAPS_1, dims=(1, 1, 1), residual=None, out=None, tile=0, stats=None):
     """x [M, Cin]; w packed [Cout, ntaps*Cin] in x.dtype; bias fp32 [Cout] or None.  stats (optional): record view that receives
     the GroupNorm statistics of the output (include/mmd.h: mmd_conv_gemm_stats)."""
     _chk2d(x)
     M, Cin = x.shape
     Cout = w.shape[0]
-    if w.dtype != x.dtype or w.shape[1] != len(taps) * Cin or not w.is_contiguous():
-        raise H.MMDError(f"conv_gemm: weight {tuple(w.shape)} {w.dtype} does not match input {tuple(x.shape)} {x.dtype} x {len(taps)} taps")
+    _chk_conv_w("conv_gemm", x, w, len(taps))
     out = alloc(M, Cout, dtype=x.dtype, device=x.device) if out is None else out
     _chk2d(out)
     arr, nt = H.taps_array(taps)
@@ -453,13 +490,11 @@ def conv_gemm(x, w, bias, taps=TAPS_1, dims=(1, 1, 1), residual=None, out=None, 
             cands = cands + (132,)
         tile = _pick_tile((es, M, Cin, nt, Cout, residual is not None, False, tuple(dims) if 130 in cands else None),
                           lambda t: H.call("mmd_conv_gemm", *base, t, H.stream_handle()), M, Cout, cands, out=out, scratch=(x, residual))
-    flops = 2 * M * Cout * Cin * nt
-    nbytes = es * (M * Cin + M * Cout * (2 if residual is not None else 1) + Cout * Cin * nt) + 4 * Cout
-    label = f"conv_gemm<{'bf16' if es == 2 else 'f32'},{_tile_name(tile)}>[M={M},K={Cin * nt},N={Cout}]"
+    meta = _conv_meta("conv_gemm", x, Cout, nt, tile, residual)
     if stats is not None:
-        _dispatch("mmd_conv_gemm_stats", *base, tile, *_stats_args(stats, M, Cout), meta=(label, flops, nbytes))
+        _dispatch("mmd_conv_gemm_stats", *base, tile, *_stats_args(stats, M, Cout), meta=meta)
     else:
-        _dispatch("mmd_conv_gemm", *base, tile, meta=(label, flops, nbytes))
+        _dispatch("mmd_conv_gemm", *base, tile, meta=meta)
     return out
 
 
@@ -484,6 +519,11 @@ def strip_column_split(M, K, Cout):
     return n
 
 
+def gn_tiled_ok(geom: Geom, Cin, Cout):
+    """Launches the tiled loader of mmd_gn_conv1x1 accepts: contiguous slices of >= 128 rows, narrow K and N."""
+    return geom.contiguous and geom.Tn >= 128 and Cin <= 256 and (Cout + 127) // 128 <= 2
+
+
 def gn_fusable(geom: Geom, Cin, Cout, x=None, stats=None, act=False):
     """Whether GroupNorm can ride in the 1x1 GEMM: in the tiled loader (contiguous slices of >= 128 rows, narrow K and N: every
     column tile redoes the normalisation) or, given the input x (and whether the launch will emit output statistics), in the
@@ -497,8 +537,7 @@ def gn_fusable(geom: Geom, Cin, Cout, x=None, stats=None, act=False):
         if not strip_tile_pinned(x, Cout, stats=stats, geom=geom):
             return False                                   # slices the strip cannot fuse: gn_apply + strip GEMM
         return not (act and strip_column_split(x.shape[0], Cin, Cout) > 2)
-    return (geom.inner == 1 and geom.tstride == 1 and geom.outer_stride == geom.Tn and geom.Tn >= 128 and Cin <= 256
-            and (Cout + 127) // 128 <= 2)
+    return gn_tiled_ok(geom, Cin, Cout)
 
 
 def gn_conv1x1(x, a, b, geom: Geom, act, w, bias, residual=None, out=None, tile=0, stats=None):
@@ -506,14 +545,12 @@ def gn_conv1x1(x, a, b, geom: Geom, act, w, bias, residual=None, out=None, tile=
     _chk2d(x)
     M, Cin = x.shape
     Cout = w.shape[0]
-    if w.dtype != x.dtype or w.shape[1] != Cin or not w.is_contiguous():
-        raise H.MMDError(f"gn_conv1x1: weight {tuple(w.shape)} {w.dtype} does not match input {tuple(x.shape)} {x.dtype}")
+    _chk_conv_w("gn_conv1x1", x, w, 1)
     out = alloc(M, Cout, dtype=x.dtype, device=x.device) if out is None else out
     _chk2d(out)
     es = x.element_size()
     # capability, not preference: an explicit tile is checked against what THAT main loop can do (gn_fusable is the caller's cost rule)
-    tiled_ok = (geom.inner == 1 and geom.tstride == 1 and geom.outer_stride == geom.Tn and geom.Tn >= 128 and Cin <= 256
-                and (Cout + 127) // 128 <= 2)
+    tiled_ok = gn_tiled_ok(geom, Cin, Cout)
     strip_ok = strip_tile_ok(x, Cout, stats=stats, geom=geom)
     if not ((tile == 131 and strip_ok) or (tile in (64, 128) and tiled_ok) or (tile == 0 and (tiled_ok or strip_ok))):
         raise H.MMDError("gn_conv1x1: needs contiguous slices of >= 128 rows, Cin <= 256 (use gn_apply + conv_gemm otherwise)")
@@ -528,8 +565,7 @@ def gn_conv1x1(x, a, b, geom: Geom, act, w, bias, residual=None, out=None, tile=
         tile = _pick_tile((es, M, Cin, 1, Cout, residual is not None, True),
                           lambda t: H.call("mmd_gn_conv1x1", *base, t, H.stream_handle()), M, Cout,
                           candidates=(128,) if stats is not None else (64, 128), out=out, scratch=(x, residual, a, b))
-    nbytes = es * (M * Cin + M * Cout * (2 if residual is not None else 1) + Cout * Cin) + 4 * Cout
-    meta = (f"gn_conv1x1<{'bf16' if es == 2 else 'f32'},{_tile_name(tile)}>[M={M},K={Cin},N={Cout}]", 2 * M * Cout * Cin, nbytes)
+    meta = _conv_meta("gn_conv1x1", x, Cout, 1, tile, residual)
     if stats is not None:
         _dispatch("mmd_gn_conv1x1_stats", *base, tile, *_stats_args(stats, M, Cout), meta=meta)
     else:
@@ -540,14 +576,13 @@ def gn_conv1x1(x, a, b, geom: Geom, act, w, bias, residual=None, out=None, tile=
 # GroupNorm(+FiLM)(+SiLU) of the INPUT of a 3x3 conv applied to the staged halo tile in LDS (mmd_gn_conv_gemm): the gn_apply pass in
 # front of the ResBlock in-convs disappears wherever the conv runs on tile 130.  Bitwise equal to gn_apply + conv_gemm(tile 130), so
 # the switch (MMD_HALO_GN=0: separate pass) is a pure speed choice.
-_HALO_GN = os.environ.get("MMD_HALO_GN", "1") != "0"
+_HALO_GN = _flag("MMD_HALO_GN")
 
 
 def halo_gn_ok(x, taps, dims, geom: Geom):
     """Launches mmd_gn_conv_gemm accepts: what tile 130 is pinned on (bf16 3x3 convs on frames of >= 1024 pixels) with per-sample
     slices of whole frames."""
-    return (_HALO_GN and halo_tile_pinned(x, taps, dims) and geom.inner == 1 and geom.tstride == 1 and geom.outer_stride == geom.Tn
-            and geom.S * geom.Tn == x.shape[0] and geom.Tn % (dims[1] * dims[2]) == 0)
+    return _HALO_GN and halo_tile_pinned(x, taps, dims) and geom.covers(x.shape[0]) and geom.Tn % (dims[1] * dims[2]) == 0
 
 
 def gn_conv_gemm(x, a, b, geom: Geom, act, w, bias, taps, dims, residual=None, out=None, tile=0):
@@ -555,21 +590,18 @@ def gn_conv_gemm(x, a, b, geom: Geom, act, w, bias, taps, dims, residual=None, o
     _chk2d(x)
     M, Cin = x.shape
     Cout = w.shape[0]
-    if w.dtype != x.dtype or w.shape[1] != len(taps) * Cin or not w.is_contiguous():
-        raise H.MMDError(f"gn_conv_gemm: weight {tuple(w.shape)} {w.dtype} does not match input {tuple(x.shape)} {x.dtype} x {len(taps)} taps")
-    if not (halo_tile_ok(x, taps, dims) and len(taps) == 9 and x.dtype == torch.bfloat16 and geom.S * geom.Tn == M
-            and geom.inner == 1 and geom.tstride == 1 and geom.outer_stride == geom.Tn and geom.Tn % (dims[1] * dims[2]) == 0):
+    _chk_conv_w("gn_conv_gemm", x, w, len(taps))
+    if not (halo_tile_ok(x, taps, dims) and len(taps) == 9 and x.dtype == torch.bfloat16 and geom.covers(M)
+            and geom.Tn % (dims[1] * dims[2]) == 0):
         raise H.MMDError("gn_conv_gemm: needs a bf16 3x3 conv tile 130 accepts and contiguous slices of whole frames")
     out = alloc(M, Cout, dtype=x.dtype, device=x.device) if out is None else out
     _chk2d(out)
     arr, nt = H.taps_array(taps)
-    es = x.element_size()
-    flops = 2 * M * Cout * Cin * nt
-    nbytes = es * (M * Cin + M * Cout * (2 if residual is not None else 1) + Cout * Cin * nt) + 4 * Cout
+    tile = tile or halo_tile_code(x, taps, dims)
     _dispatch("mmd_gn_conv_gemm", H.dt_of(x), x.data_ptr(), x.stride(0), a.data_ptr(), b.data_ptr(), 1 if act else 0, geom.S, geom.Tn,
               w.data_ptr(), H.ptr(bias), H.ptr(residual), 0 if residual is None else residual.stride(0), out.data_ptr(), out.stride(0),
-              M, Cout, Cin, nt, arr, int(dims[0]), int(dims[1]), int(dims[2]), tile or halo_tile_code(x, taps, dims),
-              meta=(f"gn_conv_gemm<bf16,{_tile_name(tile or halo_tile_code(x, taps, dims))}>[M={M},K={Cin * nt},N={Cout}]", flops, nbytes))
+              M, Cout, Cin, nt, arr, int(dims[0]), int(dims[1]), int(dims[2]), tile,
+              meta=_conv_meta("gn_conv_gemm", x, Cout, nt, tile, residual))
     return out
 
 
@@ -577,7 +609,7 @@ def gn_conv_gemm(x, a, b, geom: Geom, act, w, bias, taps, dims, residual=None, o
 # SiLU applied to the staged halo and the output statistics in the epilogue.  Its spatial K order is its own (32-channel chunks), so -
 # like the halo tiles and the strip - it is chosen by the LAYER GEOMETRY alone: bf16, 16 frames, 128 output channels (the ds1 level of
 # the base model), Cin a multiple of 32, frame sides multiples of 4.  MMD_VCONV_FUSED=0: the two-launch path (A/B).
-_VCONV_FUSED = os.environ.get("MMD_VCONV_FUSED", "1") != "0"
+_VCONV_FUSED = _flag("MMD_VCONV_FUSED")
 
 
 def vconv_shape_ok(x, Cout, N, F, Hh, Ww):
@@ -620,8 +652,7 @@ def vconv2d1d(x, wf, bias_s, bias_t, N, F, Hh, Ww, a=None, b=None, geom=None, ac
     Cout = 128
     if not vconv_shape_ok(x, Cout, N, F, Hh, Ww):
         raise H.MMDError(f"vconv2d1d: unsupported launch (x {tuple(x.shape)} {x.dtype}, N={N} F={F} H={Hh} W={Ww})")
-    if (a is None) != (b is None) or (a is not None and (geom is None or geom.inner != 1 or geom.tstride != 1 or geom.outer_stride != geom.Tn
-                                                         or geom.S * geom.Tn != M or geom.Tn % (F * Hh * Ww))):
+    if (a is None) != (b is None) or (a is not None and (geom is None or not geom.covers(M) or geom.Tn % (F * Hh * Ww))):
         raise H.MMDError("vconv2d1d: the fused input norm needs contiguous slices of whole samples")
     out = alloc(M, Cout, dtype=x.dtype, device=x.device) if out is None else out
     _chk2d(out)
@@ -630,19 +661,18 @@ def vconv2d1d(x, wf, bias_s, bias_t, N, F, Hh, Ww, a=None, b=None, geom=None, ac
                          "compares whole ranges: column slices of one buffer count as overlapping)")
     if wf.numel() * wf.element_size() != H.lib().mmd_vconv2d1d_weight_bytes(Cin):
         raise H.MMDError("vconv2d1d: the weight image does not match Cin (pack it with vconv_pack)")
-    sp, sld = (None, 0) if stats is None else _stats_args(stats, M, Cout)
     flops = 2 * M * Cout * (9 * Cin + 3 * Cout)
     nbytes = 2 * (M * Cin + M * Cout + Cout * (9 * Cin + 3 * Cout)) + 8 * Cout
     _dispatch("mmd_vconv2d1d", x.data_ptr(), x.stride(0), H.ptr(a), H.ptr(b), 1 if act else 0, 0 if geom is None else geom.S,
               0 if geom is None else geom.Tn, wf.data_ptr(), H.ptr(bias_s), H.ptr(bias_t), out.data_ptr(), out.stride(0), N, F, Hh, Ww, Cin, Cout,
-              sp, sld, meta=(f"vconv2d1d<bf16{',gn' if a is not None else ''}>[M={M},Cin={Cin},N={Cout}]", flops, nbytes))
+              *_stats_args(stats, M, Cout), meta=(f"vconv2d1d<bf16{',gn' if a is not None else ''}>[M={M},Cin={Cin},N={Cout}]", flops, nbytes))
     return out
 
 
 # The temporal k = 3 conv of VideoConv with stationary activations (include/mmd.h: mmd_tconv): per-pixel row order, tap shift = DPP lane
 # shift.  Bitwise equal to conv_gemm with TAPS_TEMPORAL, so the switch (MMD_TCONV=0: the tiled / strip GEMM) is a pure speed choice -
 # except for the ORDER of the statistics records (the kernel's own inside a sample), which the engine accounts for (perm_unit).
-_TCONV = os.environ.get("MMD_TCONV", "1") != "0"
+_TCONV = _flag("MMD_TCONV")
 
 
 def tconv_shape_ok(x, Cout, N, F, HW):
@@ -678,8 +708,7 @@ def tconv(x, wf, bias, Cout, N, F, HW, out=None, stats=None):
     _chk2d(out)
     if out.data_ptr() == x.data_ptr():
         raise H.MMDError("tconv: in-place is not supported")
-    sp, sld = (None, 0) if stats is None else _stats_args(stats, M, Cout)
-    _dispatch("mmd_tconv", x.data_ptr(), x.stride(0), wf.data_ptr(), H.ptr(bias), out.data_ptr(), out.stride(0), N, F, HW, Cin, Cout, sp, sld,
+    _dispatch("mmd_tconv", x.data_ptr(), x.stride(0), wf.data_ptr(), H.ptr(bias), out.data_ptr(), out.stride(0), N, F, HW, Cin, Cout, *_stats_args(stats, M, Cout),
               meta=(f"tconv<bf16>[M={M},K={3 * Cin},N={Cout}]", 2 * M * Cout * 3 * Cin, 2 * (M * Cin + M * Cout + Cout * 3 * Cin) + 4 * Cout))
     return out
 
@@ -687,7 +716,7 @@ def tconv(x, wf, bias, Cout, N, F, HW, out=None, stats=None):
 # The audio in_layers of a ResBlock in one launch (include/mmd.h: mmd_aconv): GroupNorm + SiLU + dilated k = 3 conv, rows stationary, K
 # streamed.  Bitwise equal to gn_apply + conv_gemm with taps_audio(dilation), so the switch (MMD_ACONV=0: the two launches) is a pure
 # speed choice - which is why it may depend on an environment variable at all.
-_ACONV = os.environ.get("MMD_ACONV", "1") != "0"
+_ACONV = _flag("MMD_ACONV")
 # Where the engine uses it: the kernel redoes the normalisation (~8 VALU instructions per element with SiLU) for each of the three taps
 # and each column range of a row block, so it only pays where the column split is shallow - measured (profiles/r06_aconv_bench.txt, batch
 # 4): 25600 x 128 -> 128 36.8 vs 41.6 us, 6400 x 256 -> 256 35.1 vs 36.6 us, but 6400 x 640 -> 256 75 vs 50, 1600 x 896 -> 384 84 vs 59,
@@ -715,9 +744,8 @@ def aconv(x, a, b, w, bias, N, L, dilation, act=True, out=None, stats=None):
         raise H.MMDError(f"aconv: the fused affine must be two contiguous fp32 [N, Cin] tensors (got {tuple(a.shape)}, {tuple(b.shape)})")
     out = alloc(M, Cout, dtype=x.dtype, device=x.device) if out is None else out
     _chk2d(out)
-    sp, sld = (None, 0) if stats is None else _stats_args(stats, M, Cout)
     _dispatch("mmd_aconv", x.data_ptr(), x.stride(0), w.data_ptr(), H.ptr(bias), a.data_ptr(), b.data_ptr(), 1 if act else 0, out.data_ptr(),
-              out.stride(0), M, L, Cin, Cout, int(dilation), sp, sld,
+              out.stride(0), M, L, Cin, Cout, int(dilation), *_stats_args(stats, M, Cout),
               meta=(f"aconv<bf16>[M={M},K={3 * Cin},N={Cout}]", 2 * M * Cout * 3 * Cin, 2 * (M * Cin + M * Cout + Cout * 3 * Cin) + 4 * Cout))
     return out
 
@@ -726,9 +754,9 @@ def aconv(x, a, b, w, bias, N, L, dilation, act=True, out=None, stats=None):
 # frames, proj_out and the residual - instead of gn_small + qkv GEMM + attn_small + proj_out GEMM.  Built for 256 channels (the ds2
 # level), 4 heads, 16 frames; like every kernel choice it depends on the layer's geometry only.  (The 384 / 512-channel instances of
 # round 4 - ds4 neutral in the step, ds8 74 vs 44 us - were removed in round 5.)  MMD_TATTN_FUSED=0: the four-launch path (A/B).
-_TATTN_FUSED = os.environ.get("MMD_TATTN_FUSED", "1") != "0"
+_TATTN_FUSED = _flag("MMD_TATTN_FUSED")
 # the spatial block's proj_out + residual as the front stage of the same launch (MMD_TATTN_PRE=0: its own strip GEMM; A/B)
-_TATTN_PRE = os.environ.get("MMD_TATTN_PRE", "1") != "0"
+_TATTN_PRE = _flag("MMD_TATTN_PRE")
 
 
 def tattn_shape_ok(x, heads, N, F, HW):
@@ -738,6 +766,10 @@ def tattn_shape_ok(x, heads, N, F, HW):
 
 def tattn_fused_ok(x, heads, N, F, HW):
     return _TATTN_FUSED and tattn_shape_ok(x, heads, N, F, HW)
+
+
+def tattn_pre_ok(x, heads, N, F, HW):
+    return _TATTN_PRE and tattn_fused_ok(x, heads, N, F, HW)
 
 
 def tattn_pack(wqkv, wproj, wpre=None):
@@ -775,13 +807,12 @@ def tattn_block(x, wf, bias_qkv, bias_proj, gamma, beta, heads, N, F, HW, out=No
             raise H.MMDError("tattn_block: the front stage needs att / mid of x's shape, four distinct buffers and weights packed with wpre")
     elif wf.numel() * 2 != H.lib().mmd_tattn_weight_bytes(C, 0):
         raise H.MMDError("tattn_block: weights packed with a front stage need pre=(att, bias_pre, mid)")
-    sp, sld = (None, 0) if stats is None else _stats_args(stats, M, C)
     npre = 0 if pre is None else 1
     flops = 2 * M * C * (4 + npre) * C + 4 * M * F * C
     nbytes = 2 * ((3 + 2 * npre) * M * C) + 2 * (4 + npre) * C * C
     _dispatch("mmd_tattn_block", x.data_ptr(), x.stride(0), H.ptr(att), 0 if att is None else att.stride(0), H.ptr(mid),
               0 if mid is None else mid.stride(0), wf.data_ptr(), H.ptr(bpre), bias_qkv.data_ptr(), bias_proj.data_ptr(), gamma.data_ptr(),
-              beta.data_ptr(), GN_EPS, out.data_ptr(), out.stride(0), N, F, HW, C, heads, sp, sld,
+              beta.data_ptr(), GN_EPS, out.data_ptr(), out.stride(0), N, F, HW, C, heads, *_stats_args(stats, M, C),
               meta=(f"tattn_block<bf16{',pre' if npre else ''}>[M={M},C={C}]", flops, nbytes))
     return out
 
@@ -840,10 +871,15 @@ def copy2d(x, out):
     return out
 
 
-def temb(t, dim, W0, b0, W2, b2, out_silu, out_raw=None):
+def _t_kind(t):      # the timestep dtype code of mmd_temb_fwd / mmd_timestep_embedding
     kind = {torch.int64: 0, torch.int32: 1, torch.float32: 2}.get(t.dtype)
     if kind is None:
         raise H.MMDError(f"timesteps must be int64/int32/float32, got {t.dtype}")
+    return kind
+
+
+def temb(t, dim, W0, b0, W2, b2, out_silu, out_raw=None):
+    kind = _t_kind(t)
     H.require_cuda(t, W0)
     _dispatch("mmd_temb_fwd", t.data_ptr(), kind, t.shape[0], dim, W0.data_ptr(), b0.data_ptr(), W2.data_ptr(), b2.data_ptr(),
            out_silu.data_ptr(), H.ptr(out_raw))
@@ -878,15 +914,14 @@ def head_conv(x, w, bias, out, N, F, Hh, Ww, taps):
 # The head for few output channels as GEMM + gather (include/mmd.h: mmd_head_gemm / mmd_head_gather): GroupNorm + SiLU in the GEMM's
 # operand registers, per-row products on the matrix cores, then a coalesced gather over the taps.  MMD_HEAD_GEMM=0: gn_apply + the direct
 # kernel (A/B).
-_HEAD_GEMM = os.environ.get("MMD_HEAD_GEMM", "1") != "0"
+_HEAD_GEMM = _flag("MMD_HEAD_GEMM")
 
 
 def head_gemm_ok(x, w, geom: Geom):
     """Launches the GEMM + gather head accepts: bf16 rows of 128 channels, ntaps * Co <= 96, Co in (1, 2, 3, 4, 6), contiguous slices that
     are multiples of 128 rows."""
     return (_HEAD_GEMM and x.dtype == torch.bfloat16 and x.shape[1] == 128 and w.shape[0] * w.shape[2] <= 96 and w.shape[2] in (1, 2, 3, 4, 6)
-            and geom.inner == 1 and geom.tstride == 1 and geom.outer_stride == geom.Tn and geom.Tn % 128 == 0 and geom.S * geom.Tn == x.shape[0]
-            and x.stride(0) % 8 == 0)
+            and geom.covers(x.shape[0]) and geom.Tn % 128 == 0 and x.stride(0) % 8 == 0)
 
 
 def head_gemm_pack(w):
@@ -1050,7 +1085,7 @@ def conv_wgrad(dy, x, dW, db, taps, dims, torch_layout=False):
 
 # GroupNorm backward workspaces kept zero between calls (mmd_gn_bwd_ws0): one per (device, launch stream, size); MMD_GN_BWD_WS0=0 = the
 # per-call workspace with its fill launch (A/B)
-_GN_BWD_WS0 = os.environ.get("MMD_GN_BWD_WS0", "1") != "0"
+_GN_BWD_WS0 = _flag("MMD_GN_BWD_WS0")
 _gn_bwd_ws = {}
 
 
@@ -1139,10 +1174,7 @@ def adamw_step(p, g, m, v, ema, lr, beta1, beta2, eps, weight_decay, step, ema_r
 
 
 def timestep_embedding(t, dim, out):
-    kind = {torch.int64: 0, torch.int32: 1, torch.float32: 2}.get(t.dtype)
-    if kind is None:
-        raise H.MMDError(f"timesteps must be int64/int32/float32, got {t.dtype}")
-    _dispatch("mmd_timestep_embedding", t.data_ptr(), kind, t.shape[0], dim, out.data_ptr())
+    _dispatch("mmd_timestep_embedding", t.data_ptr(), _t_kind(t), t.shape[0], dim, out.data_ptr())
     return out
 
 

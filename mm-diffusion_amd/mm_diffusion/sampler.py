@@ -74,17 +74,17 @@ class GraphStepper:
             plan = []
             with ops.recording(plan):
                 # in place: x_{t-1} overwrites x_t (purely elementwise); each update rides its own stream, then join
-                ops.cur_sid = 0
                 if update == "ddim":       # ddim_sample (gd:821-901): same graph, different fused update
                     tab3 = diffusion.ddim_tables(self.device)
-                    ops.ddim_update(e.x_video, e.out_video, nv, e.x_video, self.tab, tab3, t_idx, F, C, HW, self.flags, eta)
-                    ops.cur_sid = 1
-                    ops.ddim_update(e.x_audio, e.out_audio, na, e.x_audio, self.tab, tab3, t_idx, 1, e.Ca_in, e.L0, self.flags, eta)
+                    with ops.on_stream(0):
+                        ops.ddim_update(e.x_video, e.out_video, nv, e.x_video, self.tab, tab3, t_idx, F, C, HW, self.flags, eta)
+                    with ops.on_stream(1):
+                        ops.ddim_update(e.x_audio, e.out_audio, na, e.x_audio, self.tab, tab3, t_idx, 1, e.Ca_in, e.L0, self.flags, eta)
                 else:
-                    ops.ddpm_update(e.x_video, e.out_video, nv, e.x_video, self.tab, t_idx, F, C, HW, self.flags)
-                    ops.cur_sid = 1
-                    ops.ddpm_update(e.x_audio, e.out_audio, na, e.x_audio, self.tab, t_idx, 1, e.Ca_in, e.L0, self.flags)
-                ops.cur_sid = 0
+                    with ops.on_stream(0):
+                        ops.ddpm_update(e.x_video, e.out_video, nv, e.x_video, self.tab, t_idx, F, C, HW, self.flags)
+                    with ops.on_stream(1):
+                        ops.ddpm_update(e.x_audio, e.out_audio, na, e.x_audio, self.tab, t_idx, 1, e.Ca_in, e.L0, self.flags)
                 ops.record_sync(1, 0)
             self.update_plans.append(plan)
         self.update_plan = self.update_plans[0]

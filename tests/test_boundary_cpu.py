@@ -126,3 +126,24 @@ def test_bench_dump_outputs_float32_budget_and_fixed_sample(tmp_path):
     assert sum(v.nbytes for v in a.values()) <= bench.DUMP_BUDGET_BYTES and a["big"].size >= 1 << 20
     assert np.all(np.diff(a["big"]) >= 0) and a["big"][-1] < 20 << 20
     assert np.array_equal(a["big"], np.load(tmp_path / "b" / "big.npy"))
+
+
+def test_switch_table_lists_every_environment_read():
+    """INTEGRATION.md section 4 has one row per MMD_* variable that the library, the Python host or the build reads - no more, no fewer.
+    A plain regex over the sources: names inside getenv(...) / os.environ / os.getenv reads and inside ops._flag(...), the host's on / off
+    helper over os.environ."""
+    import glob
+    import re
+    base = os.path.join(ROOT, "mm-diffusion_amd")
+    files = glob.glob(os.path.join(base, "csrc", "*")) + glob.glob(os.path.join(base, "mm_diffusion", "*.py")) + [os.path.join(base, "build.py")]
+    read = re.compile(r'(?:\bgetenv\(|\bos\.environ(?:\.get\(|\.setdefault\(|\[)|\b_flag\()\s*"(MMD_[A-Z0-9_]+)"')
+    used = set()
+    for f in files:
+        with open(f, errors="replace") as fh:
+            used |= set(read.findall(fh.read()))
+    with open(os.path.join(ROOT, "INTEGRATION.md")) as fh:
+        section = fh.read().split("## 4. Environment switches", 1)[1].split("\n## ", 1)[0]
+    listed = re.findall(r"^\| `(MMD_[A-Z0-9_]+)` \|", section, flags=re.M)
+    assert len(listed) == len(set(listed)), sorted(n for n in set(listed) if listed.count(n) > 1)
+    assert len(used) > 40, sorted(used)                  # the scan found the sources
+    assert set(listed) == used, (sorted(used - set(listed)), sorted(set(listed) - used))
