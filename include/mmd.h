@@ -288,6 +288,22 @@ int mmd_loss_terms(const float* x0, const float* xt, const float* model_out, con
                    const int64_t* t, int T, int N, int F, int C, int HW, int flags, float vb_scale, float* mse_out, float* vb_out,
                    void* workspace, void* stream);
 
+/* One term of the variational bound in bits / dim for one stream (_vb_terms_bpd + the per-step reductions of calc_bpd_loop, gd:1048-1092,
+ * 1231-1286), one pass: vb (KL for t>0, decoder NLL at t==0, model mean live), xstart_mse = mean((pred_x0 - x0)^2), eps_mse =
+ * mean((eps(pred_x0) - noise)^2).  flags 1 / 2 / 4 as mmd_ddpm_update (fixed variance: model log-variance = table row 4; the true
+ * posterior's is row 5).  Results of sample n go to column t[n] of row n of the fp32 tables [N, out_ld] (out_ld == 0: fp32 [N]), so a
+ * whole loop runs from a captured graph and is read back once.  noise / xstart_mse_out / eps_mse_out / pred_xstart_out are nullable.
+ * Deterministic fixed-order reduction.  The per-element arithmetic is the device function of mmd_loss_terms instantiated in double: with
+ * flag 4 and clip off vb agrees with mmd_loss_terms' vb (vb_scale 1) to the accuracy of that fp32 evaluation. */
+int64_t mmd_vlb_workspace_bytes(int N);
+int mmd_vlb_terms(const float* x0, const float* xt, const float* noise, const float* model_out, const float* tables, const int64_t* t,
+                  int T, int N, int F, int C, int HW, int flags, float* vb_out, float* xstart_mse_out, float* eps_mse_out,
+                  int64_t out_ld, float* pred_xstart_out, void* workspace, void* stream);
+/* Gradient of sum_n dvb[n] vb[n] of mmd_vlb_terms w.r.t. the model output (KL / RESCALED_KL training, gaussian_diffusion.py:872-882): the
+ * mean channels get the KL / NLL gradient through pred_x0 -> posterior mean, the variance channels as mmd_loss_terms_bwd.  Clip off only. */
+int mmd_vlb_terms_bwd(const float* x0, const float* xt, const float* model_out, const float* tables, const int64_t* t, int T, int N,
+                      int F, int C, int HW, int flags, const float* dvb, float* g_model_out, void* stream);
+
 /* ---------------------------------------------------------------- training step: backward kernels (gd:1114-1203 backward)
  * conv wgrad: dW fp32 [Cout][ntaps*Cin] += dY^T gather(X) (same tap semantics as mmd_conv_gemm; caller zeroes dW), db
  * (nullable, fp32 [Cout]) += column sums of dY.  conv dgrad = mmd_conv_gemm(dY, W^T-packed, taps negated).  bf16 with >= 64 channels on

@@ -430,6 +430,35 @@ struct LossParams {
 __device__ __forceinline__ float approx_std_normal_cdf(float x) {
   return 0.5f * (1.0f + tanhf(0.7978845608028654f * (x + 0.044715f * x * x * x)));
 }
+// One element of the variational bound in nats, shared by loss_terms_kernel (R = float: the training loss, fp32 like the reference) and
+// vlb_terms_kernel (R = double: the evaluation form, evaluated in double from the fp32 inputs and tables): the discretized-Gaussian
+// decoder NLL at t == 0, else KL(q(x_{t-1}|x_t,x_0) || p) with the true posterior (tmean, post_log).  The |x0| > 0.999 edge tests
+// compare the fp32 datum, as the reference does.
+__device__ __forceinline__ float vlb_exp(float x) { return expf(x); }
+__device__ __forceinline__ double vlb_exp(double x) { return exp(x); }
+__device__ __forceinline__ float vlb_log(float x) { return logf(x); }
+__device__ __forceinline__ double vlb_log(double x) { return log(x); }
+__device__ __forceinline__ float vlb_max(float a, float b) { return fmaxf(a, b); }
+__device__ __forceinline__ double vlb_max(double a, double b) { return fmax(a, b); }
+__device__ __forceinline__ float vlb_cdf(float x) { return approx_std_normal_cdf(x); }
+__device__ __forceinline__ double vlb_cdf(double x) { return 0.5 * (1.0 + tanh(0.7978845608028654 * (x + 0.044715 * x * x * x))); }
+template <typename R>
+__device__ __forceinline__ R vlb_term(int ti, float x0f, R mean, R tmean, R logvar, R post_log) {
+  const R x0 = x0f;
+  R term;
+  if (ti == 0) {        // decoder NLL
+    const R cx = x0 - mean, inv = vlb_exp(R(-0.5) * logvar);
+    const R cdf_p = vlb_cdf(inv * (cx + R(1) / R(255)));
+    const R cdf_m = vlb_cdf(inv * (cx - R(1) / R(255)));
+    const R lp = vlb_log(vlb_max(cdf_p, R(1e-12))), lm = vlb_log(vlb_max(R(1) - cdf_m, R(1e-12)));
+    const R ld = vlb_log(vlb_max(cdf_p - cdf_m, R(1e-12)));
+    term = -(x0f < -0.999f ? lp : (x0f > 0.999f ? lm : ld));
+  } else {              // KL(q || p), true posterior log-variance = posterior_log_variance_clipped
+    const R dm = tmean - mean;
+    term = R(0.5) * (R(-1) + logvar - post_log + vlb_exp(post_log - logvar) + dm * dm * vlb_exp(-logvar));
+  }
+  return term;
+}
 __global__ __launch_bounds__(256) void loss_terms_kernel(const LossParams p) {
   __shared__ double s_a[256], s_b[256];
   const int n = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
@@ -456,18 +485,7 @@ __global__ __launch_bounds__(256) void loss_terms_kernel(const LossParams p) {
       const float px0 = (p.flags & 2) ? o : cr * xv - crm1 * o;          // clip_denoised=False in the vb term
       const float mean = c1 * px0 + c2 * xv;
       const float tmean = c1 * x0 + c2 * xv;
-      float term;
-      if (ti == 0) {        // decoder NLL
-        const float cx = x0 - mean, inv = expf(-0.5f * logvar);
-        const float cdf_p = approx_std_normal_cdf(inv * (cx + 1.f / 255.f));
-        const float cdf_m = approx_std_normal_cdf(inv * (cx - 1.f / 255.f));
-        const float lp = logf(fmaxf(cdf_p, 1e-12f)), lm = logf(fmaxf(1.f - cdf_m, 1e-12f));
-        const float ld = logf(fmaxf(cdf_p - cdf_m, 1e-12f));
-        term = -(x0 < -0.999f ? lp : (x0 > 0.999f ? lm : ld));
-      } else {              // KL(q || p), true posterior log-variance = min_log (posterior_log_variance_clipped)
-        const float dm = tmean - mean;
-        term = 0.5f * (-1.0f + logvar - min_log + expf(min_log - logvar) + dm * dm * expf(-logvar));
-      }
+      const float term = vlb_term<float>(ti, x0, mean, tmean, logvar, min_log);
       vb += (double)term;
     }
   }
@@ -1195,6 +1213,114 @@ extern "C" int mmd_loss_terms(const float* x0, const float* xt, const float* mod
   return mmd_check_launch("loss_finalize");
 }
 
+// ----------------------------------------------------------------------------- variational bound, evaluation form (bits / dim)
+// One term of calc_bpd_loop (gd:1048-1092, 1231-1286; SR gaussian_diffusion.py:796-829, 953-1008) for one stream, API layout as
+// ddpm_update / loss_terms, in ONE pass over the tensors.  Per sample n (t = t[n]):
+//   vb[n]         = mean KL(q(x_{t-1}|x_t,x_0) || p(x_{t-1}|x_t)) / ln 2  (t > 0), decoder NLL / ln 2 (t == 0)
+//   xstart_mse[n] = mean((pred_x0 - x0)^2)
+//   eps_mse[n]    = mean((eps - noise)^2),  eps = (sqrt_recip_ac x_t - pred_x0) / sqrt_recipm1_ac  (so it sees the clamp); noise nullable
+// flags 1 / 2 / 4 as ddpm_update; without flag 4 the model's log-variance is table row 4; the true posterior's is always row 5.
+// Inputs and table coefficients are fp32; the per-element arithmetic and the sums are evaluated in double (vlb_term<double>).
+// Same (sample, chunk) grid and fixed-order double reduction as loss_terms_kernel; partial [N, nchunk, 3] doubles.  The finalize
+// kernel writes sample n's results at column t[n] of row n of the result tables (ld floats per row; ld == 0: plain [N] vectors), so a
+// whole loop needs no per-step host value and sits in a captured graph.
+struct VlbParams {
+  const float* x0; const float* xt; const float* noise; const float* mo; float* px0_out;
+  const float* tables; const int64_t* t;
+  double* partial;
+  int T, N, F, C, HW, flags, nchunk;
+};
+__global__ __launch_bounds__(256) void vlb_terms_kernel(const VlbParams p) {
+  __shared__ double s_a[256], s_b[256], s_c[256];
+  const int n = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
+  const int64_t per = (int64_t)p.F * p.C * p.HW;
+  const int Cm = (p.flags & 4) ? 2 * p.C : p.C;
+  const int ti = (int)p.t[n];
+  // fp32 table and tensor values, every operation on them in double (what that costs beside an fp32 form: DESIGN, the bound's row)
+  const double cr = p.tables[ti], crm1 = p.tables[p.T + ti], c1 = p.tables[2 * p.T + ti], c2 = p.tables[3 * p.T + ti];
+  const double fixed_log = p.tables[4 * p.T + ti], min_log = p.tables[5 * p.T + ti], max_log = p.tables[6 * p.T + ti];
+  double vb = 0.0, xs = 0.0, em = 0.0;
+  const int64_t lo = per * chunk / p.nchunk, hi = per * (chunk + 1) / p.nchunk;
+  for (int64_t r = lo + tid; r < hi; r += 256) {
+    const int hw = (int)(r % p.HW), c = (int)((r / p.HW) % p.C);
+    const int64_t f = r / ((int64_t)p.HW * p.C);
+    const int64_t i = n * per + r;
+    const int64_t mbase = ((n * (int64_t)p.F + f) * Cm) * (int64_t)p.HW + hw;
+    const double o = p.mo[mbase + (int64_t)c * p.HW];
+    double logvar = fixed_log;
+    if (p.flags & 4) {
+      const double vv = p.mo[mbase + (int64_t)(c + p.C) * p.HW];
+      const double frac = (vv + 1.0) / 2.0;
+      logvar = frac * max_log + (1.0 - frac) * min_log;
+    }
+    const float x0f = p.x0[i];
+    const double xv = p.xt[i], x0 = x0f;
+    double px0 = (p.flags & 2) ? o : cr * xv - crm1 * o;
+    if (p.flags & 1) px0 = fmin(fmax(px0, -1.0), 1.0);
+    const double mean = c1 * px0 + c2 * xv;
+    const double tmean = c1 * x0 + c2 * xv;
+    vb += vlb_term<double>(ti, x0f, mean, tmean, logvar, min_log);
+    const double dx = px0 - x0;
+    xs += dx * dx;
+    if (p.noise) {
+      const double de = (cr * xv - px0) / crm1 - (double)p.noise[i];
+      em += de * de;
+    }
+    if (p.px0_out) p.px0_out[i] = (float)px0;
+  }
+  s_a[tid] = vb;
+  s_b[tid] = xs;
+  s_c[tid] = em;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) { s_a[tid] += s_a[tid + o]; s_b[tid] += s_b[tid + o]; s_c[tid] += s_c[tid + o]; }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    double* q = p.partial + ((int64_t)n * p.nchunk + chunk) * 3;
+    q[0] = s_a[0]; q[1] = s_b[0]; q[2] = s_c[0];
+  }
+}
+__global__ void vlb_finalize_kernel(const double* __restrict__ partial, int nchunk, int N, double inv_count, const int64_t* __restrict__ t,
+                                    int64_t ld, float* __restrict__ vb_out, float* __restrict__ xs_out, float* __restrict__ eps_out) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  double a = 0.0, b = 0.0, c = 0.0;
+  for (int k = 0; k < nchunk; ++k) {
+    const double* q = partial + ((int64_t)n * nchunk + k) * 3;
+    a += q[0]; b += q[1]; c += q[2];
+  }
+  if (ld && (t[n] < 0 || t[n] >= ld)) return;      // a timestep outside the row is never written
+  const int64_t at = ld ? (int64_t)n * ld + t[n] : n;
+  vb_out[at] = (float)(a * inv_count / 0.6931471805599453);
+  if (xs_out) xs_out[at] = (float)(b * inv_count);
+  if (eps_out) eps_out[at] = (float)(c * inv_count);
+}
+
+extern "C" int64_t mmd_vlb_workspace_bytes(int N) { return (int64_t)N * MMD_LOSS_CHUNKS * 3 * sizeof(double); }
+
+// vb_out / xstart_mse_out / eps_mse_out: fp32 result tables [N, out_ld], sample n written at column t[n]; out_ld == 0: fp32 [N].
+// noise == NULL skips eps_mse (eps_mse_out must then be NULL); xstart_mse_out and pred_xstart_out (fp32 like x0) are optional.
+extern "C" int mmd_vlb_terms(const float* x0, const float* xt, const float* noise, const float* model_out, const float* tables,
+                             const int64_t* t, int T, int N, int F, int C, int HW, int flags, float* vb_out, float* xstart_mse_out,
+                             float* eps_mse_out, int64_t out_ld, float* pred_xstart_out, void* workspace, void* stream) {
+  MMD_REQUIRE(x0 && xt && model_out && tables && t && vb_out && workspace && T > 0 && N > 0 && F > 0 && C > 0 && HW > 0, "vlb_terms: bad argument");
+  MMD_REQUIRE(!(flags & ~7), "vlb_terms: flags are 1 (clip x0), 2 (model predicts x0), 4 (learned-range variance); got %d", flags);
+  MMD_REQUIRE(!eps_mse_out || noise, "vlb_terms: eps_mse needs the noise tensor");
+  MMD_REQUIRE(out_ld == 0 || out_ld >= T, "vlb_terms: result rows of %ld floats cannot hold %d timesteps", (long)out_ld, T);
+  VlbParams p;
+  p.x0 = x0; p.xt = xt; p.noise = eps_mse_out ? noise : nullptr; p.mo = model_out; p.px0_out = pred_xstart_out; p.tables = tables; p.t = t;
+  p.partial = (double*)workspace;
+  p.T = T; p.N = N; p.F = F; p.C = C; p.HW = HW; p.flags = flags; p.nchunk = MMD_LOSS_CHUNKS;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(vlb_terms_kernel, dim3(MMD_LOSS_CHUNKS, N), dim3(256), 0, st, p);
+  int rc = mmd_check_launch("vlb_terms");
+  if (rc) return rc;
+  hipLaunchKernelGGL(vlb_finalize_kernel, dim3(cdiv(N, 64)), dim3(64), 0, st, (const double*)workspace, MMD_LOSS_CHUNKS, N,
+                     1.0 / ((double)F * C * HW), t, out_ld, vb_out, xstart_mse_out, eps_mse_out);
+  return mmd_check_launch("vlb_finalize");
+}
+
 // sinusoidal timestep embedding alone (nn.py:192-210): out[N, dim] fp32 (training path keeps the MLP as separate linears)
 __global__ void timestep_embedding_kernel(const void* __restrict__ t, int t_kind, int dim, float* __restrict__ out) {
   const int n = blockIdx.x;
@@ -1527,6 +1653,41 @@ extern "C" int mmd_bilinear_concat_rows(int dtype, const float* x, const float* 
 //   variance channels c >= C: dvb[n] * vb_scale / (per ln 2) * d term / d logvar * (max_log - min_log) / 2
 // with term = KL(q || p) for t > 0 and the discretized-Gaussian decoder NLL at t == 0 (losses.py:12-77), exactly the forward
 // arithmetic of loss_terms_kernel.
+// d vlb_term / d logvar (returned) and d vlb_term / d mean (*dmean), in the forward's own arithmetic; the clamped logs of the decoder
+// NLL have zero slope below the clamp.
+__device__ __forceinline__ float vlb_term_grad(int ti, float x0, float mean, float tmean, float logvar, float post_log, float* dmean) {
+  float dterm;
+  if (ti == 0) {
+    const float cx = x0 - mean, inv = expf(-0.5f * logvar);
+    const float up = inv * (cx + 1.f / 255.f), um = inv * (cx - 1.f / 255.f);
+    const float cdf_p = approx_std_normal_cdf(up), cdf_m = approx_std_normal_cdf(um);
+    // d cdf(u) / d logvar = pdf~(u) * (-u / 2),  pdf~ = derivative of the tanh approximation
+    auto dcdf = [](float u) {
+      const float k = 0.7978845608028654f, a = 0.044715f;
+      const float th_ = tanhf(k * (u + a * u * u * u));
+      return 0.5f * (1.f - th_ * th_) * k * (1.f + 3.f * a * u * u) * (-0.5f * u);
+    };
+    // d cdf(u) / d mean = pdf~(u) * (-inv)
+    auto dcdf_mean = [inv](float u) {
+      const float k = 0.7978845608028654f, a = 0.044715f;
+      const float th_ = tanhf(k * (u + a * u * u * u));
+      return 0.5f * (1.f - th_ * th_) * k * (1.f + 3.f * a * u * u) * (-inv);
+    };
+    const float dp = dcdf(up), dm_ = dcdf(um);
+    const float ep = dcdf_mean(up), em = dcdf_mean(um);
+    float dlog, elog;
+    if (x0 < -0.999f) { dlog = cdf_p > 1e-12f ? dp / cdf_p : 0.f; elog = cdf_p > 1e-12f ? ep / cdf_p : 0.f; }
+    else if (x0 > 0.999f) { dlog = (1.f - cdf_m) > 1e-12f ? -dm_ / (1.f - cdf_m) : 0.f; elog = (1.f - cdf_m) > 1e-12f ? -em / (1.f - cdf_m) : 0.f; }
+    else { dlog = (cdf_p - cdf_m) > 1e-12f ? (dp - dm_) / (cdf_p - cdf_m) : 0.f; elog = (cdf_p - cdf_m) > 1e-12f ? (ep - em) / (cdf_p - cdf_m) : 0.f; }
+    dterm = -dlog;
+    *dmean = -elog;
+  } else {
+    const float dm = tmean - mean;
+    dterm = 0.5f * (1.f - expf(post_log - logvar) - dm * dm * expf(-logvar));
+    *dmean = -dm * expf(-logvar);
+  }
+  return dterm;
+}
 __global__ __launch_bounds__(256) void loss_terms_bwd_kernel(const LossParams p, const float* __restrict__ dmse, const float* __restrict__ dvb,
                                                              float vb_scale, float* __restrict__ g) {
   const int64_t per = (int64_t)p.F * p.C * p.HW;
@@ -1549,27 +1710,8 @@ __global__ __launch_bounds__(256) void loss_terms_bwd_kernel(const LossParams p,
       const float xv = p.xt[i], x0 = p.x0[i];
       const float px0 = (p.flags & 2) ? o : cr * xv - crm1 * o;
       const float mean = c1 * px0 + c2 * xv;
-      float dterm;                                   // d term / d logvar
-      if (ti == 0) {
-        const float cx = x0 - mean, inv = expf(-0.5f * logvar);
-        const float up = inv * (cx + 1.f / 255.f), um = inv * (cx - 1.f / 255.f);
-        const float cdf_p = approx_std_normal_cdf(up), cdf_m = approx_std_normal_cdf(um);
-        // d cdf(u) / d logvar = pdf~(u) * (-u / 2),  pdf~ = derivative of the tanh approximation
-        auto dcdf = [](float u) {
-          const float k = 0.7978845608028654f, a = 0.044715f;
-          const float th_ = tanhf(k * (u + a * u * u * u));
-          return 0.5f * (1.f - th_ * th_) * k * (1.f + 3.f * a * u * u) * (-0.5f * u);
-        };
-        const float dp = dcdf(up), dm_ = dcdf(um);
-        float dlog;
-        if (x0 < -0.999f) dlog = cdf_p > 1e-12f ? dp / cdf_p : 0.f;
-        else if (x0 > 0.999f) dlog = (1.f - cdf_m) > 1e-12f ? -dm_ / (1.f - cdf_m) : 0.f;
-        else dlog = (cdf_p - cdf_m) > 1e-12f ? (dp - dm_) / (cdf_p - cdf_m) : 0.f;
-        dterm = -dlog;
-      } else {
-        const float dm = (c1 * x0 + c2 * xv) - mean;
-        dterm = 0.5f * (1.f - expf(min_log - logvar) - dm * dm * expf(-logvar));
-      }
+      float dmean_unused;
+      const float dterm = vlb_term_grad(ti, x0, mean, c1 * x0 + c2 * xv, logvar, min_log, &dmean_unused);      // d term / d logvar
       g[mbase + (int64_t)(c + p.C) * p.HW] = dvb[n] * vb_scale / ((float)per * 0.6931471805599453f) * dterm * 0.5f * (max_log - min_log);
     }
   }
@@ -1585,4 +1727,51 @@ extern "C" int mmd_loss_terms_bwd(const float* x0, const float* xt, const float*
   hipLaunchKernelGGL(loss_terms_bwd_kernel, dim3(ew_grid((int64_t)N * F * C * HW)), dim3(256), 0, (hipStream_t)stream, p, dmse, dvb, vb_scale,
                      g_model_out);
   return mmd_check_launch("loss_terms_bwd");
+}
+
+// ----------------------------------------------------------------------------- variational-bound gradient (KL / RESCALED_KL training)
+// Gradient of  sum_n dvb[n] * vb[n]  of mmd_vlb_terms w.r.t. the model output, the mean NOT detached (gaussian_diffusion.py:872-882 calls
+// _vb_terms_bpd on the live model output with clip_denoised=False):
+//   mean channels     : dvb[n] / (per ln 2) * d term / d mean * c1 * (1 with flag 2, else -sqrt_recipm1_ac)     (pred_x0 -> posterior mean)
+//   variance channels : as loss_terms_bwd_kernel (flag 4 only)
+__global__ __launch_bounds__(256) void vlb_terms_bwd_kernel(const VlbParams p, const float* __restrict__ dvb, float* __restrict__ g) {
+  const int64_t per = (int64_t)p.F * p.C * p.HW;
+  const int64_t total = per * p.N;
+  const int Cm = (p.flags & 4) ? 2 * p.C : p.C;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int64_t n = i / per, r = i % per;
+    const int hw = (int)(r % p.HW), c = (int)((r / p.HW) % p.C);
+    const int64_t f = r / ((int64_t)p.HW * p.C);
+    const int ti = (int)p.t[n];
+    const float cr = p.tables[ti], crm1 = p.tables[p.T + ti], c1 = p.tables[2 * p.T + ti], c2 = p.tables[3 * p.T + ti];
+    const float min_log = p.tables[5 * p.T + ti], max_log = p.tables[6 * p.T + ti];
+    const int64_t mbase = ((n * (int64_t)p.F + f) * Cm) * (int64_t)p.HW + hw;
+    const float o = p.mo[mbase + (int64_t)c * p.HW];
+    float logvar = p.tables[4 * p.T + ti];
+    if (p.flags & 4) {
+      const float vv = p.mo[mbase + (int64_t)(c + p.C) * p.HW];
+      const float frac = (vv + 1.f) / 2.f;
+      logvar = frac * max_log + (1.f - frac) * min_log;
+    }
+    const float xv = p.xt[i], x0 = p.x0[i];
+    const float px0 = (p.flags & 2) ? o : cr * xv - crm1 * o;
+    const float mean = c1 * px0 + c2 * xv;
+    float dmean;
+    const float dterm = vlb_term_grad(ti, x0, mean, c1 * x0 + c2 * xv, logvar, min_log, &dmean);
+    const float w = dvb[n] / ((float)per * 0.6931471805599453f);
+    g[mbase + (int64_t)c * p.HW] = w * dmean * c1 * ((p.flags & 2) ? 1.f : -crm1);
+    if (p.flags & 4) g[mbase + (int64_t)(c + p.C) * p.HW] = w * dterm * 0.5f * (max_log - min_log);
+  }
+}
+// g_model_out like model_out ([N, F, Cm, HW]); every element is written.  Clip (flag 1) is not differentiable here.
+extern "C" int mmd_vlb_terms_bwd(const float* x0, const float* xt, const float* model_out, const float* tables, const int64_t* t, int T,
+                                 int N, int F, int C, int HW, int flags, const float* dvb, float* g_model_out, void* stream) {
+  MMD_REQUIRE(x0 && xt && model_out && tables && t && dvb && g_model_out && T > 0 && N > 0 && F > 0 && C > 0 && HW > 0, "vlb_terms_bwd: bad argument");
+  MMD_REQUIRE(!(flags & ~7), "vlb_terms_bwd: flags are 2 (model predicts x0) and 4 (learned-range variance); got %d", flags);
+  MMD_REQUIRE(!(flags & 1), "vlb_terms_bwd: the clipped x0 prediction (flag 1) is not differentiable here (training uses clip_denoised=False)");
+  VlbParams p;
+  p.x0 = x0; p.xt = xt; p.noise = nullptr; p.mo = model_out; p.px0_out = nullptr; p.tables = tables; p.t = t; p.partial = nullptr;
+  p.T = T; p.N = N; p.F = F; p.C = C; p.HW = HW; p.flags = flags; p.nchunk = 0;
+  hipLaunchKernelGGL(vlb_terms_bwd_kernel, dim3(ew_grid((int64_t)N * F * C * HW)), dim3(256), 0, (hipStream_t)stream, p, dvb, g_model_out);
+  return mmd_check_launch("vlb_terms_bwd");
 }

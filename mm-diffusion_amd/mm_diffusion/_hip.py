@@ -101,6 +101,9 @@ _PROTOS = {
     "mmd_mse_grad": (i32, [vp, vp, vp, vp, i32, i64, vp]),
     "mmd_adamw_step": (i32, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, vp]),
     "mmd_q_sample": (i32, [vp, vp, vp, vp, vp, i32, i32, i64, vp]),
+    "mmd_vlb_workspace_bytes": (i64, [i32]),
+    "mmd_vlb_terms": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp]),
+    "mmd_vlb_terms_bwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
 }
 EXPORTS = tuple(_PROTOS)
 

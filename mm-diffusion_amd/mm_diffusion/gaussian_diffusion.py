@@ -10,8 +10,11 @@ Reference behaviours kept: `p_sample_loop` hands its `noise` argument down to `p
 the SAME tensor is re-used as the per-step noise of every step (gd:547-556, 423-424); `ddim_sample` always draws fresh noise
 (gd:661); `ddim_sample_loop_progressive` defaults to eta = 0.5 while `ddim_sample_loop` defaults to 0.0 (gd:725,759).
 `training_losses` (gd:850-927; py_scripts/image_sr_train.py through train_util.TrainLoop) runs q_sample, the model and the MSE /
-learned-range vb reductions in libmmd and is differentiable when the model output carries a grad_fn.
-Not built: cond_fn (classifier guidance), the KL / RESCALED_KL loss types and the bpd loops."""
+learned-range vb reductions in libmmd and is differentiable when the model output carries a grad_fn; with LossType.KL / RESCALED_KL
+(`--use_kl True`, gd:872-882) the loss is the bound term itself with the mean live (mmd_vlb_terms / mmd_vlb_terms_bwd).
+`_vb_terms_bpd`, `_prior_bpd` and `calc_bpd_loop` (gd:796-829, 935-1008) evaluate the variational bound in bits / dim: one reduction
+kernel per step writes into device result tables, read back once at the end.
+Not built: cond_fn (classifier guidance)."""
 import torch as th
 
 from . import _hip as H
@@ -124,11 +127,15 @@ class GaussianDiffusion(_Base):
 
     def training_losses(self, model, x_start, t, model_kwargs=None, noise=None):
         """gd:850-927 -> per-sample {"loss", "mse"[, "vb"]}: MSE / RESCALED_MSE with fixed or learned-range variance (the vb term sees the
-        mean prediction detached and clip_denoised=False, gd:887-901; RESCALED_MSE scales it by num_timesteps / 1000)."""
-        if self.loss_type not in (LossType.MSE, LossType.RESCALED_MSE):
-            raise NotImplementedError("training_losses: the KL / RESCALED_KL loss types are not built (the full-bound bpd walk has no "
-                                      "libmmd kernel; the SR stage trains with MSE + learned-range vb)")
+        mean prediction detached and clip_denoised=False, gd:887-901; RESCALED_MSE scales it by num_timesteps / 1000); KL / RESCALED_KL
+        -> {"loss"} alone (RESCALED_KL times num_timesteps)."""
         H.require_cuda(x_start)
+        if self.loss_type.is_vb():          # gd:872-882: the bound term itself, mean live, clip off
+            if noise is None:
+                noise = self._randn_like(x_start)
+            xt = self.q_sample(x_start, t, noise=noise)
+            loss = self._vb_terms_bpd(model, x_start, xt, t, clip_denoised=False, model_kwargs=model_kwargs)["output"]
+            return {"loss": loss * self.num_timesteps if self.loss_type == LossType.RESCALED_KL else loss}
         if noise is None:
             noise = self._randn_like(x_start)
         xt = self.q_sample(x_start, t, noise=noise)
@@ -161,6 +168,46 @@ class GaussianDiffusion(_Base):
                 terms["vb"] = vb
         terms["loss"] = terms["mse"] + terms["vb"] if "vb" in terms else terms["mse"]
         return terms
+
+    # ------------------------------------------------------------------ variational bound (bits / dim)
+    def _vb_terms_bpd(self, model, x_start, x_t, t, clip_denoised=True, model_kwargs=None):
+        """gd:796-829 -> {"output" [N] (KL for t > 0, decoder NLL at t == 0, bits / dim), "pred_xstart"}.  Differentiable w.r.t. the model
+        output (mean and variance channels) when it carries a grad_fn; that needs clip_denoised=False, as training_losses uses it.
+        To EVALUATE with the default clip_denoised=True, call it under torch.no_grad(): a model with trainable parameters called with
+        autograd on runs its training walk and its output requires grad, and the clipped bound then raises (the gradient through the
+        clamp is not built, and a detached value in its place would be a silent fallback)."""
+        H.require_cuda(x_start, x_t)
+        mo = self._model_out(model, x_t, t, model_kwargs)
+        F, C, HW = _geom4(x_t)
+        N = x_t.shape[0]
+        if th.is_grad_enabled() and mo.requires_grad:
+            if clip_denoised:
+                raise NotImplementedError("_vb_terms_bpd: the gradient through the clipped x_0 prediction is not built: evaluate under "
+                                          "torch.no_grad(), or pass clip_denoised=False for a differentiable bound")
+            from .train_ops import VlbTermsFn
+            tab, _ = self.device_tables(x_t.device)
+            vb, px0 = VlbTermsFn.apply(mo.reshape(N, 1, -1, HW), x_start.float().reshape(N, 1, C, HW).contiguous(),
+                                       x_t.float().reshape(N, 1, C, HW).contiguous(), tab, t.to(th.int64).contiguous(), (F, C, HW),
+                                       self._flags(False))
+            return {"output": vb, "pred_xstart": px0.reshape(x_t.shape)}
+        vb, _, _, px0 = self._vlb_stream(x_start, x_t, mo, t, clip_denoised, (F, C, HW), want_x0=True)
+        return {"output": vb, "pred_xstart": px0}
+
+    def calc_bpd_loop(self, model, x_start, clip_denoised=True, model_kwargs=None):
+        """gd:953-1008 -> total_bpd / prior_bpd [N], vb / xstart_mse / mse [N, T] (column j is t = T-1-j, the reference's stacking order).
+        Per step: fresh noise through noise_source, q_sample, the model, mmd_vlb_terms into device tables - no host sync in the loop."""
+        H.require_cuda(x_start)
+        device, N, T = x_start.device, x_start.shape[0], self.num_timesteps
+        tabs = tuple(th.zeros(N, T, dtype=th.float32, device=device) for _ in range(3))
+        geom = _geom4(x_start)
+        for i in self._indices(False):
+            t = th.tensor([i] * N, device=device)
+            noise = self._randn_like(x_start)
+            x_t = self.q_sample(x_start, t, noise=noise)
+            with th.no_grad():
+                mo = self._model_out(model, x_t, t, model_kwargs)
+                self._vlb_stream(x_start, x_t, mo, t, clip_denoised, geom, noise=noise, tables=tabs)
+        return self._bpd_result(*tabs, self._prior_bpd(x_start))
 
     # the multimodal dict-valued entry points do not apply to the tensor-valued process
     def multimodal_training_losses(self, *a, **kw):

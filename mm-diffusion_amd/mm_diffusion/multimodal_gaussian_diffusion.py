@@ -15,8 +15,14 @@ MI355X-first differences:
   * DDIM (`ddim_sample(_loop)`) rides the same graph with mmd_ddim_update; zero-shot conditional sampling
     (`conditional_p_sample_loop`, gd:584-819) is built for both the replacement and the gradient-guided method
     (the latter differentiates the HIP training path w.r.t. the target stream's input)
+  * the variational bound in bits / dim (`_vb_terms_bpd`, `_prior_bpd`, `calc_bpd_loop`, gd:1048-1092, 1213-1286) is one
+    reduction kernel per stream and step (mmd_vlb_terms) that writes into device result tables; `calc_bpd_loop` replays
+    [q_sample + U-Net plan + both reductions] as one hipGraph per step and reads the tables back once.  The reference's
+    own multimodal `calc_bpd_loop` cannot run (it calls `.device` / `th.randn_like` on the stream dict, gd:1249-1257); here
+    it is the per-stream loop over the reference's working pieces, every result keyed {"video", "audio"}
 Not built: cond_fn (the reference's condition_mean / condition_score call `.float()` / `.shape` on the stream
-dict, gd:385,403, and raise for every multimodal call), calc_bpd_loop.
+dict, gd:385,403, and raise for every multimodal call); KL / RESCALED_KL in multimodal_training_losses (no terms in the
+reference either, gd:1143).
 """
 import enum
 import math
@@ -497,6 +503,100 @@ class GaussianDiffusion:
                 out = self.p_sample(model, x, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn, model_kwargs=model_kwargs)
             yield out["sample"]
             x = out["sample"]
+
+    # ------------------------------------------------------------------ variational bound (bits / dim)
+    def _vlb_stream(self, x_start, x_t, model_out, t, clip_denoised, geom, noise=None, tables=None, want_x0=False):
+        """mmd_vlb_terms on one stream.  `tables` = (vb, xstart_mse, eps_mse) [N, T] result tables (sample n lands at column t[n]); without
+        them fresh [N] vectors.  Returns (vb, xstart_mse, eps_mse or None, pred_xstart or None).  Evaluation only: a model output that
+        carries a graph raises rather than yield a bound that looks like a loss and has no gradient."""
+        H.require_cuda(x_start, x_t, model_out)
+        if th.is_grad_enabled() and model_out.requires_grad:
+            raise H.MMDError("variational bound: the model output requires grad and this evaluation is not differentiable (only the "
+                             "tensor-valued _vb_terms_bpd with clip_denoised=False is) - call it under torch.no_grad()")
+        tab, _ = self.device_tables(x_t.device)
+        F, C, HW = geom
+        x0, xt, mo = x_start.float().contiguous(), x_t.float().contiguous(), model_out.float().contiguous()
+        N = x0.shape[0]
+        if tables is None:
+            tables = tuple(th.empty(N, dtype=th.float32, device=x0.device) for _ in range(3))
+        vb, xs, em = tables
+        px0 = th.empty_like(x0) if want_x0 else None
+        nz = None if noise is None else noise.float().contiguous()
+        ops.vlb_terms(x0, xt, mo, tab, t.to(th.int64).contiguous(), F, C, HW, self._flags(clip_denoised), vb, xstart_mse=xs,
+                      eps_mse=em if nz is not None else None, noise=nz, pred_xstart=px0)
+        return vb, xs, (em if nz is not None else None), px0
+
+    def _model_out2(self, model, x, t, model_kwargs):
+        """(video_output, audio_output) of the model at x_t; SpacedDiffusion maps the timesteps in here."""
+        return model(x["video"], x["audio"], self._scale_timesteps(t), **(model_kwargs or {}))
+
+    def _vb_terms_bpd(self, model, x_start, x_t, t, clip_denoised=True, model_kwargs=None):
+        """gd:1048-1092 -> {"output": {"video","audio"} [N] (KL for t > 0, decoder NLL at t == 0, bits / dim), "pred_xstart": {...}}."""
+        video_output, audio_output = self._model_out2(model, x_t, t, model_kwargs)
+        res = {"output": {}, "pred_xstart": {}}
+        for key, mo in (("video", video_output), ("audio", audio_output)):
+            vb, _, _, px0 = self._vlb_stream(x_start[key], x_t[key], mo, t, clip_denoised, _geom(x_t[key]), want_x0=True)
+            res["output"][key], res["pred_xstart"][key] = vb, px0
+        return res
+
+    def _prior_bpd(self, x_start):
+        """gd:1213-1229 on one stream's tensor: mean KL(q(x_T | x_0) || N(0, I)) / ln 2.  The KL kernel does it: a two-column table
+        whose 'posterior' is q(x_T | x_0) (mean sqrt_ac[T-1] x_0, log-variance log(1 - ac[T-1])) against a model that predicts mean 0
+        with log-variance 0, evaluated at column 1."""
+        H.require_cuda(x_start)
+        dev = x_start.device
+        key = ("prior", str(dev))
+        if key not in self._dev_tables:
+            tab = np.zeros((7, 2))
+            tab[1] = 1.0
+            tab[2] = self.sqrt_alphas_cumprod[-1]
+            tab[5] = self.log_one_minus_alphas_cumprod[-1]
+            self._dev_tables[key] = th.from_numpy(tab).float().to(dev).contiguous()
+        x0 = x_start.float().contiguous()
+        N = x0.shape[0]
+        zero = th.zeros_like(x0)
+        out = th.empty(N, dtype=th.float32, device=dev)
+        ops.vlb_terms(x0, zero, zero, self._dev_tables[key], th.ones(N, dtype=th.int64, device=dev), 1, 1, x0[0].numel(), 2, out)
+        return out
+
+    @staticmethod
+    def _bpd_result(vb, xstart_mse, mse, prior):
+        """Result tables indexed by t -> the reference's dict: it appends t = T-1 ... 0 and stacks, so column j is t = T-1-j."""
+        vb, xstart_mse, mse = (a.flip(1) for a in (vb, xstart_mse, mse))
+        return {"total_bpd": vb.sum(dim=1) + prior, "prior_bpd": prior, "vb": vb, "xstart_mse": xstart_mse, "mse": mse}
+
+    def calc_bpd_loop(self, model, x_start, clip_denoised=True, model_kwargs=None, use_graph=True, lanes=None):
+        """The whole bound (gd:1231-1286) on {"video","audio"}: total_bpd / prior_bpd [N] and vb / xstart_mse / mse [N, T], each as
+        {"video": ..., "audio": ...}.  Per step t = T-1 ... 0: fresh noise (video first, then audio, through noise_source), x_t =
+        q_sample, one model call (one window-shift draw per block through the model's shift_source), mmd_vlb_terms per stream into
+        device tables; nothing comes back to the host until the caller reads the result.  With a plain MultimodalUNet the step is one
+        graph replay per lane (sampler.GraphStepper, update="vlb"); use_graph=False launches the same kernels eagerly."""
+        device = x_start["video"].device
+        self._sampling_device(device)
+        B, T = x_start["video"].shape[0], self.num_timesteps
+        from .sampler import GraphStepper, unwrap_unet
+        unet = unwrap_unet(model)
+        if use_graph and unet is not None and not (model_kwargs or {}):
+            stepper = GraphStepper(self, unet, B, device, clip_denoised, update="vlb", lanes=lanes)
+            try:
+                stepper.load_x0(x_start["video"], x_start["audio"])
+                for i in self._indices(False):
+                    stepper.step(i)
+                tabs = stepper.results()
+            finally:
+                stepper.close()
+        else:
+            tabs = {k: tuple(th.zeros(B, T, dtype=th.float32, device=device) for _ in range(3)) for k in ("video", "audio")}
+            for i in self._indices(False):
+                t = th.tensor([i] * B, device=device)
+                noise = {"video": self._randn_like(x_start["video"]), "audio": self._randn_like(x_start["audio"])}
+                x_t = {k: self.q_sample(x_start[k], t, noise=noise[k]) for k in ("video", "audio")}
+                with th.no_grad():
+                    video_output, audio_output = self._model_out2(model, x_t, t, model_kwargs)
+                    for key, mo in (("video", video_output), ("audio", audio_output)):
+                        self._vlb_stream(x_start[key], x_t[key], mo, t, clip_denoised, _geom(x_t[key]), noise=noise[key], tables=tabs[key])
+        per = {k: self._bpd_result(*tabs[k], self._prior_bpd(x_start[k])) for k in ("video", "audio")}
+        return {name: {k: per[k][name] for k in ("video", "audio")} for name in ("total_bpd", "prior_bpd", "vb", "xstart_mse", "mse")}
 
     # ------------------------------------------------------------------ training loss (forward value only for now)
     def multimodal_training_losses(self, model, x_start, t, model_kwargs=None, noise=None):

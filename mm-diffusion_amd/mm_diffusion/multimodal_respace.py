@@ -58,6 +58,9 @@ class SpacedDiffusion(GaussianDiffusion):
     def _ddim(self, model, *args, **kwargs):          # ddim_sample / ddim_reverse_sample reach the model through here
         return super()._ddim(self._wrap_model(model), *args, **kwargs)
 
+    def _model_out2(self, model, *args, **kwargs):    # _vb_terms_bpd / the eager calc_bpd_loop reach the model through here
+        return super()._model_out2(self._wrap_model(model), *args, **kwargs)
+
     def multimodal_training_losses(self, model, *args, **kwargs):
         return super().multimodal_training_losses(self._wrap_model(model), *args, **kwargs)
 

@@ -1063,6 +1063,34 @@ def loss_terms(model_out, target, tables, t, F, C, HW, flags, x0=None, xt=None, 
     return mse, vb
 
 
+def vlb_workspace(N, device):
+    return alloc(H.lib().mmd_vlb_workspace_bytes(N) // 8, dtype=torch.float64, device=device)
+
+
+def vlb_terms(x0, xt, model_out, tables, t, F, C, HW, flags, vb, xstart_mse=None, eps_mse=None, noise=None, pred_xstart=None, ws=None):
+    """One variational-bound term of one stream on API-layout fp32 tensors (see include/mmd.h).  vb / xstart_mse / eps_mse are fp32 [N]
+    vectors, or [N, T'] result tables in which sample n lands at column t[n]."""
+    H.require_cuda(x0, xt, model_out, tables, t, vb, xstart_mse, eps_mse, noise, pred_xstart)
+    N = x0.shape[0]
+    ld = 0 if vb.dim() == 1 else vb.stride(0)
+    for r in (vb, xstart_mse, eps_mse):
+        if r is not None and (r.dtype != torch.float32 or r.shape[0] != N or (0 if r.dim() == 1 else r.stride(0)) != ld or r.stride(-1) != 1):
+            raise H.MMDError("vlb_terms: the result buffers must be fp32 [N] vectors or [N, T] tables of one row stride")
+    ws = vlb_workspace(N, x0.device) if ws is None else ws
+    _dispatch("mmd_vlb_terms", x0.data_ptr(), xt.data_ptr(), H.ptr(noise), model_out.data_ptr(), tables.data_ptr(), t.data_ptr(),
+              tables.shape[1], N, F, C, HW, flags, vb.data_ptr(), H.ptr(xstart_mse), H.ptr(eps_mse), ld, H.ptr(pred_xstart), ws.data_ptr(),
+              meta=("vlb_terms", 0, 4 * (x0.numel() * (3 if noise is None else 4) + model_out.numel())))
+    return vb
+
+
+def vlb_terms_bwd(x0, xt, model_out, tables, t, F, C, HW, flags, dvb, g):
+    """g (like model_out) = d(sum dvb * vb)/d model_out of vlb_terms with the mean live; clip off only."""
+    H.require_cuda(x0, xt, model_out, tables, t, dvb, g)
+    _dispatch("mmd_vlb_terms_bwd", x0.data_ptr(), xt.data_ptr(), model_out.data_ptr(), tables.data_ptr(), t.data_ptr(), tables.shape[1],
+              model_out.shape[0], F, C, HW, flags, dvb.data_ptr(), g.data_ptr(), meta=("vlb_terms_bwd", 0, 4 * (2 * x0.numel() + 2 * model_out.numel())))
+    return g
+
+
 # ------------------------------------------------------------------ training step (backward) wrappers
 def loss_terms_bwd(model_out, target, tables, t, F, C, HW, flags, dmse, dvb, g, x0=None, xt=None, vb_scale=1.0):
     """g (like model_out) = d(sum dmse*mse + dvb*vb)/d model_out of loss_terms; see include/mmd.h."""

@@ -1,6 +1,8 @@
 """Graph-replayed denoising step: [U-Net launch plan + fused DDPM update of both streams] captured once into a
 hipGraph (mmd_graph_*), replayed per step.  Between replays only three small device buffers change: the
-timestep (loop index + model timestep), the window shifts and the noise.
+timestep (loop index + model timestep), the window shifts and the noise.  update="vlb" replays one step of the
+variational bound instead (calc_bpd_loop): [q_sample of both streams from static x_0 buffers + U-Net plan + mmd_vlb_terms of
+both streams], whose per-sample results land in device tables at the step's column.
 
 Replaces the per-step host work of the reference loop (gd:561-582 + resp:134-139): th.tensor([i]*B) H2D,
 the timestep_map tensor rebuild, ~16 table uploads and ~55k ATen dispatches."""
@@ -47,6 +49,8 @@ class GraphStepper:
     full-batch (lanes read slices), so the RNG stream does not depend on `lanes`.  Default: see default_lanes."""
 
     def __init__(self, diffusion, unet, batch, device, clip_denoised=True, use_graph=True, update="ddpm", eta=0.0, lanes=None):
+        if update not in ("ddpm", "ddim", "vlb"):
+            raise H.MMDError(f"unknown update {update!r} (ddpm, ddim or vlb)")
         self.diff, self.unet, self.N = diffusion, unet, int(batch)
         self.device = th.device(device)
         self.lanes = default_lanes(self.N) if lanes is None else int(lanes)
@@ -67,14 +71,35 @@ class GraphStepper:
         self.orig_T = getattr(diffusion, "original_num_steps", diffusion.num_timesteps)
         self.use_f32 = self.rescale
         F, C, HW = e.F, e.Cv_in, e.H0 * e.W0
-        self.update_plans = []
+        self.update_plans, self.pre_plans = [], []
+        if update == "vlb":
+            # static x_0, and per stream the (vb, xstart_mse, eps_mse) result tables [N, T] the reductions write at column t
+            T = self.tab.shape[1]
+            _, qtab = diffusion.device_tables(self.device)
+            self.x0_v, self.x0_a = th.zeros_like(self.noise_v), th.zeros_like(self.noise_a)
+            self.res = {k: tuple(th.zeros(self.N, T, dtype=th.float32, device=self.device) for _ in range(3)) for k in ("video", "audio")}
+            self._ws = [(ops.vlb_workspace(n, self.device), ops.vlb_workspace(n, self.device)) for _ in self.engs]
         for r, e in enumerate(self.engs):
             sl = slice(r * n, (r + 1) * n)
             t_idx, nv, na = self.t_idx[sl], self.noise_v[sl], self.noise_a[sl]
             plan = []
+            if update == "vlb":
+                pre = []
+                with ops.recording(pre):       # both on the origin stream: the U-Net plan forks its audio stream behind them
+                    ops.q_sample(self.x0_v[sl], nv, e.x_video, qtab, t_idx)
+                    ops.q_sample(self.x0_a[sl], na, e.x_audio, qtab, t_idx)
+                self.pre_plans.append(pre)
             with ops.recording(plan):
                 # in place: x_{t-1} overwrites x_t (purely elementwise); each update rides its own stream, then join
-                if update == "ddim":       # ddim_sample (gd:821-901): same graph, different fused update
+                if update == "vlb":
+                    rv, ra = (tuple(a[sl] for a in self.res[k]) for k in ("video", "audio"))
+                    with ops.on_stream(0):
+                        ops.vlb_terms(self.x0_v[sl], e.x_video, e.out_video, self.tab, t_idx, F, C, HW, self.flags, rv[0], xstart_mse=rv[1],
+                                      eps_mse=rv[2], noise=nv, ws=self._ws[r][0])
+                    with ops.on_stream(1):
+                        ops.vlb_terms(self.x0_a[sl], e.x_audio, e.out_audio, self.tab, t_idx, 1, e.Ca_in, e.L0, self.flags, ra[0],
+                                      xstart_mse=ra[1], eps_mse=ra[2], noise=na, ws=self._ws[r][1])
+                elif update == "ddim":       # ddim_sample (gd:821-901): same graph, different fused update
                     tab3 = diffusion.ddim_tables(self.device)
                     with ops.on_stream(0):
                         ops.ddim_update(e.x_video, e.out_video, nv, e.x_video, self.tab, tab3, t_idx, F, C, HW, self.flags, eta)
@@ -107,6 +132,15 @@ class GraphStepper:
             e.x_video.copy_(video[r * n:(r + 1) * n])
             e.x_audio.copy_(audio[r * n:(r + 1) * n])
 
+    def load_x0(self, video, audio):
+        """update="vlb": the clean clips every step noises afresh."""
+        self.x0_v.copy_(video)
+        self.x0_a.copy_(audio)
+
+    def results(self):
+        """update="vlb": {"video" / "audio": (vb, xstart_mse, eps_mse)} [N, T] tables, column = loop index t."""
+        return self.res
+
     def set_x(self, key, value):
         """Overwrite one stream of the current state (replacement-method conditional sampling)."""
         n = self.n
@@ -122,6 +156,8 @@ class GraphStepper:
         """Enqueue lane r's U-Net plan and fused update with `stream` as its video-chain stream (its engine's aux = audio chain)."""
         e = self.engs[r]
         aux = e.aux.cuda_stream
+        if self.pre_plans:
+            ops.run_plan(self.pre_plans[r], stream, aux)
         ops.run_plan(e.plan_f32 if self.use_f32 else e.plan, stream, aux)
         ops.run_plan(self.update_plans[r], stream, aux)
 

@@ -398,6 +398,32 @@ class LossTermsFn(Function):
         return g, None, None, None, None, None, None, None, None
 
 
+class VlbTermsFn(Function):
+    """(vb [N], pred_xstart) of one stream with the mean LIVE (KL / RESCALED_KL training, gaussian_diffusion.py:872-882): model_out
+    [N,F,Cm,HW] API layout fp32, clip off.  The gradient reaches the mean channels through pred_x0 -> posterior mean and, with the
+    learned-range variance, the variance channels (mmd_vlb_terms_bwd)."""
+
+    @staticmethod
+    def forward(ctx, model_out, x0, xt, tables, t, geom, flags):
+        mo = model_out.float().contiguous()
+        F, C, HW = geom
+        vb = torch.empty(mo.shape[0], dtype=torch.float32, device=mo.device)
+        px0 = torch.empty_like(x0)
+        ops.vlb_terms(x0, xt, mo, tables, t, F, C, HW, flags, vb, pred_xstart=px0)
+        ctx.save_for_backward(mo, x0, xt, tables, t)
+        ctx.cfg = (geom, flags)
+        ctx.mark_non_differentiable(px0)
+        return vb, px0
+
+    @staticmethod
+    def backward(ctx, dvb, _dpx0):
+        mo, x0, xt, tables, t = ctx.saved_tensors
+        (F, C, HW), flags = ctx.cfg
+        g = torch.empty_like(mo)
+        ops.vlb_terms_bwd(x0, xt, mo, tables, t, F, C, HW, flags, dvb.float().contiguous(), g)
+        return g, None, None, None, None, None, None
+
+
 class DdpmUpdateFn(Function):
     """Differentiable p_sample update of one stream (gd:231-343,415-474; fixed variance): returns (sample, pred_xstart);
     gradients flow through the posterior mean to x_t and to the model output (mmd_ddpm_update_bwd)."""

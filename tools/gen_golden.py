@@ -438,12 +438,12 @@ SR_TRAIN = {
 }
 
 
-def gen_sr_train(only=None):
+def gen_sr_train(only=None, table=None):
     """Training step of the SR model (py_scripts/image_sr_train.py): diffusion.training_losses(model, x0, t, model_kwargs={"low_res": low},
     noise=noise) and .backward() of the reference in train() mode with synth weights (the zero-initialised convs are non-zero).  Per
     fixture: the loss terms, the L2 norm of EVERY parameter's gradient and every stride-th gradient element, with the parameter names.
     Inputs: torch.Generator().manual_seed(seed), draw order x0 (uniform [-1, 1]), low (uniform [-1, 1]), noise (normal)."""
-    for name, (over, B, ts, stride, seed) in SR_TRAIN.items():
+    for name, (over, B, ts, stride, seed) in (table or SR_TRAIN).items():
         if only and name not in only:
             continue
         d, model, diff = _sr_build(**over)
@@ -468,6 +468,101 @@ def gen_sr_train(only=None):
               f"{100.0 * nz / len(names):.1f} % of the norms above 1e-4 of the largest ({min(norms):.3g} ... {max(norms):.3g})")
         save(f"{name}_train_grads", seed=seed, B=B, t=t, stride=stride, names=np.asarray(names), norms=np.asarray(norms), sub=th.cat(subs),
              sub_off=np.asarray(offs), **{k: v.detach() for k, v in losses.items()})
+
+
+# ------------------------------------------------------------------ variational bound (bits / dim), see tests/golden/README_vlb.md
+# the same protocol as SR_TRAIN with use_kl=True (LossType.RESCALED_KL: loss = num_timesteps * the bound term, mean live)
+SR_TRAIN_KL = {"sr_tiny_kl": (dict(use_kl=True), 2, [0, 977], 97, 85)}
+
+
+def _mean_flat(x):
+    return x.mean(dim=list(range(1, x.dim())))
+
+
+def _x0_with_edges(shape, g):
+    """Uniform [-1, 1] with every 37th element at -1 / +1 exactly: the decoder NLL's |x| > 0.999 branches are exercised."""
+    x = th.rand(*shape, generator=g) * 2 - 1
+    flat = x.view(-1)
+    flat[::74] = -1.0
+    flat[37::74] = 1.0
+    return x
+
+
+def gen_bpd(name, seed, respacing, k, **over):
+    """The multimodal bound.  The reference's own multimodal calc_bpd_loop cannot run (it calls .device / randn_like on the stream dict,
+    gd:1249-1257), so the loop is composed here from its working pieces, per step t = T-1 ... 0: noise (video, then audio) from the global
+    CPU generator, q_sample, _vb_terms_bpd (clip on), mean_flat((pred_xstart - x0)^2), _predict_eps_from_xstart, and _prior_bpd at the
+    end - per stream what the tensor-valued calc_bpd_loop does.  Then one _vb_terms_bpd call at t = [0, k], clip on and off."""
+    B = 2
+    f = flags(name, timestep_respacing=respacing, **over)
+    model, diff = msu.create_model_and_diffusion(**f)
+    synth_init(model).eval()
+    g = th.Generator().manual_seed(seed)
+    x0 = {"video": _x0_with_edges((B, *f["video_size"]), g), "audio": _x0_with_edges((B, *f["audio_size"]), g)}
+    keys = ("video", "audio")
+    th.manual_seed(seed)
+    random.seed(seed)
+    cols = {kk: {"vb": [], "xstart_mse": [], "mse": []} for kk in keys}
+    with ShiftRecorder() as rec, th.no_grad():
+        for t in list(range(diff.num_timesteps))[::-1]:
+            tb = th.tensor([t] * B)
+            noise = {kk: th.randn_like(x0[kk]) for kk in keys}
+            x_t = {kk: diff.q_sample(x0[kk], tb, noise=noise[kk]) for kk in keys}
+            out = diff._vb_terms_bpd(model, x_start=x0, x_t=x_t, t=tb, clip_denoised=True)
+            for kk in keys:
+                cols[kk]["vb"].append(out["output"][kk])
+                cols[kk]["xstart_mse"].append(_mean_flat((out["pred_xstart"][kk] - x0[kk]) ** 2))
+                eps = diff._predict_eps_from_xstart(x_t[kk], tb, out["pred_xstart"][kk])
+                cols[kk]["mse"].append(_mean_flat((eps - noise[kk]) ** 2))
+    arrs = {}
+    for kk in keys:
+        vb = th.stack(cols[kk]["vb"], dim=1)
+        prior = diff._prior_bpd(x0[kk])
+        arrs.update({f"vb_{kk}": vb, f"xstart_mse_{kk}": th.stack(cols[kk]["xstart_mse"], dim=1), f"mse_{kk}": th.stack(cols[kk]["mse"], dim=1),
+                     f"prior_bpd_{kk}": prior, f"total_bpd_{kk}": vb.sum(dim=1) + prior})
+    # one term at mixed timesteps: x_t from a generator of its own, the shifts of each call recorded separately
+    g2 = th.Generator().manual_seed(seed + 500)
+    t1 = th.tensor([0, k])
+    n1 = {kk: th.randn(*x0[kk].shape, generator=g2) for kk in keys}
+    x_t1 = {kk: diff.q_sample(x0[kk], t1, noise=n1[kk]) for kk in keys}
+    for clip in (True, False):
+        with ShiftRecorder() as rec1, th.no_grad():
+            out = diff._vb_terms_bpd(model, x_start=x0, x_t=x_t1, t=t1, clip_denoised=clip)
+        arrs[f"term_shifts_clip{int(clip)}"] = np.asarray(rec1.draws)
+        for kk in keys:
+            arrs[f"term_output_{kk}_clip{int(clip)}"] = out["output"][kk]
+            arrs[f"term_pred_xstart_{kk}_clip{int(clip)}"] = out["pred_xstart"][kk]
+    tag = name + ("_ls" if over.get("learn_sigma") else "")
+    save(f"{tag}_bpd", seed=seed, B=B, shifts=np.asarray(rec.draws), timestep_map=np.asarray(diff.timestep_map), x0_video=x0["video"],
+         x0_audio=x0["audio"], term_t=t1, term_xt_video=x_t1["video"], term_xt_audio=x_t1["audio"],
+         alphas_cumprod=diff.alphas_cumprod, **arrs)
+
+
+def gen_sr_bpd(seed=86, respacing="4"):
+    """The reference's own calc_bpd_loop (gaussian_diffusion.py:953-1008) on SR_TINY (learned-range variance) with low_res conditioning;
+    noise from th.manual_seed(seed), one randn_like(x0) per step."""
+    d, model, diff = _sr_build(sr_timestep_respacing=respacing)
+    B = 2
+    g = th.Generator().manual_seed(seed)
+    x0 = _x0_with_edges((B, 3, d["large_size"], d["large_size"]), g)
+    low = th.rand(B, 3, d["small_size"], d["small_size"], generator=g) * 2 - 1
+    th.manual_seed(seed)
+    with th.no_grad():
+        out = diff.calc_bpd_loop(model, x0, clip_denoised=True, model_kwargs={"low_res": low})
+    t1 = th.tensor([0, 2])
+    g2 = th.Generator().manual_seed(seed + 500)
+    x_t1 = diff.q_sample(x0, t1, noise=th.randn(*x0.shape, generator=g2))
+    with th.no_grad():
+        term = diff._vb_terms_bpd(model, x_start=x0, x_t=x_t1, t=t1, clip_denoised=True, model_kwargs={"low_res": low})
+    save("sr_tiny_bpd", seed=seed, B=B, x0=x0, low=low, timestep_map=np.asarray(diff.timestep_map), alphas_cumprod=diff.alphas_cumprod,
+         term_t=t1, term_xt=x_t1, term_output=term["output"], term_pred_xstart=term["pred_xstart"], **out)
+
+
+def gen_vlb():
+    gen_bpd("tiny", 87, "4", 2)
+    gen_bpd("tiny", 88, "4", 3, learn_sigma=True)
+    gen_sr_bpd()
+    gen_sr_train(table=SR_TRAIN_KL)
 
 
 def gen_helpers():
@@ -547,6 +642,7 @@ ALL = {
                                              method="multistep"),
     "full_train_grads": gen_train_grads_full,
     "sr_train": gen_sr_train,
+    "vlb": gen_vlb,
     "tiny_train_loss": lambda: gen_train_loss("tiny", 2, 31),
     "tiny_ls_train_loss": lambda: gen_train_loss("tiny", 2, 32, learn_sigma=True),
     # non-FiLM ResBlocks (use_scale_shift_norm=False, unet:473-477): h + emb_out, then the plain norm
