@@ -12,9 +12,10 @@
  *   - dtype: MMD_F32 (0) or MMD_BF16 (1) = element type of activations / GEMM weights; all statistics,
  *     accumulation, softmax and bias arithmetic are fp32
  *   - every call only ENQUEUES work on `stream` (a hipStream_t); no allocation, no sync: the caller owns all buffers including
- *     workspaces; calls are re-entrant and graph-capturable.  Global state: per-device one-time function attributes, and tuning /
- *     A-B switches read with getenv (INTEGRATION.md section 4 has the table) - MMD_VCONV_RING at every call; once per process, at first
- *     use: MMD_GN_BLOCKS, MMD_STRIP_BLOCKS, MMD_STRIP_K128_RF1, MMD_GEMM_DESC, MMD_TCONV_BLOCKS, MMD_STEM_MFMA, MMD_ATTN_DMA,
+ *     workspaces; calls are re-entrant and graph-capturable.  Global state: the dynamic-LDS size granted to each kernel, per device
+ *     (raised at the first launch that needs more, so a launch sequence that has run once sets nothing when repeated), and the values
+ *     of the tuning / A-B switches of the environment (INTEGRATION.md section 4 has the table; read through mmd_env_int / mmd_env_char /
+ *     mmd_env_set of mmd_common.h) - MMD_VCONV_RING at every call; once per process, at first use: MMD_GN_BLOCKS, MMD_STRIP_BLOCKS, MMD_STRIP_K128_RF1, MMD_GEMM_DESC, MMD_TCONV_BLOCKS, MMD_STEM_MFMA, MMD_ATTN_DMA,
  *     MMD_ATTN_PIPE, MMD_ATTN_PIPE_LDSPAD, MMD_WGRAD_TR, MMD_WGRAD_TILE64, MMD_WGRAD_BLOCKS
  *   - return 0 on success, <0 on error (MMD_ERR_*); mmd_last_error() gives the message (thread local)
  */

@@ -53,6 +53,16 @@ def _llvm_bin():
                        % ", ".join(str(d) for d in cands if d))
 
 
+def _code_objects(path, td):
+    """Unbundle the fat binary `path` (the library or one object) into the directory `td`; returns the paths of its gfx950 code objects
+    in bundle order.  `llvm-objdump --offloading` writes every bundle next to its input (one gfx950 code object per source file)."""
+    lib = os.path.join(td, os.path.basename(path))
+    os.symlink(os.path.abspath(path), lib)
+    subprocess.check_call([os.path.join(_llvm_bin(), "llvm-objdump"), "--offloading", lib], cwd=td, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    cos = [f for f in os.listdir(td) if f.startswith(os.path.basename(path) + ".") and f.endswith("gfx950")]
+    return [os.path.join(td, f) for f in sorted(cos, key=lambda f: (len(f), f))]      # lib.so.2.* before lib.so.10.*
+
+
 def _check_no_packed_f32(path):
     """Disassemble the device code of the linked library and refuse it if any packed-fp32 VALU instruction survived: the feature
     string above is an internal clang spelling, and a compiler that stops recognising it for the DEVICE pass would bring the
@@ -61,16 +71,12 @@ def _check_no_packed_f32(path):
     import tempfile
     llvm = _llvm_bin()
     with tempfile.TemporaryDirectory() as td:
-        # `llvm-objdump --offloading` writes every bundle of the fat binary next to the input (one gfx950 code object per source file)
-        lib = os.path.join(td, "lib.so")
-        os.symlink(os.path.abspath(path), lib)
-        subprocess.check_call([os.path.join(llvm, "llvm-objdump"), "--offloading", lib], cwd=td, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        cos = sorted(f for f in os.listdir(td) if f.endswith("gfx950"))
+        cos = _code_objects(path, td)
         if len(cos) < len(SOURCES) - 1:          # (mmd_core.hip has no kernels)
             raise RuntimeError("build check: expected >= %d gfx950 code objects in %s, found %d" % (len(SOURCES) - 1, path, len(cos)))
         asm = ""
         for f in cos:
-            asm += subprocess.run([os.path.join(llvm, "llvm-objdump"), "-d", "--mcpu=gfx950", os.path.join(td, f)],
+            asm += subprocess.run([os.path.join(llvm, "llvm-objdump"), "-d", "--mcpu=gfx950", f],
                                   stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, check=True).stdout.decode(errors="replace")
     n_mfma = len(re.findall(r"\bv_mfma_", asm))
     bad = re.findall(r"\bv_pk_(?:add|mul|fma)_f32\b", asm)

@@ -224,16 +224,8 @@ static int launch_aconv(const AConvParams& p, hipStream_t st) {
   constexpr int CS = 32 * CSUB;
   const int rowblocks = cdiv(p.M, 128), nsplit = p.Cout / CS;
   const size_t lds = 2 * (size_t)CS * 128 + (size_t)CS * 4 + 4 * CSUB * 2 * 2 * 2 * 2 * 4 + 4 * (size_t)p.Cin * 4;
-  static bool attr_done[MMD_MAX_DEVICES] = {};
-  bool& attr_set = attr_done[mmd_device_slot()];
-  if (!attr_set) {
-    const size_t lds_max = 2 * (size_t)CS * 128 + (size_t)CS * 4 + 4 * CSUB * 2 * 2 * 2 * 2 * 4 + 4 * (size_t)2048 * 4;
-    hipError_t e = hipFuncSetAttribute((const void*)aconv_kernel<CSUB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
-    if (e != hipSuccess) return mmd_set_error(MMD_ERR_LAUNCH, "aconv: set LDS attr: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((aconv_kernel<CSUB>), dim3(rowblocks * nsplit), dim3(256), lds, st, p, nsplit);
-  return mmd_check_launch("aconv");
+  const size_t lds_max = 2 * (size_t)CS * 128 + (size_t)CS * 4 + 4 * CSUB * 2 * 2 * 2 * 2 * 4 + 4 * (size_t)2048 * 4;
+  return mmd_launch_cap<aconv_kernel<CSUB>>("aconv", dim3(rowblocks * nsplit), dim3(256), lds, lds_max, st, p, nsplit);
 }
 
 // GroupNorm32(+FiLM)(+SiLU) -> Conv1d(k = 3, dilation, zero "same" padding) on channels-last rows of S = M / L samples (bf16).

@@ -1422,65 +1422,37 @@ static int launch_mfma(const AttnParams& p, int qmax, hipStream_t st) {
   constexpr int DT = (D + 31) / 32;
   const size_t lds = 64 * SK + DT * 32 * SVT_STRIDE;
   dim3 grid(cdiv(qmax, 128), p.heads, p.nb * p.G);
-  hipLaunchKernelGGL(attn_mfma_kernel<D>, grid, dim3(256), lds, st, p);
-  return mmd_check_launch("attn_mfma");
+  return mmd_launch<attn_mfma_kernel<D>>("attn_mfma", grid, dim3(256), lds, st, p);
 }
 
 template <int D>
 static int launch_dma(const AttnParams& p, int qmax, hipStream_t st) {
   const size_t lds = 4 * 64 * 128;
   dim3 grid(cdiv(qmax, 128), p.heads, p.nb * p.G);
-  hipLaunchKernelGGL(attn_dma_kernel<D>, grid, dim3(256), lds, st, p);
-  return mmd_check_launch("attn_dma");
+  return mmd_launch<attn_dma_kernel<D>>("attn_dma", grid, dim3(256), lds, st, p);
 }
 
 template <int D>
 static int launch_pipe(const AttnParams& p, int qmax, hipStream_t st) {
   // tuning switch (read once; tools only): MMD_ATTN_PIPE_LDSPAD = extra bytes of LDS per block, e.g. 65536 = one block per CU
-  static const int pad = [] { const char* e = getenv("MMD_ATTN_PIPE_LDSPAD"); const int v = e ? atoi(e) : 0; return v > 0 && v <= 120 * 1024 ? v : 0; }();
+  static const int pad = [] { const int v = mmd_env_int("MMD_ATTN_PIPE_LDSPAD", 0); return v <= 120 * 1024 ? v : 0; }();
   const size_t lds = 4 * 64 * 128 + (size_t)pad;
-  if (pad) {
-    static bool attr_done[MMD_MAX_DEVICES] = {};
-    bool& attr_set = attr_done[mmd_device_slot()];
-    if (!attr_set) {
-      if (hipFuncSetAttribute((const void*)attn_pipe_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return mmd_set_error(MMD_ERR_LAUNCH, "attn_pipe: set LDS attr");
-      attr_set = true;
-    }
-  }
   dim3 grid(cdiv(qmax, 128), p.heads, p.nb * p.G);
-  hipLaunchKernelGGL(attn_pipe_kernel<D>, grid, dim3(256), lds, st, p);
-  return mmd_check_launch("attn_pipe");
+  return mmd_launch<attn_pipe_kernel<D>>("attn_pipe", grid, dim3(256), lds, st, p);
 }
 
 template <int D>
 static int launch_stage(const AttnParams& p, int qmax, hipStream_t st) {
   const size_t lds = (size_t)ATS_KEYS * (D * 2 + 16) + (size_t)D * ATS_VT_STRIDE;
-  static bool attr_done[MMD_MAX_DEVICES] = {};
-  bool& attr_set = attr_done[mmd_device_slot()];
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)attn_stage_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return mmd_set_error(MMD_ERR_LAUNCH, "attn_stage: set LDS attr: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
   dim3 grid(cdiv(qmax, 256), p.heads, p.nb * p.G);
-  hipLaunchKernelGGL((attn_stage_kernel<D>), grid, dim3(512), lds, st, p);
-  return mmd_check_launch("attn_stage");
+  return mmd_launch<attn_stage_kernel<D>>("attn_stage", grid, dim3(512), lds, st, p);
 }
 
 template <typename T, int KT, int OB>
 static int launch_generic_as(const AttnParams& p, int qmax, hipStream_t st) {
   const size_t lds = (size_t)(64 * (p.ch + 1) + KT * (p.ch + 1) + KT * p.ch + 64 * (KT + 1) + 192) * sizeof(float);
-  static bool attr_done[MMD_MAX_DEVICES] = {};
-  bool& attr_set = attr_done[mmd_device_slot()];
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)attn_generic_kernel<T, KT, OB>, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024);
-    if (e != hipSuccess) return mmd_set_error(MMD_ERR_LAUNCH, "attn_generic: set LDS attr: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
   dim3 grid(cdiv(qmax, 64), p.heads, p.nb * p.G);
-  hipLaunchKernelGGL((attn_generic_kernel<T, KT, OB>), grid, dim3(256), lds, st, p);
-  return mmd_check_launch("attn_generic");
+  return mmd_launch_cap<attn_generic_kernel<T, KT, OB>>("attn_generic", grid, dim3(256), lds, 120 * 1024, st, p);
 }
 
 template <typename T>
@@ -1513,13 +1485,13 @@ static int attn_fwd_impl(int dtype, const void* Q, int64_t ldq, int q_off, const
   // the staged kernel stores O as whole 16-byte vectors (the per-128-query kernel: 8-byte pieces): stricter output alignment
   const bool stage_ok = dtype == MMD_BF16 && aligned && ch == 64 && ldo % 8 == 0 && (uintptr_t)O % 16 == 0;
   // DMA-staged kernel (impl 4; the default at head width 64 unless MMD_ATTN_DMA=0): 32-bit byte offsets into the K/V rows
-  static const bool dma_on = [] { const char* e = getenv("MMD_ATTN_DMA"); return !(e && e[0] == '0'); }();
+  static const bool dma_on = mmd_env_char("MMD_ATTN_DMA") != '0';
   // Its descriptor covers the K/V rows of the batches of ONE launch: a batch range beyond 2 GB is cut into several launches of
   // the same kernel (the kernel family of a layer - and with it the last bits of its output - must not depend on the batch size)
   const int64_t kv_batch_bytes = k_rows_per_batch * ldkv * 2;
   const bool dma_ok = stage_ok && kv_batch_bytes < 0x7fffffffLL;
   // hand-placed pipelined kernel (impl 5; round 6): same staging, same arithmetic, bitwise the same output
-  static const bool pipe_on = [] { const char* e = getenv("MMD_ATTN_PIPE"); return e && e[0] == '1'; }();
+  static const bool pipe_on = mmd_env_char("MMD_ATTN_PIPE") == '1';
   const bool use_pipe = impl == 5 || (impl == 0 && pipe_on);
   if (impl == 5 && !dma_ok) return mmd_set_error(MMD_ERR_UNSUPPORTED, "attn_fwd impl 5 (pipelined): needs bf16, head width 64, aligned rows, one batch of K/V below 2 GB");
   if (impl == 4 && !dma_ok) return mmd_set_error(MMD_ERR_UNSUPPORTED, "attn_fwd impl 4 (DMA-staged): needs bf16, head width 64, aligned rows, one batch of K/V below 2 GB");
@@ -1584,16 +1556,8 @@ extern "C" int mmd_attn_fwd_lse(int dtype, const void* Q, int64_t ldq, int q_off
 template <typename T, int CHQ>
 static int launch_small(const SmallAttnParams& p, hipStream_t st) {
   const size_t lds = (size_t)4 * 2 * 32 * (CHQ * 4) * sizeof(float);
-  static bool attr_done[MMD_MAX_DEVICES] = {};
-  bool& attr_set = attr_done[mmd_device_slot()];
-  if (!attr_set && lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)attn_small_kernel<T, CHQ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return mmd_set_error(MMD_ERR_LAUNCH, "attn_small: set LDS attr: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
   const int64_t items = (int64_t)p.S * p.heads;
-  hipLaunchKernelGGL((attn_small_kernel<T, CHQ>), dim3((unsigned)((items + 3) / 4)), dim3(256), lds, st, p);
-  return mmd_check_launch("attn_small");
+  return mmd_launch<attn_small_kernel<T, CHQ>>("attn_small", dim3((unsigned)((items + 3) / 4)), dim3(256), lds, st, p);
 }
 
 template <typename T>
@@ -1626,12 +1590,11 @@ extern "C" int mmd_attn_small_fwd(int dtype, const void* QKV, int64_t ld, void* 
   if (dtype == MMD_BF16 && Tn <= 16 && vec && (p.ch == 32 || p.ch == 64 || p.ch == 96 || p.ch == 128)) {
     const dim3 grid((unsigned)(((int64_t)S * heads + 3) / 4));
     switch (p.ch) {
-      case 32: hipLaunchKernelGGL(attn_small_mfma_kernel<32>, grid, dim3(256), 0, st, p); break;
-      case 64: hipLaunchKernelGGL(attn_small_mfma_kernel<64>, grid, dim3(256), 0, st, p); break;
-      case 96: hipLaunchKernelGGL(attn_small_mfma_kernel<96>, grid, dim3(256), 0, st, p); break;
-      default: hipLaunchKernelGGL(attn_small_mfma_kernel<128>, grid, dim3(256), 0, st, p); break;
+      case 32: return mmd_launch<attn_small_mfma_kernel<32>>("attn_small_mfma", grid, dim3(256), 0, st, p);
+      case 64: return mmd_launch<attn_small_mfma_kernel<64>>("attn_small_mfma", grid, dim3(256), 0, st, p);
+      case 96: return mmd_launch<attn_small_mfma_kernel<96>>("attn_small_mfma", grid, dim3(256), 0, st, p);
+      default: return mmd_launch<attn_small_mfma_kernel<128>>("attn_small_mfma", grid, dim3(256), 0, st, p);
     }
-    return mmd_check_launch("attn_small_mfma");
   }
   return dtype == MMD_BF16 ? dispatch_small<__bf16>(p, st) : dispatch_small<float>(p, st);
 }

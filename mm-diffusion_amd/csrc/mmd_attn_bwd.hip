@@ -114,41 +114,22 @@ extern "C" int mmd_attn_bwd(int dtype, const void* Q, int64_t ldq, int q_off, co
   const int qmax = q_total - (G - 1) * q_per_group;
   if (ch > 128) {                              // 32-row tiles: 4 x [32][ch+1] + [32][33] fp32 = 103,488 B (101.1 KiB) at 192
     const size_t ldsw = (size_t)(4 * 32 * (ch + 1) + 32 * 33 + 32 * 3 + 16) * sizeof(float);
-    const void* w1 = dtype == MMD_BF16 ? (const void*)attn_bwd_dq_wide_kernel<__bf16> : (const void*)attn_bwd_dq_wide_kernel<float>;
-    const void* w2 = dtype == MMD_BF16 ? (const void*)attn_bwd_dkv_wide_kernel<__bf16> : (const void*)attn_bwd_dkv_wide_kernel<float>;
-    static bool attr_done[MMD_MAX_DEVICES][2] = {};
-    bool& attr_set = attr_done[mmd_device_slot()][dtype == MMD_BF16 ? 0 : 1];
-    if (!attr_set) {
-      if (hipFuncSetAttribute(w1, hipFuncAttributeMaxDynamicSharedMemorySize, 104 * 1024) != hipSuccess ||
-          hipFuncSetAttribute(w2, hipFuncAttributeMaxDynamicSharedMemorySize, 104 * 1024) != hipSuccess)
-        return mmd_set_error(MMD_ERR_LAUNCH, "attn_bwd: set LDS attr failed");
-      attr_set = true;
-    }
-    dim3 w1g(cdiv(qmax, 32), heads, nb * G);
-    if (dtype == MMD_BF16) hipLaunchKernelGGL(attn_bwd_dq_wide_kernel<__bf16>, w1g, dim3(256), ldsw, st, p);
-    else hipLaunchKernelGGL(attn_bwd_dq_wide_kernel<float>, w1g, dim3(256), ldsw, st, p);
-    int wrc = mmd_check_launch("attn_bwd_dq_wide");
-    if (wrc) return wrc;
-    dim3 w2g(cdiv(k_mod, 32), heads, nb);
-    if (dtype == MMD_BF16) hipLaunchKernelGGL(attn_bwd_dkv_wide_kernel<__bf16>, w2g, dim3(256), ldsw, st, p);
-    else hipLaunchKernelGGL(attn_bwd_dkv_wide_kernel<float>, w2g, dim3(256), ldsw, st, p);
-    return mmd_check_launch("attn_bwd_dkv_wide");
+    dim3 w1g(cdiv(qmax, 32), heads, nb * G), w2g(cdiv(k_mod, 32), heads, nb);
+    return mmd_by_dtype(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      int wrc = mmd_launch_cap<attn_bwd_dq_wide_kernel<T>>("attn_bwd_dq_wide", w1g, dim3(256), ldsw, 104 * 1024, st, p);
+      if (wrc) return wrc;
+      return mmd_launch_cap<attn_bwd_dkv_wide_kernel<T>>("attn_bwd_dkv_wide", w2g, dim3(256), ldsw, 104 * 1024, st, p);
+    });
   }
   const size_t lds = (size_t)(4 * 64 * (ch + 1) + 64 * 65 + 64 * 3 + 16) * sizeof(float);
-  const void* f1 = dtype == MMD_BF16 ? (const void*)attn_bwd_dq_kernel<__bf16> : (const void*)attn_bwd_dq_kernel<float>;
-  const void* f2 = dtype == MMD_BF16 ? (const void*)attn_bwd_dkv_kernel<__bf16> : (const void*)attn_bwd_dkv_kernel<float>;
-  if (hipFuncSetAttribute(f1, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024) != hipSuccess ||
-      hipFuncSetAttribute(f2, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024) != hipSuccess)
-    return mmd_set_error(MMD_ERR_LAUNCH, "attn_bwd: set LDS attr failed");
-  dim3 g1(cdiv(qmax, 64), heads, nb * G);
-  if (dtype == MMD_BF16) hipLaunchKernelGGL(attn_bwd_dq_kernel<__bf16>, g1, dim3(256), lds, st, p);
-  else hipLaunchKernelGGL(attn_bwd_dq_kernel<float>, g1, dim3(256), lds, st, p);
-  int rc = mmd_check_launch("attn_bwd_dq");
-  if (rc) return rc;
-  dim3 g2(cdiv(k_mod, 64), heads, nb);
-  if (dtype == MMD_BF16) hipLaunchKernelGGL(attn_bwd_dkv_kernel<__bf16>, g2, dim3(256), lds, st, p);
-  else hipLaunchKernelGGL(attn_bwd_dkv_kernel<float>, g2, dim3(256), lds, st, p);
-  return mmd_check_launch("attn_bwd_dkv");
+  dim3 g1(cdiv(qmax, 64), heads, nb * G), g2(cdiv(k_mod, 64), heads, nb);
+  return mmd_by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    int rc = mmd_launch_cap<attn_bwd_dq_kernel<T>>("attn_bwd_dq", g1, dim3(256), lds, 158 * 1024, st, p);
+    if (rc) return rc;
+    return mmd_launch_cap<attn_bwd_dkv_kernel<T>>("attn_bwd_dkv", g2, dim3(256), lds, 158 * 1024, st, p);
+  });
 }
 
 // ============================================================================= short-sequence (temporal) backward
@@ -301,17 +282,8 @@ __global__ __launch_bounds__(256) void attn_small_bwd_kernel(const SmallAttnBwdP
 template <typename T, int CHQ>
 static int launch_small_bwd(const SmallAttnBwdParams& p, hipStream_t st) {
   const size_t lds = (size_t)4 * (4 * p.Tn * (CHQ * 4) + 2 * p.Tn * (p.Tn + 1)) * sizeof(float);
-  if (lds > 64 * 1024) {
-    static size_t attr = 0;
-    if (lds > attr) {
-      hipError_t e = hipFuncSetAttribute((const void*)attn_small_bwd_kernel<T, CHQ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return mmd_set_error(MMD_ERR_LAUNCH, "attn_small_bwd: set LDS attr: %s", hipGetErrorString(e));
-      attr = lds;
-    }
-  }
   const int64_t items = (int64_t)p.S * p.heads;
-  hipLaunchKernelGGL((attn_small_bwd_kernel<T, CHQ>), dim3((unsigned)((items + 3) / 4)), dim3(256), lds, st, p);
-  return mmd_check_launch("attn_small_bwd");
+  return mmd_launch<attn_small_bwd_kernel<T, CHQ>>("attn_small_bwd", dim3((unsigned)((items + 3) / 4)), dim3(256), lds, st, p);
 }
 
 template <typename T>

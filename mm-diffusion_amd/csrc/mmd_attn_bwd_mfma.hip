@@ -379,33 +379,12 @@ __global__ __launch_bounds__(256, (D <= 64 ? 2 : 1)) void attn_bwd_dkv_mfma_kern
 template <int D, int NS = 1>
 static int launch_bwd_mfma(const AttnBwdMParams& p, hipStream_t st) {
   constexpr int SK = D * 2 + 16, DT = (D + 31) / 32, DTA = (D / NS + 31) / 32;
-  const size_t lds_q = 128 * SK + DT * 32 * TSTRIDE;
+  const size_t lds_q = 128 * SK + DT * 32 * TSTRIDE;                     // head width 192: 75.5 KB
   const size_t lds_kv = 128 * SK + 2 * DTA * 32 * TSTRIDE + 128 * sizeof(float);
   const int qmax = (int)(p.q_rows_per_batch - (int64_t)(p.G - 1) * p.q_per_group);
-  const void* fkv = (const void*)attn_bwd_dkv_mfma_kernel<D, NS>;
-  if (lds_kv > 64 * 1024) {
-    static bool attr_done[MMD_MAX_DEVICES] = {};
-  bool& attr_set = attr_done[mmd_device_slot()];
-    if (!attr_set) {
-      if (hipFuncSetAttribute(fkv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv) != hipSuccess)
-        return mmd_set_error(MMD_ERR_LAUNCH, "attn_bwd_mfma: set LDS attr failed");
-      attr_set = true;
-    }
-  }
-  if (lds_q > 64 * 1024) {                     // head width 192: 75.5 KB
-    static bool attr_done_q[MMD_MAX_DEVICES] = {};
-    bool& attr_set = attr_done_q[mmd_device_slot()];
-    if (!attr_set) {
-      if (hipFuncSetAttribute((const void*)attn_bwd_dq_mfma_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q) != hipSuccess)
-        return mmd_set_error(MMD_ERR_LAUNCH, "attn_bwd_mfma: set LDS attr failed (dQ)");
-      attr_set = true;
-    }
-  }
-  hipLaunchKernelGGL(attn_bwd_dq_mfma_kernel<D>, dim3(cdiv(qmax, 128), p.heads, p.nb * p.G), dim3(256), lds_q, st, p);
-  int rc = mmd_check_launch("attn_bwd_dq_mfma");
+  int rc = mmd_launch<attn_bwd_dq_mfma_kernel<D>>("attn_bwd_dq_mfma", dim3(cdiv(qmax, 128), p.heads, p.nb * p.G), dim3(256), lds_q, st, p);
   if (rc) return rc;
-  hipLaunchKernelGGL((attn_bwd_dkv_mfma_kernel<D, NS>), dim3(cdiv(p.k_rows_per_batch, 128), p.heads * NS, p.nb), dim3(256), lds_kv, st, p);
-  return mmd_check_launch("attn_bwd_dkv_mfma");
+  return mmd_launch<attn_bwd_dkv_mfma_kernel<D, NS>>("attn_bwd_dkv_mfma", dim3(cdiv(p.k_rows_per_batch, 128), p.heads * NS, p.nb), dim3(256), lds_kv, st, p);
 }
 
 // bf16 MFMA backward of mmd_attn_fwd_lse (same row/window arguments).  lse2 from the forward; dsum_ws fp32 [q rows, heads].

@@ -709,7 +709,7 @@ extern "C" int mmd_conv_wgrad(int dtype, const void* dY, int64_t lddy, const voi
   p.M = M; p.Cout = Cout; p.Cin = Cin; p.ntaps = ntaps; p.D0 = D0; p.D1 = D1; p.D2 = D2;
   for (int i = 0; i < ntaps * 3; ++i) p.taps[i] = taps[i];
   hipStream_t st = (hipStream_t)stream;
-  static const bool use128 = getenv("MMD_WGRAD_TILE64") == nullptr;      // A/B switch for tools/wgrad_bench.py
+  static const bool use128 = !mmd_env_set("MMD_WGRAD_TILE64");           // A/B switch for tools/wgrad_bench.py
   if (use128 && dtype == MMD_BF16 && Cout >= 64 && Cin >= 64) {          // transposed-staging 128x128 kernel
     const int tiles = cdiv(Cout, 128) * cdiv(Cin, 128) * ntaps;
     // Row splits per launch.  Every split adds Cout * Cin * ntaps atomics on the same addresses; the blocks of a split share its rows of dY / X.
@@ -731,7 +731,7 @@ extern "C" int mmd_conv_wgrad(int dtype, const void* dY, int64_t lddy, const voi
     int splits = 1, xo = 0;
     p.rows_per_split = M;
     {
-      static const int env_target = getenv("MMD_WGRAD_BLOCKS") ? atoi(getenv("MMD_WGRAD_BLOCKS")) : 0;
+      static const int env_target = mmd_env_int("MMD_WGRAD_BLOCKS", 0);
       static const int targets[] = {256, 384, 512, 768, 1024, 1536, 2048};
       int64_t best = -1;
       for (int t : targets) {
@@ -744,28 +744,20 @@ extern "C" int mmd_conv_wgrad(int dtype, const void* dY, int64_t lddy, const voi
     }
     p.xcd_order = xo;
     // DMA-staged kernel (round 3; MMD_WGRAD_TR=0: the transposed-staging kernel): 32-bit byte offsets, float-reciprocal row positions
-    static const bool use_tr = [] { const char* e = getenv("MMD_WGRAD_TR"); return !(e && e[0] == '0'); }();
+    static const char tr_env = mmd_env_char("MMD_WGRAD_TR");
+    const bool use_tr = tr_env != '0';
     // measured (tools/wgrad_bench.py, batch 8): 3x3 ds1 128->128 436 -> 372 us, ds2 256->256 405 -> 251, ds4 384->384 240 -> 180, ds8 130 -> 110;
     // the 1x1 / k=3 convs lose what the separate colsum launch costs (1x1 ds1: 82 -> 127 us), so they stay on the older kernel
     // round 6: the bias gradient rides in the kernel (no colsum launch), so every tap count uses it; MMD_WGRAD_TR=9: the 9-tap convs only
-    static const int tr_min_taps = [] { const char* e = getenv("MMD_WGRAD_TR"); return e && e[0] == '9' ? 9 : 1; }();
+    const int tr_min_taps = tr_env == '9' ? 9 : 1;
     if (use_tr && ntaps >= tr_min_taps && M < (1 << 24) && (int64_t)M * lddy * 2 < 0x7fffffffLL && (int64_t)M * ldx * 2 < 0x7fffffffLL) {
       const size_t lds = 2 * 4 * 64 * 128;
-      static bool attr_done[MMD_MAX_DEVICES] = {};
-      bool& attr_set = attr_done[mmd_device_slot()];
-      if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)wgrad_tr_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return mmd_set_error(MMD_ERR_LAUNCH, "conv_wgrad: set LDS attr: %s", hipGetErrorString(e));
-        attr_set = true;
-      }
       p.db = db;                                                 // column sums ride in the (tap 0, ci tile 0) blocks: no colsum launch
       p.splits = splits;
-      hipLaunchKernelGGL(wgrad_tr_bf16_kernel, dim3(p.xcd_order ? 8 * tiles * cdiv(splits, 8) : tiles * splits), dim3(256), lds, st, p);
-      return mmd_check_launch("conv_wgrad");
+      return mmd_launch<wgrad_tr_bf16_kernel>("conv_wgrad", dim3(p.xcd_order ? 8 * tiles * cdiv(splits, 8) : tiles * splits), dim3(256), lds, st, p);
     } else {
       p.db = db;                                                 // column sums ride in the (tap 0, ci tile 0) blocks: no colsum launch
-      hipLaunchKernelGGL(wgrad128_bf16_kernel, dim3(cdiv(Cout, 128), cdiv(Cin, 128) * ntaps, splits), dim3(256), 0, st, p);
-      return mmd_check_launch("conv_wgrad");
+      return mmd_launch<wgrad128_bf16_kernel>("conv_wgrad", dim3(cdiv(Cout, 128), cdiv(Cin, 128) * ntaps, splits), dim3(256), 0, st, p);
     }
   } else {
     const int tiles = cdiv(Cout, 64) * cdiv(Cin, 64) * ntaps;
@@ -773,20 +765,20 @@ extern "C" int mmd_conv_wgrad(int dtype, const void* dY, int64_t lddy, const voi
     p.rows_per_split = cdiv(cdiv(M, splits), 64) * 64;
     splits = cdiv(M, p.rows_per_split);
     dim3 grid(cdiv(Cout, 64), cdiv(Cin, 64) * ntaps, splits);
-    if (dtype == MMD_BF16) hipLaunchKernelGGL(wgrad_kernel<__bf16>, grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(wgrad_kernel<float>, grid, dim3(256), 0, st, p);
+    const int rc = mmd_by_dtype(dtype, [&](auto t) { return mmd_launch<wgrad_kernel<typename decltype(t)::type>>("conv_wgrad", grid, dim3(256), 0, st, p); });
+    if (rc || !db) return rc;
   }
-  int rc = mmd_check_launch("conv_wgrad");
-  if (rc || !db) return rc;
   const int rpb = M >= 65536 ? 256 : 128;
   const int es = dtype == MMD_BF16 ? 2 : 4;
   for (int c0 = 0; c0 < Cout; c0 += 256 * epv) {       // a block covers <= 256 16-byte column vectors: wide fp32 outputs (qkv 1536) go in slabs
     const int cw = Cout - c0 < 256 * epv ? Cout - c0 : 256 * epv;
     const char* src = (const char*)dY + (int64_t)c0 * es;
-    if (dtype == MMD_BF16) hipLaunchKernelGGL(colsum_kernel<__bf16>, dim3(cdiv(M, rpb)), dim3(256), 0, st, src, lddy, M, cw, db + c0, rpb);
-    else hipLaunchKernelGGL(colsum_kernel<float>, dim3(cdiv(M, rpb)), dim3(256), 0, st, src, lddy, M, cw, db + c0, rpb);
+    const int rc = mmd_by_dtype(dtype, [&](auto t) {
+      return mmd_launch<colsum_kernel<typename decltype(t)::type>>("colsum", dim3(cdiv(M, rpb)), dim3(256), 0, st, src, lddy, M, cw, db + c0, rpb);
+    });
+    if (rc) return rc;
   }
-  return mmd_check_launch("colsum");
+  return MMD_OK;
 }
 
 // out[s, c] += sum over the Tn rows of slice s of dY[row, c] (S contiguous slices): the gradient of a per-sample row bias - the
@@ -801,10 +793,13 @@ extern "C" int mmd_colsum_slices(int dtype, const void* dY, int64_t lddy, int S,
     for (int c0 = 0; c0 < C; c0 += 256 * epv) {
       const int cw = C - c0 < 256 * epv ? C - c0 : 256 * epv;
       const char* src = (const char*)dY + ((int64_t)s * Tn * lddy + c0) * es;
-      if (dtype == MMD_BF16) hipLaunchKernelGGL(colsum_kernel<__bf16>, dim3(cdiv(Tn, rpb)), dim3(256), 0, st, src, lddy, (int)Tn, cw, out + (int64_t)s * ldo + c0, rpb);
-      else hipLaunchKernelGGL(colsum_kernel<float>, dim3(cdiv(Tn, rpb)), dim3(256), 0, st, src, lddy, (int)Tn, cw, out + (int64_t)s * ldo + c0, rpb);
+      const int rc = mmd_by_dtype(dtype, [&](auto t) {
+        return mmd_launch<colsum_kernel<typename decltype(t)::type>>("colsum_slices", dim3(cdiv(Tn, rpb)), dim3(256), 0, st, src, lddy, (int)Tn, cw,
+                                                                     out + (int64_t)s * ldo + c0, rpb);
+      });
+      if (rc) return rc;
     }
-  return mmd_check_launch("colsum_slices");
+  return MMD_OK;
 }
 
 __global__ __launch_bounds__(256) void zero_f32_kernel(float* __restrict__ p, int64_t n) {
@@ -834,34 +829,28 @@ static int gn_bwd_impl(int dtype, const void* x, int64_t ldx, const void* dy, in
   // zeroed by a kernel, not hipMemsetAsync: memset nodes of a captured graph were observed to lose their ordering against the
   // neighbouring kernel nodes on replay (train_graph.py), a fill kernel is an ordinary node of the chain
   if (!ws0) {
-    hipLaunchKernelGGL(zero_f32_kernel, dim3(ew_grid_b((int64_t)S * C * 2)), dim3(256), 0, st, PQ, (int64_t)S * C * 2);
-    if (int zrc = mmd_check_launch("gn_bwd_zero")) return zrc;
+    if (int zrc = mmd_launch<zero_f32_kernel>("gn_bwd_zero", dim3(ew_grid_b((int64_t)S * C * 2)), dim3(256), 0, st, PQ, (int64_t)S * C * 2)) return zrc;
   }
   const int rpp = max(1, 256 / (CW / epv));
   int R = 4 * rpp;
   while ((int64_t)S * cdiv(Tn, R) > 1280 && R < 1024) R *= 2;
   dim3 grid(cdiv(Tn, R), S, NZ);
-  if (dtype == MMD_BF16)
-    hipLaunchKernelGGL(gn_bwd_reduce_kernel<__bf16>, grid, dim3(256), 0, st, (const char*)x, ldx, (const char*)dy, lddy, C, g, a, b, mr, act, R, PQ);
-  else
-    hipLaunchKernelGGL(gn_bwd_reduce_kernel<float>, grid, dim3(256), 0, st, (const char*)x, ldx, (const char*)dy, lddy, C, g, a, b, mr, act, R, PQ);
-  int rc = mmd_check_launch("gn_bwd_reduce");
+  int rc = mmd_by_dtype(dtype, [&](auto t) {
+    return mmd_launch<gn_bwd_reduce_kernel<typename decltype(t)::type>>("gn_bwd_reduce", grid, dim3(256), 0, st, (const char*)x, ldx, (const char*)dy, lddy, C,
+                                                                        g, a, b, mr, act, R, PQ);
+  });
   if (rc) return rc;
-  hipLaunchKernelGGL(gn_bwd_params_kernel, dim3(C <= 1024 ? 4 : 8, S), dim3(256), 0, st, PQ, C, Tn, gamma, beta, film, film_ld, dgamma, dbeta, dfilm,
-                     dfilm_ld, m12, ws0 ? 1 : 0);
-  rc = mmd_check_launch("gn_bwd_params");
+  rc = mmd_launch<gn_bwd_params_kernel>("gn_bwd_params", dim3(C <= 1024 ? 4 : 8, S), dim3(256), 0, st, PQ, C, Tn, gamma, beta, film, film_ld, dgamma, dbeta,
+                                        dfilm, dfilm_ld, m12, ws0 ? 1 : 0);
   if (rc) return rc;
   int R3 = 4 * rpp;
   while ((int64_t)S * cdiv(Tn, R3) > 4096 && R3 < 1024) R3 *= 2;
   dim3 grid3(cdiv(Tn, R3), S, NZ);
   (void)rows;
-  if (dtype == MMD_BF16)
-    hipLaunchKernelGGL(gn_bwd_apply_kernel<__bf16>, grid3, dim3(256), 0, st, (const char*)x, ldx, (const char*)dy, lddy, (char*)dx, lddx, C, g,
-                       a, b, mr, (const float*)m12, gamma, film, film_ld, act, R3);
-  else
-    hipLaunchKernelGGL(gn_bwd_apply_kernel<float>, grid3, dim3(256), 0, st, (const char*)x, ldx, (const char*)dy, lddy, (char*)dx, lddx, C, g,
-                       a, b, mr, (const float*)m12, gamma, film, film_ld, act, R3);
-  return mmd_check_launch("gn_bwd_apply");
+  return mmd_by_dtype(dtype, [&](auto t) {
+    return mmd_launch<gn_bwd_apply_kernel<typename decltype(t)::type>>("gn_bwd_apply", grid3, dim3(256), 0, st, (const char*)x, ldx, (const char*)dy, lddy,
+                                                                       (char*)dx, lddx, C, g, a, b, mr, (const float*)m12, gamma, film, film_ld, act, R3);
+  });
 }
 
 extern "C" int mmd_gn_bwd(int dtype, const void* x, int64_t ldx, const void* dy, int64_t lddy, void* dx, int64_t lddx, int64_t rows, int C,
@@ -886,34 +875,34 @@ extern "C" int mmd_silu(int dtype, const void* x, const void* dy, void* out, int
   const int epv = dtype == MMD_BF16 ? 8 : 4;
   MMD_REQUIRE((dtype == MMD_BF16 || dtype == MMD_F32) && x && out && n > 0 && n % epv == 0, "silu: bad argument");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MMD_BF16) hipLaunchKernelGGL(silu_kernel<__bf16>, dim3(ew_grid_b(n / epv)), dim3(256), 0, st, (const char*)x, (const char*)dy, (char*)out, n / epv);
-  else hipLaunchKernelGGL(silu_kernel<float>, dim3(ew_grid_b(n / epv)), dim3(256), 0, st, (const char*)x, (const char*)dy, (char*)out, n / epv);
-  return mmd_check_launch("silu");
+  return mmd_by_dtype(dtype, [&](auto t) {
+    return mmd_launch<silu_kernel<typename decltype(t)::type>>("silu", dim3(ew_grid_b(n / epv)), dim3(256), 0, st, (const char*)x, (const char*)dy, (char*)out,
+                                                               n / epv);
+  });
 }
 
 extern "C" int mmd_dropout(int dtype, const void* x, const uint8_t* mask, float scale, void* out, int64_t n, void* stream) {
   const int epv = dtype == MMD_BF16 ? 8 : 4;
   MMD_REQUIRE((dtype == MMD_BF16 || dtype == MMD_F32) && x && mask && out && n > 0 && n % epv == 0, "dropout: bad argument");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MMD_BF16) hipLaunchKernelGGL(dropout_kernel<__bf16>, dim3(ew_grid_b(n / epv)), dim3(256), 0, st, (const char*)x, mask, scale, (char*)out, n / epv);
-  else hipLaunchKernelGGL(dropout_kernel<float>, dim3(ew_grid_b(n / epv)), dim3(256), 0, st, (const char*)x, mask, scale, (char*)out, n / epv);
-  return mmd_check_launch("dropout");
+  return mmd_by_dtype(dtype, [&](auto t) {
+    return mmd_launch<dropout_kernel<typename decltype(t)::type>>("dropout", dim3(ew_grid_b(n / epv)), dim3(256), 0, st, (const char*)x, mask, scale,
+                                                                  (char*)out, n / epv);
+  });
 }
 
 extern "C" int mmd_mse_grad(const float* out, const float* target, const float* w, float* g, int N, int64_t per_sample, void* stream) {
   MMD_REQUIRE(out && target && w && g && N > 0 && per_sample > 0, "mse_grad: bad argument");
   const int64_t total = per_sample * N;
-  hipLaunchKernelGGL(mse_grad_kernel, dim3(ew_grid_b(total)), dim3(256), 0, (hipStream_t)stream, out, target, w, g, per_sample, total);
-  return mmd_check_launch("mse_grad");
+  return mmd_launch<mse_grad_kernel>("mse_grad", dim3(ew_grid_b(total)), dim3(256), 0, (hipStream_t)stream, out, target, w, g, per_sample, total);
 }
 
 extern "C" int mmd_adamw_step(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr, float beta1, float beta2,
                               float eps, float weight_decay, int step, float ema_rate, void* stream) {
   MMD_REQUIRE(p && g && m && v && n > 0 && step >= 1, "adamw_step: bad argument");
   const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
-  hipLaunchKernelGGL(adamw_kernel, dim3(ew_grid_b(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, n, lr, beta1, beta2, eps, weight_decay,
-                     bc1, bc2, ema_rate);
-  return mmd_check_launch("adamw_step");
+  return mmd_launch<adamw_kernel>("adamw_step", dim3(ew_grid_b(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, n, lr, beta1, beta2, eps, weight_decay,
+                                  bc1, bc2, ema_rate);
 }
 
 // ----------------------------------------------------------------------------- weight packing for the training step
@@ -1023,14 +1012,13 @@ extern "C" int mmd_pack_blocks(int Cout, int Cin, int nt) {
 
 extern "C" int mmd_unpack_conv_grads(const void* descs_dev, int n, int total_blocks, void* stream) {
   MMD_REQUIRE(descs_dev && n > 0 && total_blocks > 0, "unpack_conv_grads: bad argument");      // (descriptors: at most 27 taps, mmd_pack_blocks blocks each)
-  hipLaunchKernelGGL(unpack_grads_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, (const PackDesc*)descs_dev, n);
-  return mmd_check_launch("unpack_conv_grads");
+  return mmd_launch<unpack_grads_kernel>("unpack_conv_grads", dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, (const PackDesc*)descs_dev, n);
 }
 
 extern "C" int mmd_pack_conv_weights(int dtype, const void* descs_dev, int n, int total_blocks, void* stream) {
   MMD_REQUIRE((dtype == MMD_BF16 || dtype == MMD_F32) && descs_dev && n > 0 && total_blocks > 0, "pack_conv_weights: bad argument");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MMD_BF16) hipLaunchKernelGGL(pack_weights_kernel<__bf16>, dim3(total_blocks), dim3(256), 0, st, (const PackDesc*)descs_dev, n);
-  else hipLaunchKernelGGL(pack_weights_kernel<float>, dim3(total_blocks), dim3(256), 0, st, (const PackDesc*)descs_dev, n);
-  return mmd_check_launch("pack_conv_weights");
+  return mmd_by_dtype(dtype, [&](auto t) {
+    return mmd_launch<pack_weights_kernel<typename decltype(t)::type>>("pack_conv_weights", dim3(total_blocks), dim3(256), 0, st, (const PackDesc*)descs_dev, n);
+  });
 }

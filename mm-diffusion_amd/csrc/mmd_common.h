@@ -122,11 +122,45 @@ __device__ __forceinline__ float halfwave_total(float v) {
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-DEVICE property of a kernel: the launchers remember it per device slot
-// (the only process-lifetime state of the library besides the read-only zero pages; a benign race sets it twice).
 #define MMD_MAX_DEVICES 16
 static inline int mmd_device_slot() {
   int d = 0;
   (void)hipGetDevice(&d);
   return d & (MMD_MAX_DEVICES - 1);
 }
+
+// ----------------------------------------------------------------------------- launching
+// Every kernel of the library is launched here.  mmd_launch_cap<K> raises K's dynamic-LDS limit to `cap` bytes (>= lds) when the launch
+// needs more than K has been granted on the current device (everything starts at the 64 KB default), launches, and returns
+// mmd_check_launch(what).  The limit is a per-DEVICE property of a kernel, so the granted size is kept per kernel and device slot: a
+// running maximum, hence a launch sequence that has run once makes no attribute call when it is repeated (under graph capture, say).
+// With the switch values read once and the read-only zero pages this is all the process-lifetime state of the library; a benign race
+// sets a limit twice.
+template <auto K, class... A>
+static int mmd_launch_cap(const char* what, dim3 grid, dim3 block, size_t lds, size_t cap, hipStream_t st, const A&... args) {
+  if (lds > 64 * 1024) {
+    static size_t granted[MMD_MAX_DEVICES] = {};
+    size_t& g = granted[mmd_device_slot()];
+    if (lds > g) {
+      hipError_t e = hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap);
+      if (e != hipSuccess) return mmd_set_error(MMD_ERR_LAUNCH, "%s: set LDS attr: %s", what, hipGetErrorString(e));
+      g = cap;
+    }
+  }
+  hipLaunchKernelGGL(K, grid, block, lds, st, args...);
+  return mmd_check_launch(what);
+}
+template <auto K, class... A>
+static int mmd_launch(const char* what, dim3 grid, dim3 block, size_t lds, hipStream_t st, const A&... args) {
+  return mmd_launch_cap<K>(what, grid, block, lds, lds, st, args...);
+}
+
+// Calls f with a tag of the element type of `dtype`: [&](auto t) { using T = typename decltype(t)::type; ... }
+template <typename T> struct mmd_type { using type = T; };
+template <class F>
+static int mmd_by_dtype(int dtype, F&& f) { return dtype == MMD_BF16 ? f(mmd_type<__bf16>{}) : f(mmd_type<float>{}); }
+
+// ----------------------------------------------------------------------------- environment switches
+int mmd_env_int(const char* name, int dflt);   // the value if it is a positive integer, else dflt
+char mmd_env_char(const char* name);           // first character of the value; 0 if unset or empty
+bool mmd_env_set(const char* name);            // set at all, to anything

@@ -21,6 +21,18 @@ int mmd_check_launch(const char* what) {
   return MMD_OK;
 }
 
+// The library's only reads of the environment.  Each reads on every call: a switch that is read once is a `static const` at its site.
+int mmd_env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  const int v = e ? atoi(e) : 0;
+  return v > 0 ? v : dflt;
+}
+char mmd_env_char(const char* name) {
+  const char* e = getenv(name);
+  return e ? e[0] : 0;
+}
+bool mmd_env_set(const char* name) { return getenv(name) != nullptr; }
+
 extern "C" const char* mmd_last_error(void) { return g_err; }
 extern "C" int mmd_version(void) { return 100; }   // 0.1.0
 

@@ -1907,11 +1907,7 @@ static int launch_conv1x1_strip_res(const ConvGemmParams& p, hipStream_t st) {
   // latency-bound launches then queue behind each other instead of running side by side - same-call A/B, two boxes, two passes each:
   // 11.14 -> 10.80 ms and 11.18 -> 10.94 ms per step; 224: the same, 192: 10.96, 128: 11.40, 288 / 320 (1.5 blocks per CU at ds4): 11.3 / 11.0
   // (profiles/r05_launch_width_ab.txt)
-  static const int want_blocks = [] {                     // tuning switch (read once): MMD_STRIP_BLOCKS, default 256
-    const char* e = getenv("MMD_STRIP_BLOCKS");
-    const int v = e ? atoi(e) : 0;
-    return v > 0 ? v : 256;
-  }();
+  static const int want_blocks = mmd_env_int("MMD_STRIP_BLOCKS", 256);   // tuning switch (read once)
   int nsplit = 1;
   for (int d = 1; d <= nch && d <= 16; ++d)
     if (nch % d == 0) {
@@ -1923,17 +1919,8 @@ static int launch_conv1x1_strip_res(const ConvGemmParams& p, hipStream_t st) {
   const size_t lds = 2 * (size_t)STAGE_B + (size_t)((Cs + 3) & ~3) * 4 + (p.gn_a ? 4 * (size_t)(64 * KS) * 4 : 0) + REC_B;
   const size_t lds_max = 2 * (size_t)STAGE_B + 2048 * 4 + 4 * (size_t)(64 * KS) * 4 + REC_B;
   if (lds > lds_max) return mmd_set_error(MMD_ERR_UNSUPPORTED, "conv_gemm tile 131 (strip): %d output channels per block", Cs);
-  static bool attr_done[MMD_MAX_DEVICES] = {};
-  bool& attr_set = attr_done[mmd_device_slot()];
-  if (!attr_set) {
-    const void* kfn = HR ? (const void*)conv1x1_strip_res_kernel<KS, RF, CC, GNM, STM> : (const void*)conv1x1_strip_kernel<KS, RF, CC, GNM, STM>;
-    hipError_t e = hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
-    if (e != hipSuccess) return mmd_set_error(MMD_ERR_LAUNCH, "conv1x1_strip: set LDS attr: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
-  if (HR) hipLaunchKernelGGL((conv1x1_strip_res_kernel<KS, RF, CC, GNM, STM>), dim3(rowblocks * nsplit), dim3(256), lds, st, p, nsplit);
-  else hipLaunchKernelGGL((conv1x1_strip_kernel<KS, RF, CC, GNM, STM>), dim3(rowblocks * nsplit), dim3(256), lds, st, p, nsplit);
-  return mmd_check_launch("conv1x1_strip");
+  constexpr auto kfn = HR ? conv1x1_strip_res_kernel<KS, RF, CC, GNM, STM> : conv1x1_strip_kernel<KS, RF, CC, GNM, STM>;
+  return mmd_launch_cap<kfn>("conv1x1_strip", dim3(rowblocks * nsplit), dim3(256), lds, lds_max, st, p, nsplit);
 }
 
 template <int KS, int RF, int CC, int GNM, int STM>
@@ -1968,7 +1955,7 @@ static int dispatch_conv1x1_strip(const ConvGemmParams& p, hipStream_t st) {
     // SAMPLE (the record fold of a one-fragment wave differs in the last bit: the choice must not move with the batch size).
     // Same-call A/B (profiles/r06_lanes_width_aconv_call11.txt): the graded ResBlock 0.2042 -> 0.1990 ms, the step unchanged (10.85 / 10.84 ms).
     // MMD_STRIP_K128_RF1=0: the two-fragment instance (A/B).
-    static const bool rf1 = [] { const char* e = getenv("MMD_STRIP_K128_RF1"); return !(e && e[0] == '0'); }();
+    static const bool rf1 = mmd_env_char("MMD_STRIP_K128_RF1") != '0';
     if (rf1 && p.gn_a && p.gn_rows >= 16384 && p.ntaps == 1 && p.Cout % 32 == 0) return launch_conv1x1_strip<2, 1, 32>(p, st);
     return launch_conv1x1_strip<2, 2, 64>(p, st);
   }
@@ -1988,16 +1975,8 @@ static int launch_conv_gemm_halo(const ConvGemmParams& p, hipStream_t st) {
   if (GN && (p.ntaps != 9 || p.gn_rows % ((int64_t)p.D1 * p.D2) != 0))
     return mmd_set_error(MMD_ERR_UNSUPPORTED, "conv_gemm tile 130 with fused GroupNorm: needs the nine spatial taps and slices of whole frames");
   const size_t lds = 2 * (size_t)(23 * 8 * 128) + 2 * (size_t)(128 * 128) + 336 + (GN ? 1024 : 0);     // (two blocks per CU: <= 81920 B)
-  static bool attr_done[MMD_MAX_DEVICES] = {};
-  bool& attr_set = attr_done[mmd_device_slot()];
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv_gemm_halo_kernel<T, GN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return mmd_set_error(MMD_ERR_LAUNCH, "conv_gemm_halo: set LDS attr: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
   const int grid = (p.M / 128) * cdiv(p.Cout, 128);
-  hipLaunchKernelGGL((conv_gemm_halo_kernel<T, GN>), dim3(grid), dim3(256), lds, st, p);
-  return mmd_check_launch("conv_gemm_halo");
+  return mmd_launch<conv_gemm_halo_kernel<T, GN>>("conv_gemm_halo", dim3(grid), dim3(256), lds, st, p);
 }
 
 // tile 133: halo-tile main loop on 16 x 16 patches, 8 waves, three-slot weight ring (bf16, nine spatial taps)
@@ -2014,23 +1993,15 @@ static int launch_conv_gemm_halo16(const ConvGemmParams& p, hipStream_t st) {
     return mmd_set_error(MMD_ERR_UNSUPPORTED, "conv_gemm tile 133 with fused GroupNorm: needs slices of whole frames");
   constexpr size_t OPS_B = 2 * (size_t)(41 * 8 * 128) + 3 * (size_t)(128 * 128), C_B = 256 * 132 * sizeof(float);
   const size_t lds = (OPS_B > C_B ? OPS_B : C_B) + 1024 + 256;
-  static bool attr_done[MMD_MAX_DEVICES] = {};
-  bool& attr_set = attr_done[mmd_device_slot()];
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv_gemm_halo16_kernel<GN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return mmd_set_error(MMD_ERR_LAUNCH, "conv_gemm_halo16: set LDS attr: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
   const int grid = (p.M / 256) * cdiv(p.Cout, 128);
-  hipLaunchKernelGGL((conv_gemm_halo16_kernel<GN>), dim3(grid), dim3(512), lds, st, p);
-  return mmd_check_launch("conv_gemm_halo16");
+  return mmd_launch<conv_gemm_halo16_kernel<GN>>("conv_gemm_halo16", dim3(grid), dim3(512), lds, st, p);
 }
 
 // descriptor addressing of the direct-to-LDS loops: 32-bit byte offsets into the activation view and the block's 128 weight rows;
 // MMD_GEMM_DESC=0 keeps the 64-bit pointer path (A/B)
 template <typename T>
 static bool glds_desc_ok(const ConvGemmParams& p) {
-  static const bool on = [] { const char* e = getenv("MMD_GEMM_DESC"); return !(e && e[0] == '0'); }();
+  static const bool on = mmd_env_char("MMD_GEMM_DESC") != '0';
   constexpr int ES = 16 / Elt<T>::EPV;
   int maxshift = 0;
   for (int t = 0; t < p.ntaps; ++t) {
@@ -2044,20 +2015,10 @@ static bool glds_desc_ok(const ConvGemmParams& p) {
 template <typename T>
 static int launch_conv_gemm_glds(const ConvGemmParams& p, hipStream_t st) {
   const size_t lds = 128 * 132 * sizeof(float) + 336;
-  static bool attr_done[MMD_MAX_DEVICES] = {};
-  bool& attr_set = attr_done[mmd_device_slot()];
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv_gemm_glds_kernel<T, false, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv_gemm_glds_kernel<T, true, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv_gemm_glds_kernel<T, true, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return mmd_set_error(MMD_ERR_LAUNCH, "conv_gemm_glds: set LDS attr: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
-  const int grid = cdiv(p.M, 128) * cdiv(p.Cout, 128);
-  if (p.Cin % (8 * Elt<T>::EPV) != 0) hipLaunchKernelGGL((conv_gemm_glds_kernel<T, false, 2, false>), dim3(grid), dim3(256), lds, st, p);
-  else if (glds_desc_ok<T>(p)) hipLaunchKernelGGL((conv_gemm_glds_kernel<T, true, 2, true>), dim3(grid), dim3(256), lds, st, p);
-  else hipLaunchKernelGGL((conv_gemm_glds_kernel<T, true, 2, false>), dim3(grid), dim3(256), lds, st, p);
-  return mmd_check_launch("conv_gemm_glds");
+  const dim3 grid(cdiv(p.M, 128) * cdiv(p.Cout, 128));
+  if (p.Cin % (8 * Elt<T>::EPV) != 0) return mmd_launch<conv_gemm_glds_kernel<T, false, 2, false>>("conv_gemm_glds", grid, dim3(256), lds, st, p);
+  if (!glds_desc_ok<T>(p)) return mmd_launch<conv_gemm_glds_kernel<T, true, 2, false>>("conv_gemm_glds", grid, dim3(256), lds, st, p);
+  return mmd_launch<conv_gemm_glds_kernel<T, true, 2, true>>("conv_gemm_glds", grid, dim3(256), lds, st, p);
 }
 
 // tile 132: the direct-to-LDS loop with a four-slot ring (three K steps of DMA in flight), one block per CU
@@ -2066,18 +2027,9 @@ static int launch_conv_gemm_ring(const ConvGemmParams& p, hipStream_t st) {
   if (p.Cin % (8 * Elt<T>::EPV) != 0)
     return mmd_set_error(MMD_ERR_UNSUPPORTED, "conv_gemm tile 132 (deep ring): Cin must be a multiple of one 128-byte K step");
   const size_t lds = 8 * (size_t)(128 * 128) + 336;
-  static bool attr_done[MMD_MAX_DEVICES] = {};
-  bool& attr_set = attr_done[mmd_device_slot()];
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv_gemm_glds_kernel<T, true, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv_gemm_glds_kernel<T, true, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return mmd_set_error(MMD_ERR_LAUNCH, "conv_gemm_ring: set LDS attr: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
-  const int grid = cdiv(p.M, 128) * cdiv(p.Cout, 128);
-  if (glds_desc_ok<T>(p)) hipLaunchKernelGGL((conv_gemm_glds_kernel<T, true, 4, true>), dim3(grid), dim3(256), lds, st, p);
-  else hipLaunchKernelGGL((conv_gemm_glds_kernel<T, true, 4, false>), dim3(grid), dim3(256), lds, st, p);
-  return mmd_check_launch("conv_gemm_ring");
+  const dim3 grid(cdiv(p.M, 128) * cdiv(p.Cout, 128));
+  if (!glds_desc_ok<T>(p)) return mmd_launch<conv_gemm_glds_kernel<T, true, 4, false>>("conv_gemm_ring", grid, dim3(256), lds, st, p);
+  return mmd_launch<conv_gemm_glds_kernel<T, true, 4, true>>("conv_gemm_ring", grid, dim3(256), lds, st, p);
 }
 
 template <typename T, int BM, int BN, bool GN>
@@ -2085,17 +2037,8 @@ static int launch_conv_gemm(const ConvGemmParams& p, hipStream_t st) {
   const size_t lds_ops = 2 * (size_t)(BM + BN) * ROWB;
   const size_t lds_c = (size_t)BM * (BN + 4) * sizeof(float);
   const size_t lds = (lds_ops > lds_c ? lds_ops : lds_c) + 336 + (GN ? 16 * 256 : 0);   // + tap table (+ GN affine cache, Cin <= 256)
-  static bool attr_done[MMD_MAX_DEVICES] = {};
-  bool& attr_set = attr_done[mmd_device_slot()];
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv_gemm_kernel<T, BM, BN, GN>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return mmd_set_error(MMD_ERR_LAUNCH, "conv_gemm: set LDS attr: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
   const int grid = cdiv(p.M, BM) * cdiv(p.Cout, BN);
-  hipLaunchKernelGGL((conv_gemm_kernel<T, BM, BN, GN>), dim3(grid), dim3(256), lds, st, p);
-  return mmd_check_launch("conv_gemm");
+  return mmd_launch<conv_gemm_kernel<T, BM, BN, GN>>("conv_gemm", dim3(grid), dim3(256), lds, st, p);
 }
 
 template <typename T>

@@ -518,15 +518,12 @@ extern "C" int mmd_temb_fwd(const void* t, int t_kind, int N, int dim, const flo
                             const float* b2, float* out_silu, float* out_raw, void* stream) {
   MMD_REQUIRE(t && W0 && b0 && W2 && b2 && out_silu && N > 0 && dim > 0 && dim <= 4096, "temb_fwd: bad argument");
   MMD_REQUIRE(t_kind >= 0 && t_kind <= 2, "temb_fwd: t_kind must be 0 (int64), 1 (int32) or 2 (float32)");
-  hipLaunchKernelGGL(temb_kernel, dim3(N), dim3(256), 2 * dim * sizeof(float), (hipStream_t)stream, t, t_kind, dim, W0, b0, W2,
-                     b2, out_silu, out_raw);
-  return mmd_check_launch("temb");
+  return mmd_launch<temb_kernel>("temb", dim3(N), dim3(256), 2 * dim * sizeof(float), (hipStream_t)stream, t, t_kind, dim, W0, b0, W2, b2, out_silu, out_raw);
 }
 
 extern "C" int mmd_linear_fwd(const float* x, const float* W, const float* b, float* y, int N, int K, int J, void* stream) {
   MMD_REQUIRE(x && W && y && N > 0 && K > 0 && J > 0, "linear_fwd: bad argument");
-  hipLaunchKernelGGL(linear_kernel, dim3(cdiv(J, 4)), dim3(256), 0, (hipStream_t)stream, x, W, b, y, N, K, J);
-  return mmd_check_launch("linear");
+  return mmd_launch<linear_kernel>("linear", dim3(cdiv(J, 4)), dim3(256), 0, (hipStream_t)stream, x, W, b, y, N, K, J);
 }
 
 extern "C" int mmd_resample(int dtype, const void* x, int64_t ldx, void* y, int64_t ldy, int C, int NF, int H, int W, int fh,
@@ -538,11 +535,10 @@ extern "C" int mmd_resample(int dtype, const void* x, int64_t ldx, void* y, int6
   const int64_t orows = mode == 0 ? (int64_t)NF * (H / fh) * (W / fw) : (int64_t)NF * H * fh * W * fw;
   const int grid = ew_grid(orows * (C / epv));
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MMD_BF16)
-    hipLaunchKernelGGL(resample_kernel<__bf16>, dim3(grid), dim3(256), 0, st, (const char*)x, ldx, (char*)y, ldy, C, NF, H, W, fh, fw, mode, scale);
-  else
-    hipLaunchKernelGGL(resample_kernel<float>, dim3(grid), dim3(256), 0, st, (const char*)x, ldx, (char*)y, ldy, C, NF, H, W, fh, fw, mode, scale);
-  return mmd_check_launch("resample");
+  return mmd_by_dtype(dtype, [&](auto t) {
+    return mmd_launch<resample_kernel<typename decltype(t)::type>>("resample", dim3(grid), dim3(256), 0, st, (const char*)x, ldx, (char*)y, ldy, C, NF, H, W,
+                                                                   fh, fw, mode, scale);
+  });
 }
 
 extern "C" int mmd_resample_stats(const void* x, int64_t ldx, void* y, int64_t ldy, int C, int NF, int H, int W, int fh, int fw, int mode,
@@ -558,9 +554,8 @@ extern "C" int mmd_resample_stats(const void* x, int64_t ldx, void* y, int64_t l
   int lcvp = 0;
   while ((1 << lcvp) < C / 8) ++lcvp;
   const int nrec = (int)(orows / 64);
-  hipLaunchKernelGGL(resample_stats_kernel, dim3(min(nrec, 8192)), dim3(256), 0, (hipStream_t)stream, (const char*)x, ldx, (char*)y, ldy, C, NF, H,
-                     W, fh, fw, mode, stats, stats_ld, nrec, lcvp);
-  return mmd_check_launch("resample_stats");
+  return mmd_launch<resample_stats_kernel>("resample_stats", dim3(min(nrec, 8192)), dim3(256), 0, (hipStream_t)stream, (const char*)x, ldx, (char*)y, ldy, C,
+                                           NF, H, W, fh, fw, mode, stats, stats_ld, nrec, lcvp);
 }
 
 extern "C" int mmd_copy2d(const void* x, int64_t ldx_bytes, void* y, int64_t ldy_bytes, int64_t rows, int64_t row_bytes, void* stream) {
@@ -568,9 +563,8 @@ extern "C" int mmd_copy2d(const void* x, int64_t ldx_bytes, void* y, int64_t ldy
               "copy2d: rows must be 16-byte multiples");
   MMD_REQUIRE(((uintptr_t)x | (uintptr_t)y) % 16 == 0, "copy2d: unaligned pointer");
   const int vecs = (int)(row_bytes / 16);
-  hipLaunchKernelGGL(copy2d_kernel, dim3(ew_grid(rows * vecs)), dim3(256), 0, (hipStream_t)stream, (const char*)x, ldx_bytes,
-                     (char*)y, ldy_bytes, rows, vecs);
-  return mmd_check_launch("copy2d");
+  return mmd_launch<copy2d_kernel>("copy2d", dim3(ew_grid(rows * vecs)), dim3(256), 0, (hipStream_t)stream, (const char*)x, ldx_bytes, (char*)y, ldy_bytes,
+                                   rows, vecs);
 }
 
 
@@ -660,7 +654,7 @@ __global__ __launch_bounds__(256, 2) void stem_conv_mfma_kernel(const EdgeConvPa
 }
 
 static bool stem_mfma_ok(int dtype, const EdgeConvParams& p) {
-  static const bool on = [] { const char* e = getenv("MMD_STEM_MFMA"); return !(e && e[0] == '0'); }();
+  static const bool on = mmd_env_char("MMD_STEM_MFMA") != '0';
   for (int i = 0; i < p.ntaps * 3; ++i)
     if (p.taps[i] < -1 || p.taps[i] > 1) return false;          // the kernel packs a tap offset + 1 into two bits
   return on && dtype == MMD_BF16 && p.W % 32 == 0 && p.ntaps * p.Cin <= 28 && p.Cin <= 3 && p.Cout % 32 == 0 && p.Cout <= 128 && p.ldy % 8 == 0 &&
@@ -671,12 +665,11 @@ static int launch_stem_mfma(const EdgeConvParams& p, hipStream_t st) {
   const int64_t groups = (int64_t)p.N * p.F * p.H * (p.W / 32);
   const int grid = (int)min((int64_t)2048, (groups + 3) / 4);
   switch (p.Cout / 32) {
-    case 1: hipLaunchKernelGGL(stem_conv_mfma_kernel<1>, dim3(grid), dim3(256), 0, st, p); break;
-    case 2: hipLaunchKernelGGL(stem_conv_mfma_kernel<2>, dim3(grid), dim3(256), 0, st, p); break;
-    case 3: hipLaunchKernelGGL(stem_conv_mfma_kernel<3>, dim3(grid), dim3(256), 0, st, p); break;
-    default: hipLaunchKernelGGL(stem_conv_mfma_kernel<4>, dim3(grid), dim3(256), 0, st, p); break;
+    case 1: return mmd_launch<stem_conv_mfma_kernel<1>>("stem_conv_mfma", dim3(grid), dim3(256), 0, st, p);
+    case 2: return mmd_launch<stem_conv_mfma_kernel<2>>("stem_conv_mfma", dim3(grid), dim3(256), 0, st, p);
+    case 3: return mmd_launch<stem_conv_mfma_kernel<3>>("stem_conv_mfma", dim3(grid), dim3(256), 0, st, p);
+    default: return mmd_launch<stem_conv_mfma_kernel<4>>("stem_conv_mfma", dim3(grid), dim3(256), 0, st, p);
   }
-  return mmd_check_launch("stem_conv_mfma");
 }
 
 extern "C" int mmd_stem_conv(int dtype, const float* x, const float* w, const float* bias, void* y, int64_t ldy, int N, int F,
@@ -695,15 +688,15 @@ extern "C" int mmd_stem_conv(int dtype, const float* x, const float* w, const fl
   if (stem_mfma_ok(dtype, p)) return launch_stem_mfma(p, st);
   if (W % 4 == 0 && (Cin == 1 || Cin == 3) && Cout % 4 == 0) {
     const dim3 grid(ew_grid(total / 4));
-    if (dtype == MMD_BF16 && Cin == 3) hipLaunchKernelGGL((stem_conv_strip_kernel<__bf16, 3>), grid, dim3(256), lds, st, p);
-    else if (dtype == MMD_BF16) hipLaunchKernelGGL((stem_conv_strip_kernel<__bf16, 1>), grid, dim3(256), lds, st, p);
-    else if (Cin == 3) hipLaunchKernelGGL((stem_conv_strip_kernel<float, 3>), grid, dim3(256), lds, st, p);
-    else hipLaunchKernelGGL((stem_conv_strip_kernel<float, 1>), grid, dim3(256), lds, st, p);
-    return mmd_check_launch("stem_conv_strip");
+    return mmd_by_dtype(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      if (Cin == 3) return mmd_launch<stem_conv_strip_kernel<T, 3>>("stem_conv_strip", grid, dim3(256), lds, st, p);
+      return mmd_launch<stem_conv_strip_kernel<T, 1>>("stem_conv_strip", grid, dim3(256), lds, st, p);
+    });
   }
-  if (dtype == MMD_BF16) hipLaunchKernelGGL(stem_conv_kernel<__bf16>, dim3(ew_grid(total)), dim3(256), lds, st, p);
-  else hipLaunchKernelGGL(stem_conv_kernel<float>, dim3(ew_grid(total)), dim3(256), lds, st, p);
-  return mmd_check_launch("stem_conv");
+  return mmd_by_dtype(dtype, [&](auto t) {
+    return mmd_launch<stem_conv_kernel<typename decltype(t)::type>>("stem_conv", dim3(ew_grid(total)), dim3(256), lds, st, p);
+  });
 }
 
 // Cooperative head conv: LPR = Cin/EPV lanes share one output row (each lane owns one 16-byte channel chunk, so every
@@ -884,23 +877,12 @@ static int launch_head_strip(const HeadConvParams& p, int lpr, hipStream_t st) {
   const int64_t strips = (int64_t)p.N * p.F * p.H * (p.W / 4);
   const int spb = 4 * (64 / lpr);                       // strips per block pass
   const int grid = (int)min((int64_t)2048, (strips + spb - 1) / spb);
-#define MMD_HEADS_LAUNCH(L)                                                                                         \
-  do {                                                                                                              \
-    if (lds > 64 * 1024) {                                                                                          \
-      hipError_t e = hipFuncSetAttribute((const void*)head_conv_strip_kernel<T, CO, L>,                             \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                     \
-      if (e != hipSuccess) return mmd_set_error(MMD_ERR_LAUNCH, "head_conv: set LDS attr: %s", hipGetErrorString(e)); \
-    }                                                                                                               \
-    hipLaunchKernelGGL((head_conv_strip_kernel<T, CO, L>), dim3(grid), dim3(256), lds, st, p);                      \
-  } while (0)
   switch (lpr) {
-    case 4: MMD_HEADS_LAUNCH(4); break;
-    case 8: MMD_HEADS_LAUNCH(8); break;
-    case 16: MMD_HEADS_LAUNCH(16); break;
-    default: MMD_HEADS_LAUNCH(32); break;
+    case 4: return mmd_launch<head_conv_strip_kernel<T, CO, 4>>("head_conv_strip", dim3(grid), dim3(256), lds, st, p);
+    case 8: return mmd_launch<head_conv_strip_kernel<T, CO, 8>>("head_conv_strip", dim3(grid), dim3(256), lds, st, p);
+    case 16: return mmd_launch<head_conv_strip_kernel<T, CO, 16>>("head_conv_strip", dim3(grid), dim3(256), lds, st, p);
+    default: return mmd_launch<head_conv_strip_kernel<T, CO, 32>>("head_conv_strip", dim3(grid), dim3(256), lds, st, p);
   }
-#undef MMD_HEADS_LAUNCH
-  return mmd_check_launch("head_conv_strip");
 }
 
 template <typename T, int CO>
@@ -909,25 +891,14 @@ static int launch_head_coop(const HeadConvParams& p, int lpr, hipStream_t st) {
   const size_t lds = (size_t)p.ntaps * (EPV * CO / 4) * lpr * 4 * sizeof(float);
   const int64_t rows = (int64_t)p.N * p.F * p.H * p.W;
   const int grid = (int)min((int64_t)2048, (rows + 63) / 64);
-#define MMD_HEAD_LAUNCH(L)                                                                                         \
-  do {                                                                                                             \
-    if (lds > 64 * 1024) {                                                                                         \
-      hipError_t e = hipFuncSetAttribute((const void*)head_conv_coop_kernel<T, CO, L>,                             \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                    \
-      if (e != hipSuccess) return mmd_set_error(MMD_ERR_LAUNCH, "head_conv: set LDS attr: %s", hipGetErrorString(e)); \
-    }                                                                                                              \
-    hipLaunchKernelGGL((head_conv_coop_kernel<T, CO, L>), dim3(grid), dim3(256), lds, st, p);                      \
-  } while (0)
   switch (lpr) {
-    case 4: MMD_HEAD_LAUNCH(4); break;
-    case 8: MMD_HEAD_LAUNCH(8); break;
-    case 16: MMD_HEAD_LAUNCH(16); break;
-    case 32: MMD_HEAD_LAUNCH(32); break;
-    case 64: MMD_HEAD_LAUNCH(64); break;
+    case 4: return mmd_launch<head_conv_coop_kernel<T, CO, 4>>("head_conv_coop", dim3(grid), dim3(256), lds, st, p);
+    case 8: return mmd_launch<head_conv_coop_kernel<T, CO, 8>>("head_conv_coop", dim3(grid), dim3(256), lds, st, p);
+    case 16: return mmd_launch<head_conv_coop_kernel<T, CO, 16>>("head_conv_coop", dim3(grid), dim3(256), lds, st, p);
+    case 32: return mmd_launch<head_conv_coop_kernel<T, CO, 32>>("head_conv_coop", dim3(grid), dim3(256), lds, st, p);
+    case 64: return mmd_launch<head_conv_coop_kernel<T, CO, 64>>("head_conv_coop", dim3(grid), dim3(256), lds, st, p);
     default: return mmd_set_error(MMD_ERR_UNSUPPORTED, "head_conv: lanes per row %d", lpr);
   }
-#undef MMD_HEAD_LAUNCH
-  return mmd_check_launch("head_conv_coop");
 }
 
 
@@ -966,15 +937,9 @@ static int launch_head(const HeadConvParams& p, hipStream_t st) {
   }
   const size_t lds = (size_t)p.ntaps * p.Cin * CO * sizeof(float);
   if (lds > 150 * 1024) return mmd_set_error(MMD_ERR_UNSUPPORTED, "head_conv: weights (%zu B) exceed LDS", lds);
-  const void* fn = CO == 2 ? (const void*)head_conv_kernel<T, 2> : CO == 4 ? (const void*)head_conv_kernel<T, 4> : (const void*)head_conv_kernel<T, 8>;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return mmd_set_error(MMD_ERR_LAUNCH, "head_conv: set LDS attr: %s", hipGetErrorString(e));
-  }
-  if (CO == 2) hipLaunchKernelGGL((head_conv_kernel<T, 2>), dim3(grid), dim3(256), lds, st, p);
-  else if (CO == 4) hipLaunchKernelGGL((head_conv_kernel<T, 4>), dim3(grid), dim3(256), lds, st, p);
-  else hipLaunchKernelGGL((head_conv_kernel<T, 8>), dim3(grid), dim3(256), lds, st, p);
-  return mmd_check_launch("head_conv");
+  if (CO == 2) return mmd_launch<head_conv_kernel<T, 2>>("head_conv", dim3(grid), dim3(256), lds, st, p);
+  if (CO == 4) return mmd_launch<head_conv_kernel<T, 4>>("head_conv", dim3(grid), dim3(256), lds, st, p);
+  return mmd_launch<head_conv_kernel<T, 8>>("head_conv", dim3(grid), dim3(256), lds, st, p);
 }
 
 // ----------------------------------------------------------------------------- head conv as GEMM + gather (round 5, bf16)
@@ -1126,15 +1091,7 @@ extern "C" int mmd_head_gemm(const void* x, int64_t ldx, int64_t M, int Cin, con
   p.per_block = (int)max((int64_t)1, (ngroups + 1023) / 1024);          // <= 1024 blocks: two per CU, each a run of consecutive row groups
   const int grid = (int)((ngroups + p.per_block - 1) / p.per_block);
   const size_t lds = 2 * 3 * 8 * 1024 + 2 * 128 * sizeof(float);
-  static bool attr_done[MMD_MAX_DEVICES] = {};
-  bool& attr_set = attr_done[mmd_device_slot()];
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)head_gemm_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return mmd_set_error(MMD_ERR_LAUNCH, "head_gemm: set LDS attr: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(head_gemm_kernel<8>, dim3(grid), dim3(256), lds, (hipStream_t)stream, p);
-  return mmd_check_launch("head_gemm");
+  return mmd_launch<head_gemm_kernel<8>>("head_gemm", dim3(grid), dim3(256), lds, (hipStream_t)stream, p);
 }
 
 // y[n, f, co, h, w] = bias[co] + sum_tap P[tap Co + co][m + offset(tap)] (zero outside (F, H, W)); y fp32 API layout [N, F, Co, H, W].
@@ -1148,13 +1105,12 @@ extern "C" int mmd_head_gather(const float* P, const float* bias, float* y, int 
   const int grid = (int)((p.M + 255) / 256);
   hipStream_t st = (hipStream_t)stream;
   switch (Co) {
-    case 1: hipLaunchKernelGGL(head_gather_kernel<1>, dim3(grid), dim3(256), 0, st, p); break;
-    case 2: hipLaunchKernelGGL(head_gather_kernel<2>, dim3(grid), dim3(256), 0, st, p); break;
-    case 3: hipLaunchKernelGGL(head_gather_kernel<3>, dim3(grid), dim3(256), 0, st, p); break;
-    case 4: hipLaunchKernelGGL(head_gather_kernel<4>, dim3(grid), dim3(256), 0, st, p); break;
-    default: hipLaunchKernelGGL(head_gather_kernel<6>, dim3(grid), dim3(256), 0, st, p); break;
+    case 1: return mmd_launch<head_gather_kernel<1>>("head_gather", dim3(grid), dim3(256), 0, st, p);
+    case 2: return mmd_launch<head_gather_kernel<2>>("head_gather", dim3(grid), dim3(256), 0, st, p);
+    case 3: return mmd_launch<head_gather_kernel<3>>("head_gather", dim3(grid), dim3(256), 0, st, p);
+    case 4: return mmd_launch<head_gather_kernel<4>>("head_gather", dim3(grid), dim3(256), 0, st, p);
+    default: return mmd_launch<head_gather_kernel<6>>("head_gather", dim3(grid), dim3(256), 0, st, p);
   }
-  return mmd_check_launch("head_gather");
 }
 
 extern "C" int mmd_head_conv(int dtype, const void* x, int64_t ldx, const float* w, const float* bias, float* y, int N, int F,
@@ -1179,16 +1135,14 @@ extern "C" int mmd_ddpm_update(const float* x, const float* model_out, const flo
   p.x = x; p.mo = model_out; p.noise = noise; p.out = out; p.x0_out = x0_out; p.mean_out = mean_out; p.logvar_out = logvar_out;
   p.tables = tables; p.t = t;
   p.T = T; p.N = N; p.F = F; p.C = C; p.HW = HW; p.flags = flags;
-  hipLaunchKernelGGL(ddpm_update_kernel, dim3(ew_grid((int64_t)N * F * C * HW)), dim3(256), 0, (hipStream_t)stream, p);
-  return mmd_check_launch("ddpm_update");
+  return mmd_launch<ddpm_update_kernel>("ddpm_update", dim3(ew_grid((int64_t)N * F * C * HW)), dim3(256), 0, (hipStream_t)stream, p);
 }
 
 extern "C" int mmd_q_sample(const float* x0, const float* eps, float* out, const float* tab2, const int64_t* t, int T, int N,
                             int64_t per_sample, void* stream) {
   MMD_REQUIRE(x0 && eps && out && tab2 && t && T > 0 && N > 0 && per_sample > 0, "q_sample: bad argument");
   const int64_t total = per_sample * N;
-  hipLaunchKernelGGL(q_sample_kernel, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, x0, eps, out, tab2, t, T, per_sample, total);
-  return mmd_check_launch("q_sample");
+  return mmd_launch<q_sample_kernel>("q_sample", dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, x0, eps, out, tab2, t, T, per_sample, total);
 }
 
 #define MMD_LOSS_CHUNKS 64
@@ -1205,12 +1159,10 @@ extern "C" int mmd_loss_terms(const float* x0, const float* xt, const float* mod
   p.x0 = x0; p.xt = xt; p.mo = model_out; p.target = target; p.tables = tables; p.t = t; p.partial = (double*)workspace;
   p.T = T; p.N = N; p.F = F; p.C = C; p.HW = HW; p.flags = flags; p.nchunk = MMD_LOSS_CHUNKS;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(loss_terms_kernel, dim3(MMD_LOSS_CHUNKS, N), dim3(256), 0, st, p);
-  int rc = mmd_check_launch("loss_terms");
+  int rc = mmd_launch<loss_terms_kernel>("loss_terms", dim3(MMD_LOSS_CHUNKS, N), dim3(256), 0, st, p);
   if (rc) return rc;
-  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(N), 0, st, (const double*)workspace, MMD_LOSS_CHUNKS,
-                     1.0 / ((double)F * C * HW), vb_scale, mse_out, (flags & 4) ? vb_out : nullptr);
-  return mmd_check_launch("loss_finalize");
+  return mmd_launch<loss_finalize_kernel>("loss_finalize", dim3(1), dim3(N), 0, st, (const double*)workspace, MMD_LOSS_CHUNKS, 1.0 / ((double)F * C * HW),
+                                          vb_scale, mse_out, (flags & 4) ? vb_out : nullptr);
 }
 
 // ----------------------------------------------------------------------------- variational bound, evaluation form (bits / dim)
@@ -1313,12 +1265,10 @@ extern "C" int mmd_vlb_terms(const float* x0, const float* xt, const float* nois
   p.partial = (double*)workspace;
   p.T = T; p.N = N; p.F = F; p.C = C; p.HW = HW; p.flags = flags; p.nchunk = MMD_LOSS_CHUNKS;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(vlb_terms_kernel, dim3(MMD_LOSS_CHUNKS, N), dim3(256), 0, st, p);
-  int rc = mmd_check_launch("vlb_terms");
+  int rc = mmd_launch<vlb_terms_kernel>("vlb_terms", dim3(MMD_LOSS_CHUNKS, N), dim3(256), 0, st, p);
   if (rc) return rc;
-  hipLaunchKernelGGL(vlb_finalize_kernel, dim3(cdiv(N, 64)), dim3(64), 0, st, (const double*)workspace, MMD_LOSS_CHUNKS, N,
-                     1.0 / ((double)F * C * HW), t, out_ld, vb_out, xstart_mse_out, eps_mse_out);
-  return mmd_check_launch("vlb_finalize");
+  return mmd_launch<vlb_finalize_kernel>("vlb_finalize", dim3(cdiv(N, 64)), dim3(64), 0, st, (const double*)workspace, MMD_LOSS_CHUNKS, N,
+                                         1.0 / ((double)F * C * HW), t, out_ld, vb_out, xstart_mse_out, eps_mse_out);
 }
 
 // sinusoidal timestep embedding alone (nn.py:192-210): out[N, dim] fp32 (training path keeps the MLP as separate linears)
@@ -1341,8 +1291,7 @@ __global__ void timestep_embedding_kernel(const void* __restrict__ t, int t_kind
 }
 extern "C" int mmd_timestep_embedding(const void* t, int t_kind, int N, int dim, float* out, void* stream) {
   MMD_REQUIRE(t && out && N > 0 && dim > 0 && t_kind >= 0 && t_kind <= 2, "timestep_embedding: bad argument");
-  hipLaunchKernelGGL(timestep_embedding_kernel, dim3(N), dim3(128), 0, (hipStream_t)stream, t, t_kind, dim, out);
-  return mmd_check_launch("timestep_embedding");
+  return mmd_launch<timestep_embedding_kernel>("timestep_embedding", dim3(N), dim3(128), 0, (hipStream_t)stream, t, t_kind, dim, out);
 }
 
 // ----------------------------------------------------------------------------- DDIM step / helper combinations
@@ -1396,8 +1345,7 @@ extern "C" int mmd_ddim_update(const float* x, const float* model_out, const flo
   DdimParams p;
   p.x = x; p.mo = model_out; p.noise = noise; p.out = out; p.x0_out = x0_out; p.tables = tables; p.tab3 = tab3; p.t = t;
   p.T = T; p.N = N; p.F = F; p.C = C; p.HW = HW; p.flags = flags; p.eta = eta;
-  hipLaunchKernelGGL(ddim_update_kernel, dim3(ew_grid((int64_t)N * F * C * HW)), dim3(256), 0, (hipStream_t)stream, p);
-  return mmd_check_launch("ddim_update");
+  return mmd_launch<ddim_update_kernel>("ddim_update", dim3(ew_grid((int64_t)N * F * C * HW)), dim3(256), 0, (hipStream_t)stream, p);
 }
 
 // out[n, i] = (ca[t_n] a + cb[t_n] b) * cs[t_n]    per-sample coefficients looked up from fp32 tables of length T
@@ -1417,8 +1365,7 @@ extern "C" int mmd_lincomb_t(const float* a, const float* b, float* out, const f
                              const int64_t* t, int N, int64_t per_sample, void* stream) {
   MMD_REQUIRE(a && out && t && N > 0 && per_sample > 0, "lincomb_t: bad argument");
   const int64_t total = per_sample * N;
-  hipLaunchKernelGGL(lincomb_t_kernel, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, a, b, out, ca, cb, cs, t, per_sample, total);
-  return mmd_check_launch("lincomb_t");
+  return mmd_launch<lincomb_t_kernel>("lincomb_t", dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, a, b, out, ca, cb, cs, t, per_sample, total);
 }
 
 // out = ca a + cb b + cc c with host scalars (b, c nullable): the DPM-Solver update combinations (dpm:520-1100).
@@ -1434,8 +1381,7 @@ __global__ __launch_bounds__(256) void lincomb_kernel(const float* __restrict__ 
 extern "C" int mmd_lincomb(const float* a, float ca, const float* b, float cb, const float* c, float cc, float* out, int64_t n,
                            void* stream) {
   MMD_REQUIRE(a && out && n > 0, "lincomb: bad argument");
-  hipLaunchKernelGGL(lincomb_kernel, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, a, b, c, out, ca, cb, cc, n);
-  return mmd_check_launch("lincomb");
+  return mmd_launch<lincomb_kernel>("lincomb", dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, a, b, c, out, ca, cb, cc, n);
 }
 
 // Gradient payload conversion of the data-parallel all-reduce (optim.FlatAdamW, grad_payload = "bf16"): y = (T_out)(x * scale).
@@ -1450,9 +1396,7 @@ __global__ __launch_bounds__(256) void cast_kernel(const void* __restrict__ x, v
 extern "C" int mmd_cast(const void* x, int src_dtype, void* y, int dst_dtype, float scale, int64_t n, void* stream) {
   MMD_REQUIRE(x && y && n > 0, "cast: bad argument");
   MMD_REQUIRE((src_dtype == MMD_F32 || src_dtype == MMD_BF16) && (dst_dtype == MMD_F32 || dst_dtype == MMD_BF16), "cast: bad dtype");
-  hipLaunchKernelGGL(cast_kernel, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, x, y, src_dtype == MMD_BF16, dst_dtype == MMD_BF16,
-                     scale, n);
-  return mmd_check_launch("cast");
+  return mmd_launch<cast_kernel>("cast", dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, x, y, src_dtype == MMD_BF16, dst_dtype == MMD_BF16, scale, n);
 }
 
 // Backward of the sampling update through the posterior mean (gradient-guided conditional sampling, gd:722-817):
@@ -1479,8 +1423,8 @@ extern "C" int mmd_ddpm_update_bwd(const float* x, const float* model_out, const
   DdpmParams p;
   p.x = x; p.mo = model_out; p.noise = nullptr; p.out = nullptr; p.x0_out = nullptr; p.mean_out = nullptr; p.logvar_out = nullptr;
   p.tables = tables; p.t = t; p.T = T; p.N = N; p.F = 1; p.C = 1; p.HW = (int)per_sample; p.flags = flags;
-  hipLaunchKernelGGL(ddpm_update_bwd_kernel, dim3(ew_grid((int64_t)N * per_sample)), dim3(256), 0, (hipStream_t)stream, p, dsample, dx, dmodel_out);
-  return mmd_check_launch("ddpm_update_bwd");
+  return mmd_launch<ddpm_update_bwd_kernel>("ddpm_update_bwd", dim3(ew_grid((int64_t)N * per_sample)), dim3(256), 0, (hipStream_t)stream, p, dsample, dx,
+                                            dmodel_out);
 }
 
 // ----------------------------------------------------------------------------- DPM-Solver helpers
@@ -1530,8 +1474,7 @@ __global__ __launch_bounds__(1024) void abs_quantile_kernel(const float* __restr
 }
 extern "C" int mmd_abs_quantile(const float* x, int N, int64_t per_sample, float q, float* out, void* stream) {
   MMD_REQUIRE(x && out && N > 0 && per_sample > 0 && q >= 0.f && q <= 1.f, "abs_quantile: bad argument");
-  hipLaunchKernelGGL(abs_quantile_kernel, dim3(N), dim3(1024), 0, (hipStream_t)stream, x, per_sample, q, out);
-  return mmd_check_launch("abs_quantile");
+  return mmd_launch<abs_quantile_kernel>("abs_quantile", dim3(N), dim3(1024), 0, (hipStream_t)stream, x, per_sample, q, out);
 }
 
 // x[n, :] = clamp(x, -s_n, s_n) / (s_n / max_val),  s_n = max(s[n], 1)        (in place)
@@ -1545,8 +1488,7 @@ __global__ __launch_bounds__(256) void clamp_scale_kernel(float* __restrict__ x,
 extern "C" int mmd_clamp_scale(float* x, const float* s, float max_val, int N, int64_t per_sample, void* stream) {
   MMD_REQUIRE(x && s && N > 0 && per_sample > 0 && max_val > 0.f, "clamp_scale: bad argument");
   const int64_t total = per_sample * N;
-  hipLaunchKernelGGL(clamp_scale_kernel, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, x, s, max_val, per_sample, total);
-  return mmd_check_launch("clamp_scale");
+  return mmd_launch<clamp_scale_kernel>("clamp_scale", dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, x, s, max_val, per_sample, total);
 }
 
 // Adaptive step-size error term (dpm:1088-1149): out[n] += sum_i ((hi - lo) / max(atol, rtol * max(|lo|, |prev|)))^2
@@ -1575,9 +1517,8 @@ extern "C" int mmd_dpm_err(const float* hi, const float* lo, const float* prev, 
                            double* out, void* stream) {
   MMD_REQUIRE(hi && lo && prev && out && N > 0 && per_sample > 0, "dpm_err: bad argument");
   const int chunks = (int)((per_sample + 256 * 16 - 1) / (256 * 16));
-  hipLaunchKernelGGL(dpm_err_kernel, dim3(chunks < 1 ? 1 : (chunks > 256 ? 256 : chunks), N), dim3(256), 0, (hipStream_t)stream, hi, lo, prev,
-                     atol, rtol, per_sample, out);
-  return mmd_check_launch("dpm_err");
+  return mmd_launch<dpm_err_kernel>("dpm_err", dim3(chunks < 1 ? 1 : (chunks > 256 ? 256 : chunks), N), dim3(256), 0, (hipStream_t)stream, hi, lo, prev, atol,
+                                    rtol, per_sample, out);
 }
 
 // ----------------------------------------------------------------------------- super-resolution model input
@@ -1605,9 +1546,8 @@ __global__ __launch_bounds__(256) void bilinear_concat_kernel(const float* __res
 }
 extern "C" int mmd_bilinear_concat(const float* x, const float* low, float* out, int N, int C, int H, int W, int h, int w, void* stream) {
   MMD_REQUIRE(x && low && out && N > 0 && C > 0 && H > 0 && W > 0 && h > 0 && w > 0, "bilinear_concat: bad argument");
-  hipLaunchKernelGGL(bilinear_concat_kernel, dim3(ew_grid((int64_t)N * 2 * C * H * W)), dim3(256), 0, (hipStream_t)stream, x, low, out, N, C, H,
-                     W, h, w);
-  return mmd_check_launch("bilinear_concat");
+  return mmd_launch<bilinear_concat_kernel>("bilinear_concat", dim3(ew_grid((int64_t)N * 2 * C * H * W)), dim3(256), 0, (hipStream_t)stream, x, low, out, N, C,
+                                            H, W, h, w);
 }
 
 // The same input as channels-last ROWS for the implicit-GEMM stem: rows[(n, y, x), 0:C] = x, [C:2C] = bilinear(low), [2C:Cpad] = 0.
@@ -1642,9 +1582,10 @@ extern "C" int mmd_bilinear_concat_rows(int dtype, const float* x, const float* 
   MMD_REQUIRE(x && low && out && N > 0 && C > 0 && H > 0 && W > 0 && h > 0 && w > 0 && Cpad >= 2 * C, "bilinear_concat_rows: bad argument");
   MMD_REQUIRE(dtype == MMD_BF16 || dtype == MMD_F32, "bilinear_concat_rows: bad dtype");
   const dim3 grid(ew_grid((int64_t)N * H * W));
-  if (dtype == MMD_BF16) hipLaunchKernelGGL(bilinear_concat_rows_kernel<__bf16>, grid, dim3(256), 0, (hipStream_t)stream, x, low, (char*)out, N, C, H, W, h, w, Cpad);
-  else hipLaunchKernelGGL(bilinear_concat_rows_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, x, low, (char*)out, N, C, H, W, h, w, Cpad);
-  return mmd_check_launch("bilinear_concat_rows");
+  return mmd_by_dtype(dtype, [&](auto t) {
+    return mmd_launch<bilinear_concat_rows_kernel<typename decltype(t)::type>>("bilinear_concat_rows", grid, dim3(256), 0, (hipStream_t)stream, x, low,
+                                                                               (char*)out, N, C, H, W, h, w, Cpad);
+  });
 }
 
 // ----------------------------------------------------------------------------- training-loss gradient (learned-range variance)
@@ -1724,9 +1665,8 @@ extern "C" int mmd_loss_terms_bwd(const float* x0, const float* xt, const float*
   LossParams p;
   p.x0 = x0; p.xt = xt; p.mo = model_out; p.target = target; p.tables = tables; p.t = t; p.partial = nullptr;
   p.T = T; p.N = N; p.F = F; p.C = C; p.HW = HW; p.flags = flags; p.nchunk = 0;
-  hipLaunchKernelGGL(loss_terms_bwd_kernel, dim3(ew_grid((int64_t)N * F * C * HW)), dim3(256), 0, (hipStream_t)stream, p, dmse, dvb, vb_scale,
-                     g_model_out);
-  return mmd_check_launch("loss_terms_bwd");
+  return mmd_launch<loss_terms_bwd_kernel>("loss_terms_bwd", dim3(ew_grid((int64_t)N * F * C * HW)), dim3(256), 0, (hipStream_t)stream, p, dmse, dvb, vb_scale,
+                                           g_model_out);
 }
 
 // ----------------------------------------------------------------------------- variational-bound gradient (KL / RESCALED_KL training)
@@ -1772,6 +1712,5 @@ extern "C" int mmd_vlb_terms_bwd(const float* x0, const float* xt, const float* 
   VlbParams p;
   p.x0 = x0; p.xt = xt; p.noise = nullptr; p.mo = model_out; p.px0_out = nullptr; p.tables = tables; p.t = t; p.partial = nullptr;
   p.T = T; p.N = N; p.F = F; p.C = C; p.HW = HW; p.flags = flags; p.nchunk = 0;
-  hipLaunchKernelGGL(vlb_terms_bwd_kernel, dim3(ew_grid((int64_t)N * F * C * HW)), dim3(256), 0, (hipStream_t)stream, p, dvb, g_model_out);
-  return mmd_check_launch("vlb_terms_bwd");
+  return mmd_launch<vlb_terms_bwd_kernel>("vlb_terms_bwd", dim3(ew_grid((int64_t)N * F * C * HW)), dim3(256), 0, (hipStream_t)stream, p, dvb, g_model_out);
 }

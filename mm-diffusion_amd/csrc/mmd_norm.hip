@@ -418,7 +418,7 @@ static int check_geom(const char* who, int dtype, int C, int S, int Tn, int inne
 static int gn_rows_per_block(int dtype, int C, int S, int Tn) {
   const int cv = C / (dtype == MMD_BF16 ? 8 : 4);
   const int rpp = 256 / cv > 0 ? 256 / cv : 1;
-  static const int cap = [] { const char* e = getenv("MMD_GN_BLOCKS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 1280; }();
+  static const int cap = mmd_env_int("MMD_GN_BLOCKS", 1280);
   // R depends on the slice (Tn, C) only, never on the number of slices: the per-thread fp32 partial sums - and with them the last
   // bit of the statistics - must not change with the batch size (a batch-4 run equals four batch-1 runs bitwise).  320 chunks per
   // slice = one resident wave of blocks (5/CU x 256 CUs) at the 4 slices of the headline batch; MMD_GN_BLOCKS: tuning (x4).
@@ -445,28 +445,21 @@ extern "C" int mmd_gn_stats(int dtype, const void* x, int64_t ld, int C, int S, 
   hipStream_t st = (hipStream_t)stream;
   const int R = gn_rows_per_block(dtype, C, S, Tn);
   const int nchunks = cdiv(Tn, R);
-  if (nchunks == 1) {
-    if (dtype == MMD_BF16)
-      hipLaunchKernelGGL((gn_partial_kernel<__bf16, true>), dim3(1, S), dim3(256), 0, st, (const char*)x, ld, C, g, R, (double*)nullptr, 1,
-                         gamma, beta, film, film_ld, eps, a_out, b_out, mr_out);
-    else
-      hipLaunchKernelGGL((gn_partial_kernel<float, true>), dim3(1, S), dim3(256), 0, st, (const char*)x, ld, C, g, R, (double*)nullptr, 1,
-                         gamma, beta, film, film_ld, eps, a_out, b_out, mr_out);
-    return mmd_check_launch("gn_stats_one");
-  }
+  if (nchunks == 1)
+    return mmd_by_dtype(dtype, [&](auto t) {
+      return mmd_launch<gn_partial_kernel<typename decltype(t)::type, true>>("gn_stats_one", dim3(1, S), dim3(256), 0, st, (const char*)x, ld, C, g, R,
+                                                                             (double*)nullptr, 1, gamma, beta, film, film_ld, eps, a_out, b_out, mr_out);
+    });
   MMD_REQUIRE(workspace && ((uintptr_t)workspace) % 16 == 0, "gn_stats: 16-byte aligned workspace required for multi-block slices");
   dim3 grid(nchunks, S);
-  if (dtype == MMD_BF16)
-    hipLaunchKernelGGL((gn_partial_kernel<__bf16, false>), grid, dim3(256), 0, st, (const char*)x, ld, C, g, R, (double*)workspace, nchunks,
-                       gamma, beta, film, film_ld, eps, a_out, b_out, (float*)nullptr);
-  else
-    hipLaunchKernelGGL((gn_partial_kernel<float, false>), grid, dim3(256), 0, st, (const char*)x, ld, C, g, R, (double*)workspace, nchunks,
-                       gamma, beta, film, film_ld, eps, a_out, b_out, (float*)nullptr);
-  rc = mmd_check_launch("gn_partial");
+  rc = mmd_by_dtype(dtype, [&](auto t) {
+    return mmd_launch<gn_partial_kernel<typename decltype(t)::type, false>>("gn_partial", grid, dim3(256), 0, st, (const char*)x, ld, C, g, R,
+                                                                            (double*)workspace, nchunks, gamma, beta, film, film_ld, eps, a_out, b_out,
+                                                                            (float*)nullptr);
+  });
   if (rc) return rc;
-  hipLaunchKernelGGL(gn_finalize_kernel, dim3(S), dim3(1024), 0, st, (const char*)x, dtype, ld, g, (const double*)workspace, nchunks, C, Tn, gamma, beta,
-                     film, film_ld, eps, a_out, b_out, mr_out);
-  return mmd_check_launch("gn_finalize");
+  return mmd_launch<gn_finalize_kernel>("gn_finalize", dim3(S), dim3(1024), 0, st, (const char*)x, dtype, ld, g, (const double*)workspace, nchunks, C, Tn,
+                                        gamma, beta, film, film_ld, eps, a_out, b_out, mr_out);
 }
 
 // ---- GroupNorm finalize from PRODUCER-side statistics (mmd_conv_gemm_stats): rec[(row / 64) * rec_ld + q] = (sum, sum of squares) of
@@ -544,9 +537,8 @@ extern "C" int mmd_gn_finalize_stats(const float* rec, int64_t rec_ld, int C, in
   MMD_REQUIRE(C > 0 && C % (4 * GN_GROUPS) == 0 && C / GN_GROUPS <= 256 && rec_ld >= C / 4,
               "gn_finalize_stats: channel count %d (groups of whole quads: a multiple of 128; ld %ld quads)", C, (long)rec_ld);
   MMD_REQUIRE(S > 0 && Tn > 0 && Tn % 64 == 0, "gn_finalize_stats: slices must be multiples of 64 rows (S=%d Tn=%d)", S, Tn);
-  hipLaunchKernelGGL(gn_finalize_rec_kernel, dim3(GN_GROUPS, S), dim3(256), 0, (hipStream_t)stream, rec, rec_ld, C, S, Tn, gamma, beta,
-                     film, film_ld, eps, a_out, b_out, mr_out);
-  return mmd_check_launch("gn_finalize_stats");
+  return mmd_launch<gn_finalize_rec_kernel>("gn_finalize_stats", dim3(GN_GROUPS, S), dim3(256), 0, (hipStream_t)stream, rec, rec_ld, C, S, Tn, gamma, beta,
+                                            film, film_ld, eps, a_out, b_out, mr_out);
 }
 
 // ---- GroupNorm32(+FiLM)(+SiLU) of slices of a few hundred rows in ONE launch: block = one (group, slice), its Tn x cpg elements stay in
@@ -663,13 +655,10 @@ extern "C" int mmd_gn_group(int dtype, const void* x, int64_t ldx, void* y, int6
   MMD_REQUIRE(((uintptr_t)x) % 16 == 0 && ldx % 4 == 0 && (!y || (((uintptr_t)y) % 16 == 0 && ldy % 4 == 0)), "gn_group: rows must be aligned to channel quads");
   (void)eb;
   SliceGeom g{S, Tn, inner, outer_stride, inner_stride, tstride};
-  if (dtype == MMD_BF16)
-    hipLaunchKernelGGL(gn_group_kernel<__bf16>, dim3(GN_GROUPS, S), dim3(256), 0, (hipStream_t)stream, (const char*)x, ldx, (char*)y, ldy, C, g, gamma,
-                       beta, film, film_ld, eps, act, a_out, b_out, mr_out);
-  else
-    hipLaunchKernelGGL(gn_group_kernel<float>, dim3(GN_GROUPS, S), dim3(256), 0, (hipStream_t)stream, (const char*)x, ldx, (char*)y, ldy, C, g, gamma,
-                       beta, film, film_ld, eps, act, a_out, b_out, mr_out);
-  return mmd_check_launch("gn_group");
+  return mmd_by_dtype(dtype, [&](auto t) {
+    return mmd_launch<gn_group_kernel<typename decltype(t)::type>>("gn_group", dim3(GN_GROUPS, S), dim3(256), 0, (hipStream_t)stream, (const char*)x, ldx,
+                                                                   (char*)y, ldy, C, g, gamma, beta, film, film_ld, eps, act, a_out, b_out, mr_out);
+  });
 }
 
 extern "C" int mmd_gn_apply(int dtype, const void* x, int64_t ldx, void* y, int64_t ldy, int64_t rows, int C, int S, int Tn,
@@ -685,11 +674,9 @@ extern "C" int mmd_gn_apply(int dtype, const void* x, int64_t ldx, void* y, int6
   while ((int64_t)S * cdiv(Tn, R) > 4096 && R < 4096) R *= 2;
   dim3 grid(cdiv(Tn, R), S);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MMD_BF16)
-    hipLaunchKernelGGL(gn_apply_kernel<__bf16>, grid, dim3(256), 0, st, (const char*)x, ldx, (char*)y, ldy, C, g, a, b, act, R);
-  else
-    hipLaunchKernelGGL(gn_apply_kernel<float>, grid, dim3(256), 0, st, (const char*)x, ldx, (char*)y, ldy, C, g, a, b, act, R);
-  return mmd_check_launch("gn_apply");
+  return mmd_by_dtype(dtype, [&](auto t) {
+    return mmd_launch<gn_apply_kernel<typename decltype(t)::type>>("gn_apply", grid, dim3(256), 0, st, (const char*)x, ldx, (char*)y, ldy, C, g, a, b, act, R);
+  });
 }
 
 extern "C" int mmd_add_rowbias(int dtype, void* x, int64_t ld, int64_t rows, int C, int64_t rows_per_sample, const float* e,
@@ -699,11 +686,9 @@ extern "C" int mmd_add_rowbias(int dtype, void* x, int64_t ld, int64_t rows, int
   const int64_t total = rows * (C / (dtype == MMD_BF16 ? 8 : 4));
   const int grid = (int)min((int64_t)4096, (total + 255) / 256);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MMD_BF16)
-    hipLaunchKernelGGL(add_rowbias_kernel<__bf16>, dim3(grid), dim3(256), 0, st, (char*)x, ld, rows, C, rows_per_sample, e, e_ld);
-  else
-    hipLaunchKernelGGL(add_rowbias_kernel<float>, dim3(grid), dim3(256), 0, st, (char*)x, ld, rows, C, rows_per_sample, e, e_ld);
-  return mmd_check_launch("add_rowbias");
+  return mmd_by_dtype(dtype, [&](auto t) {
+    return mmd_launch<add_rowbias_kernel<typename decltype(t)::type>>("add_rowbias", dim3(grid), dim3(256), 0, st, (char*)x, ld, rows, C, rows_per_sample, e, e_ld);
+  });
 }
 
 // GroupNorm32(+SiLU) of S short slices (Tn <= 16 rows each; geometry as mmd_gn_stats) in ONE launch: y = act(GN(x) gamma + beta).
@@ -720,12 +705,9 @@ extern "C" int mmd_gn_small(int dtype, const void* x, int64_t ldx, void* y, int6
   MMD_REQUIRE(cv <= 256, "gn_small: %d channels is too wide", C);
   const int spb = 256 / cv;
   const size_t lds = (size_t)spb * (C / 4) * sizeof(float);
-  if (dtype == MMD_BF16)
-    hipLaunchKernelGGL((gn_small_kernel<__bf16>), dim3(cdiv(S, spb)), dim3(256), lds, (hipStream_t)stream, (const char*)x, ldx, (char*)y, ldy, C, g,
-                       gamma, beta, eps, act, spb);
-  else
-    hipLaunchKernelGGL((gn_small_kernel<float>), dim3(cdiv(S, spb)), dim3(256), lds, (hipStream_t)stream, (const char*)x, ldx, (char*)y, ldy, C, g,
-                       gamma, beta, eps, act, spb);
-  return mmd_check_launch("gn_small");
+  return mmd_by_dtype(dtype, [&](auto t) {
+    return mmd_launch<gn_small_kernel<typename decltype(t)::type>>("gn_small", dim3(cdiv(S, spb)), dim3(256), lds, (hipStream_t)stream, (const char*)x, ldx,
+                                                                   (char*)y, ldy, C, g, gamma, beta, eps, act, spb);
+  });
 }
 

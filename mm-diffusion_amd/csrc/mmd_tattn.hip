@@ -453,23 +453,14 @@ extern "C" int mmd_tattn_pack(const void* Wpre, const void* Wqkv, const void* Wp
   MMD_REQUIRE(Wqkv && Wproj && out, "tattn_pack: null pointer");
   MMD_REQUIRE(C == 256, "tattn_pack: built for C = 256 (got %d)", C);
   const int64_t chunks16 = mmd_tattn_weight_bytes(C, Wpre != nullptr) / 16;
-  hipLaunchKernelGGL(tattn_pack_kernel, dim3((unsigned)((chunks16 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)Wpre,
-                     (const uint16_t*)Wqkv, (const uint16_t*)Wproj, (uint16_t*)out, C, tattn_cch(C), Wpre ? 1 : 0);
-  return mmd_check_launch("tattn_pack");
+  return mmd_launch<tattn_pack_kernel>("tattn_pack", dim3((unsigned)((chunks16 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)Wpre,
+                                       (const uint16_t*)Wqkv, (const uint16_t*)Wproj, (uint16_t*)out, C, tattn_cch(C), Wpre ? 1 : 0);
 }
 
 template <int C, bool PRE>
 static int launch_tattn(const TAttnParams& p, hipStream_t st) {
   const size_t lds = 2 * (size_t)TACfg<C>::STAGE_B + (size_t)TACfg<C>::TAB_F * sizeof(float);
-  static bool attr_done[MMD_MAX_DEVICES] = {};
-  bool& attr_set = attr_done[mmd_device_slot()];
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)tattn_kernel<C, PRE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return mmd_set_error(MMD_ERR_LAUNCH, "tattn_block: set LDS attr: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((tattn_kernel<C, PRE>), dim3(p.N * (p.HW / 8)), dim3(256), lds, st, p);
-  return mmd_check_launch("tattn_block");
+  return mmd_launch<tattn_kernel<C, PRE>>("tattn_block", dim3(p.N * (p.HW / 8)), dim3(256), lds, st, p);
 }
 
 // X / Y: rows (n, f, pixel) x C bf16 (Y may not alias X: other workgroups' residual reads); Wf from mmd_tattn_pack; bias_qkv [3 C],

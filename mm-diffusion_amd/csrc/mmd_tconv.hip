@@ -203,29 +203,17 @@ extern "C" int mmd_tconv_pack(const void* W, void* out, int Cin, int Cout, void*
   MMD_REQUIRE(W && out, "tconv_pack: null pointer");
   MMD_REQUIRE((Cin == 256 || Cin == 384 || Cin == 512) && Cout > 0 && Cout % 64 == 0 && Cout <= 512, "tconv_pack: Cin in {256, 384, 512}, Cout %% 64 == 0, <= 512 (got %d -> %d)", Cin, Cout);
   const int64_t chunks16 = (int64_t)Cout * 3 * Cin / 8;
-  hipLaunchKernelGGL(tconv_pack_kernel, dim3((unsigned)((chunks16 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)W,
-                     (uint16_t*)out, Cin, Cout, tconv_cc(Cin));
-  return mmd_check_launch("tconv_pack");
+  return mmd_launch<tconv_pack_kernel>("tconv_pack", dim3((unsigned)((chunks16 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)W,
+                                       (uint16_t*)out, Cin, Cout, tconv_cc(Cin));
 }
 
 template <int KS, int CC>
 static int launch_tconv(const TConvParams& p, hipStream_t st) {
   const size_t lds = 2 * (size_t)(KS * CC * 128) + (512 + 128) * sizeof(float);
-  static bool attr_done[MMD_MAX_DEVICES] = {};
-  bool& attr_set = attr_done[mmd_device_slot()];
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)tconv_kernel<KS, CC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return mmd_set_error(MMD_ERR_LAUNCH, "tconv: set LDS attr: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
   // column split (results do not depend on it): the smallest divisor of the column-block count that gives the chip ONE workgroup per CU
   // (two until round 5: see the row-strip GEMM's split, mmd_gemm.hip - the second slot of a CU is the other launch chain's)
   const int rowblocks = p.N * (p.HW / 8), ncb = p.Cout / CC;
-  static const int want_blocks = [] {                     // tuning switch (read once): MMD_TCONV_BLOCKS
-    const char* e = getenv("MMD_TCONV_BLOCKS");
-    const int v = e ? atoi(e) : 0;
-    return v > 0 ? v : 256;
-  }();
+  static const int want_blocks = mmd_env_int("MMD_TCONV_BLOCKS", 256);   // tuning switch (read once)
   int nsplit = 1;
   for (int d = 1; d <= ncb; ++d)
     if (ncb % d == 0) {
@@ -234,8 +222,7 @@ static int launch_tconv(const TConvParams& p, hipStream_t st) {
     }
   TConvParams q = p;
   q.nsplit = nsplit;
-  hipLaunchKernelGGL((tconv_kernel<KS, CC>), dim3(rowblocks * nsplit), dim3(256), lds, st, q);
-  return mmd_check_launch("tconv");
+  return mmd_launch<tconv_kernel<KS, CC>>("tconv", dim3(rowblocks * nsplit), dim3(256), lds, st, q);
 }
 
 // Y[(n, f, pixel), :] = bias + sum over df of X[(n, f + df, pixel), :] W_df^T (zero outside the 16 frames).  X / Y: rows (n, f, pixel),

@@ -572,9 +572,8 @@ extern "C" int mmd_vconv2d1d_pack(const void* Ws, const void* Wt, void* out, int
   MMD_REQUIRE(Ws && Wt && out, "vconv2d1d_pack: null pointer");
   MMD_REQUIRE(Cout == 128 && Cin > 0 && Cin % 32 == 0, "vconv2d1d_pack: needs 128 output channels and Cin %% 32 == 0 (got %d -> %d)", Cin, Cout);
   const int64_t total = mmd_vconv2d1d_weight_bytes(Cin) / 2;
-  hipLaunchKernelGGL(vconv_pack_kernel, dim3(cdiv(total, 256 * 8)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)Ws, (const uint16_t*)Wt,
-                     (uint16_t*)out, Cin, total);
-  return mmd_check_launch("vconv2d1d_pack");
+  return mmd_launch<vconv_pack_kernel>("vconv2d1d_pack", dim3(cdiv(total, 256 * 8)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)Ws,
+                                       (const uint16_t*)Wt, (uint16_t*)out, Cin, total);
 }
 
 extern "C" int mmd_vconv2d1d(const void* X, int64_t ldx, const float* gn_a, const float* gn_b, int act, int S, int64_t rows_per_slice,
@@ -605,28 +604,15 @@ extern "C" int mmd_vconv2d1d(const void* X, int64_t ldx, const float* gn_a, cons
   // another launch queue fits beside it; weights one step ahead).  Bitwise equal, measured (profiles/r06_vconv_two_slot_ring.txt): the
   // kernel alone + 1 ... 3 %, the step unchanged (11.09 vs 11.04 ms, three alternating runs each) - with 2 x 200 of a SIMD's 512 VGPRs
   // held by this kernel's two waves only kernels of <= 112 VGPRs can join, LDS or not.  Default: three slots.
-  const char* ring_env = getenv("MMD_VCONV_RING");           // read per call (a launch plan is recorded once): tests flip it in-process
-  const bool ring2 = ring_env && atoi(ring_env) == 2;
+  const bool ring2 = mmd_env_int("MMD_VCONV_RING", 0) == 2;  // read per call (a launch plan is recorded once): tests flip it in-process
   const size_t lds = 2 * VC_STAGE_B + (ring2 ? 2 : 3) * VC_WSLOT_B + 512 + 1024 + 256;
-  static bool attr_done[MMD_MAX_DEVICES] = {};
-  bool& attr_set = attr_done[mmd_device_slot()];
-  if (!attr_set) {
-    const void* fns[6] = {(const void*)vconv2d1d_kernel<0, false>, (const void*)vconv2d1d_kernel<1, false>, (const void*)vconv2d1d_kernel<2, false>,
-                          (const void*)vconv2d1d_kernel<0, true>,  (const void*)vconv2d1d_kernel<1, true>,  (const void*)vconv2d1d_kernel<2, true>};
-    for (int i = 0; i < 6; ++i) {
-      const hipError_t e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * VC_STAGE_B + (i < 3 ? 3 : 2) * VC_WSLOT_B + 512 + 1024 + 256));
-      if (e != hipSuccess) return mmd_set_error(MMD_ERR_LAUNCH, "vconv2d1d: set LDS attr: %s", hipGetErrorString(e));
-    }
-    attr_set = true;
-  }
   int ncu = 0;
   if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, mmd_device_slot()) != hipSuccess || ncu <= 0) ncu = 256;
   const int total = N * (H / 4) * (W / 4);
   const int grid = total < ncu ? total : ncu;               // persistent blocks, one per CU
   const int gnm = !gn_a ? 0 : (act ? 2 : 1);
-#define VC_LAUNCH(G, R) hipLaunchKernelGGL((vconv2d1d_kernel<G, R>), dim3(grid), dim3(512), lds, (hipStream_t)stream, p)
-  if (ring2) { if (gnm == 0) VC_LAUNCH(0, true); else if (gnm == 1) VC_LAUNCH(1, true); else VC_LAUNCH(2, true); }
-  else { if (gnm == 0) VC_LAUNCH(0, false); else if (gnm == 1) VC_LAUNCH(1, false); else VC_LAUNCH(2, false); }
+#define VC_LAUNCH(G, R) mmd_launch<vconv2d1d_kernel<G, R>>("vconv2d1d", dim3(grid), dim3(512), lds, (hipStream_t)stream, p)
+  if (!ring2) return gnm == 0 ? VC_LAUNCH(0, false) : gnm == 1 ? VC_LAUNCH(1, false) : VC_LAUNCH(2, false);
+  return gnm == 0 ? VC_LAUNCH(0, true) : gnm == 1 ? VC_LAUNCH(1, true) : VC_LAUNCH(2, true);
 #undef VC_LAUNCH
-  return mmd_check_launch("vconv2d1d");
 }

@@ -130,13 +130,13 @@ def test_bench_dump_outputs_float32_budget_and_fixed_sample(tmp_path):
 
 def test_switch_table_lists_every_environment_read():
     """INTEGRATION.md section 4 has one row per MMD_* variable that the library, the Python host or the build reads - no more, no fewer.
-    A plain regex over the sources: names inside getenv(...) / os.environ / os.getenv reads and inside ops._flag(...), the host's on / off
-    helper over os.environ."""
+    A plain regex over the sources: names inside getenv(...) / mmd_env_int|char|set(...) (the library's readers) / os.environ / os.getenv
+    reads and inside ops._flag(...), the host's on / off helper over os.environ."""
     import glob
     import re
     base = os.path.join(ROOT, "mm-diffusion_amd")
     files = glob.glob(os.path.join(base, "csrc", "*")) + glob.glob(os.path.join(base, "mm_diffusion", "*.py")) + [os.path.join(base, "build.py")]
-    read = re.compile(r'(?:\bgetenv\(|\bos\.environ(?:\.get\(|\.setdefault\(|\[)|\b_flag\()\s*"(MMD_[A-Z0-9_]+)"')
+    read = re.compile(r'(?:\bgetenv\(|\bmmd_env_(?:int|char|set)\(|\bos\.environ(?:\.get\(|\.setdefault\(|\[)|\b_flag\()\s*"(MMD_[A-Z0-9_]+)"')
     used = set()
     for f in files:
         with open(f, errors="replace") as fh:
