@@ -400,6 +400,42 @@ int mmd_mse_grad(const float* out, const float* target, const float* w, float* g
 int mmd_adamw_step(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr, float beta1, float beta2, float eps,
                    float weight_decay, int step, float ema_rate, void* stream);
 
+/* --- training step guard: gradient / parameter norms, non-finite skip and clipping decided ON THE DEVICE (reference
+ * fp16_util.py:188-236: norms logged per step, took_step = False on a non-finite gradient norm, EMA only if took_step).
+ * Three ordinary launches in stream order; none communicates between its blocks and every sum has a fixed order (double), so
+ * the results are bitwise repeatable.  The host reads the control block only when it logs. */
+#define MMD_STEP_CHUNK 16384     /* longest chunk of the chunk table, in elements */
+#define MMD_STEP_MAX_EMA 4
+struct mmd_step_ctrl {           /* 64 bytes, device memory, zero-initialised by the caller */
+  double cum_grad_norm;          /* never-reset sums over the TAKEN steps: interval means come from differencing two reads */
+  double cum_param_norm;
+  int64_t cum_count;
+  float grad_norm;               /* this step, before clipping; rounded once from the double sqrt */
+  float param_norm;              /* the parameters the step is applied to (before the update) */
+  float clip_coef;               /* 1, or max_grad_norm / (grad_norm + 1e-6) when the norm exceeds max_grad_norm > 0 */
+  float bc1, bc2;                /* 1 - beta^steps_taken of the step about to be applied */
+  int32_t took_step;             /* 1 iff the gradient sum of squares is finite */
+  int32_t steps_taken;           /* incremented only when took_step */
+  int32_t skipped_total;
+  int32_t first_bad_param;       /* this step: lowest parameter whose gradient sum is non-finite, else -1 */
+  int32_t last_bad_param;        /* first_bad_param of the most recent skipped step (the caller initialises both to -1) */
+};
+int mmd_step_ctrl_bytes(void);   /* sizeof(struct mmd_step_ctrl) as the library was compiled (host only) */
+/* partial[c] = { sum g^2, sum p^2 } (double) over chunk c = elements [chunk_lo[c], chunk_lo[c] + chunk_len[c]) of the flat fp32
+ * buffers g / p (p nullable: 0), one block per chunk; chunk starts need only 4-byte alignment.  A chunk that leaves [0, n) is
+ * clipped to it.  An fp32 square cannot overflow a double, so a sum is non-finite exactly when one of its elements is. */
+int mmd_sumsq_chunks(const float* g, const float* p, int64_t n, const int64_t* chunk_lo, const int32_t* chunk_len, int nchunks,
+                     double* partial, void* stream);
+/* One block: param_sumsq[i] = fold of the chunks param_first_chunk[i] .. param_first_chunk[i + 1] - 1 in ascending order, the
+ * totals a fixed-order fold of those; then the control block is advanced by one step (see the struct). */
+int mmd_step_control(const double* partial, const int32_t* param_first_chunk, int P, double* param_sumsq, float max_grad_norm,
+                     float beta1, float beta2, struct mmd_step_ctrl* ctrl, void* stream);
+/* AdamW + up to MMD_STEP_MAX_EMA EMA copies (NULL = absent) in one launch on g * ctrl->clip_coef with the bias corrections of
+ * ctrl; every thread returns at once when ctrl->took_step is 0 (p, m, v and the EMA copies stay bitwise what they were). */
+int mmd_adamw_step_guarded(float* p, const float* g, float* m, float* v, float* ema0, float* ema1, float* ema2, float* ema3,
+                           float rate0, float rate1, float rate2, float rate3, int64_t n, float lr, float beta1, float beta2,
+                           float eps, float weight_decay, const struct mmd_step_ctrl* ctrl, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -693,6 +693,145 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
   }
 }
 
+// ----------------------------------------------------------------------------- training step guard (include/mmd.h: mmd_step_ctrl)
+// Three launches in stream order, the reduction pattern of loss_terms_kernel / loss_finalize_kernel (mmd_misc.hip): per-block partials
+// in double, folded in ascending order by a second launch.  No block waits for or signals another one.
+// One block per chunk: every thread sums its elements in ascending order, then a fixed tree over the 256 threads.  The chunk start is
+// only element aligned (chunks are cut at parameter boundaries): up to 3 head elements, 16-byte vectors, up to 3 tail elements.
+__global__ __launch_bounds__(256) void sumsq_chunks_kernel(const float* __restrict__ g, const float* __restrict__ p, int64_t n,
+                                                           const int64_t* __restrict__ chunk_lo, const int32_t* __restrict__ chunk_len,
+                                                           double* __restrict__ partial) {
+  __shared__ double s_g[256], s_p[256];
+  const int tid = threadIdx.x;
+  int64_t lo = chunk_lo[blockIdx.x];
+  int64_t hi = lo + chunk_len[blockIdx.x];
+  lo = lo < 0 ? 0 : lo;
+  hi = hi > n ? n : hi;
+  const int len = hi > lo ? (int)(hi - lo) : 0;
+  const int head = min(len, (int)((4 - (lo & 3)) & 3));          // g and p are 16-byte aligned (checked by the caller side)
+  const int nvec = (len - head) >> 2;
+  const int tail = len - head - 4 * nvec;
+  double sg = 0.0, sp = 0.0;
+  if (tid < head) {
+    const double a = (double)g[lo + tid];
+    sg += a * a;
+    if (p) { const double b = (double)p[lo + tid]; sp += b * b; }
+  }
+  const float4* gv = (const float4*)(g + lo + head);
+  const float4* pv = p ? (const float4*)(p + lo + head) : nullptr;
+  for (int i = tid; i < nvec; i += 256) {
+    const float4 a = gv[i];
+    sg += (double)a.x * (double)a.x;
+    sg += (double)a.y * (double)a.y;
+    sg += (double)a.z * (double)a.z;
+    sg += (double)a.w * (double)a.w;
+    if (pv) {
+      const float4 b = pv[i];
+      sp += (double)b.x * (double)b.x;
+      sp += (double)b.y * (double)b.y;
+      sp += (double)b.z * (double)b.z;
+      sp += (double)b.w * (double)b.w;
+    }
+  }
+  if (tid < tail) {
+    const int64_t i = lo + head + 4 * (int64_t)nvec + tid;
+    const double a = (double)g[i];
+    sg += a * a;
+    if (p) { const double b = (double)p[i]; sp += b * b; }
+  }
+  s_g[tid] = sg;
+  s_p[tid] = sp;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) { s_g[tid] += s_g[tid + o]; s_p[tid] += s_p[tid + o]; }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    partial[(int64_t)blockIdx.x * 2] = s_g[0];
+    partial[(int64_t)blockIdx.x * 2 + 1] = s_p[0];
+  }
+}
+
+__device__ __forceinline__ bool sg_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }      // false for inf and nan
+
+// One block.  Thread i folds the chunks of parameters i, i + 256, ... in ascending order; the totals are each thread's parameters in
+// ascending order, then the same fixed tree.  Thread 0 advances the control block.
+__global__ __launch_bounds__(256) void step_control_kernel(const double* __restrict__ partial, const int32_t* __restrict__ first_chunk, int P,
+                                                           double* __restrict__ param_sumsq, float max_grad_norm, float beta1, float beta2,
+                                                           mmd_step_ctrl* __restrict__ ctrl) {
+  __shared__ double s_g[256], s_p[256];
+  __shared__ int s_bad[256];
+  const int tid = threadIdx.x;
+  double tg = 0.0, tp = 0.0;
+  int bad = 0x7fffffff;
+  for (int i = tid; i < P; i += 256) {
+    double a = 0.0, b = 0.0;
+    const int c1 = first_chunk[i + 1];
+    for (int c = first_chunk[i]; c < c1; ++c) { a += partial[(int64_t)c * 2]; b += partial[(int64_t)c * 2 + 1]; }
+    param_sumsq[(int64_t)i * 2] = a;
+    param_sumsq[(int64_t)i * 2 + 1] = b;
+    tg += a;
+    tp += b;
+    if (!sg_finite(a) && i < bad) bad = i;
+  }
+  s_g[tid] = tg;
+  s_p[tid] = tp;
+  s_bad[tid] = bad;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) {
+      s_g[tid] += s_g[tid + o];
+      s_p[tid] += s_p[tid + o];
+      s_bad[tid] = min(s_bad[tid], s_bad[tid + o]);
+    }
+    __syncthreads();
+  }
+  if (tid != 0) return;
+  const double gsum = s_g[0], psum = s_p[0];
+  const bool ok = sg_finite(gsum);
+  const float gn = (float)sqrt(gsum), pn = (float)sqrt(psum);
+  ctrl->grad_norm = gn;
+  ctrl->param_norm = pn;
+  ctrl->took_step = ok ? 1 : 0;
+  ctrl->first_bad_param = ok ? -1 : s_bad[0];
+  if (ok) {
+    const int steps = ctrl->steps_taken + 1;
+    ctrl->steps_taken = steps;
+    ctrl->bc1 = (float)(1.0 - pow((double)beta1, (double)steps));
+    ctrl->bc2 = (float)(1.0 - pow((double)beta2, (double)steps));
+    ctrl->clip_coef = (max_grad_norm > 0.f && gn > max_grad_norm) ? max_grad_norm / (gn + 1e-6f) : 1.f;
+    ctrl->cum_grad_norm += sqrt(gsum);
+    ctrl->cum_param_norm += sqrt(psum);
+    ctrl->cum_count += 1;
+  } else {
+    ctrl->clip_coef = 1.f;
+    ctrl->skipped_total += 1;
+    ctrl->last_bad_param = s_bad[0];
+  }
+}
+
+struct EmaSet { float* e[MMD_STEP_MAX_EMA]; float rate[MMD_STEP_MAX_EMA]; };
+// adamw_kernel's arithmetic on g * clip_coef with the bias corrections of the control block; every EMA copy in the same launch.
+__global__ __launch_bounds__(256) void adamw_guarded_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                            float* __restrict__ v, const EmaSet ema, int64_t n, float lr, float beta1, float beta2,
+                                                            float eps, float wd, const mmd_step_ctrl* __restrict__ ctrl) {
+  if (!ctrl->took_step) return;
+  const float clip = ctrl->clip_coef, bc1 = ctrl->bc1, bc2 = ctrl->bc2;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    float w = p[i] * (1.f - lr * wd);
+    const float gi = g[i] * clip;
+    const float mi = beta1 * m[i] + (1.f - beta1) * gi;
+    const float vi = beta2 * v[i] + (1.f - beta2) * gi * gi;
+    m[i] = mi;
+    v[i] = vi;
+    w -= lr * (mi / bc1) / (sqrtf(vi / bc2) + eps);
+    p[i] = w;
+#pragma unroll
+    for (int k = 0; k < MMD_STEP_MAX_EMA; ++k)
+      if (ema.e[k]) ema.e[k][i] = ema.e[k][i] * ema.rate[k] + w * (1.f - ema.rate[k]);
+  }
+}
+
 // ============================================================================= C-ABI
 static inline int ew_grid_b(int64_t total) { return (int)min((int64_t)4096, (total + 255) / 256); }
 
@@ -903,6 +1042,36 @@ extern "C" int mmd_adamw_step(float* p, const float* g, float* m, float* v, floa
   const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
   return mmd_launch<adamw_kernel>("adamw_step", dim3(ew_grid_b(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, n, lr, beta1, beta2, eps, weight_decay,
                                   bc1, bc2, ema_rate);
+}
+
+extern "C" int mmd_step_ctrl_bytes(void) { return (int)sizeof(mmd_step_ctrl); }
+
+extern "C" int mmd_sumsq_chunks(const float* g, const float* p, int64_t n, const int64_t* chunk_lo, const int32_t* chunk_len, int nchunks,
+                                double* partial, void* stream) {
+  MMD_REQUIRE(g && chunk_lo && chunk_len && partial && n > 0 && nchunks > 0, "sumsq_chunks: bad argument");
+  MMD_REQUIRE(((uintptr_t)g | (uintptr_t)p) % 16 == 0 && (uintptr_t)partial % 8 == 0, "sumsq_chunks: unaligned pointer");
+  return mmd_launch<sumsq_chunks_kernel>("sumsq_chunks", dim3(nchunks), dim3(256), 0, (hipStream_t)stream, g, p, n, chunk_lo, chunk_len, partial);
+}
+
+extern "C" int mmd_step_control(const double* partial, const int32_t* param_first_chunk, int P, double* param_sumsq, float max_grad_norm,
+                                float beta1, float beta2, struct mmd_step_ctrl* ctrl, void* stream) {
+  MMD_REQUIRE(partial && param_first_chunk && param_sumsq && ctrl && P > 0, "step_control: bad argument");
+  MMD_REQUIRE(((uintptr_t)partial | (uintptr_t)param_sumsq | (uintptr_t)ctrl) % 8 == 0, "step_control: unaligned pointer");
+  MMD_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, "step_control: betas must be in [0, 1)");
+  return mmd_launch<step_control_kernel>("step_control", dim3(1), dim3(256), 0, (hipStream_t)stream, partial, param_first_chunk, P, param_sumsq,
+                                         max_grad_norm, beta1, beta2, ctrl);
+}
+
+extern "C" int mmd_adamw_step_guarded(float* p, const float* g, float* m, float* v, float* ema0, float* ema1, float* ema2, float* ema3,
+                                      float rate0, float rate1, float rate2, float rate3, int64_t n, float lr, float beta1, float beta2,
+                                      float eps, float weight_decay, const struct mmd_step_ctrl* ctrl, void* stream) {
+  MMD_REQUIRE(p && g && m && v && ctrl && n > 0, "adamw_step_guarded: bad argument");
+  MMD_REQUIRE((uintptr_t)ctrl % 8 == 0, "adamw_step_guarded: unaligned control block");
+  EmaSet ema;
+  ema.e[0] = ema0; ema.e[1] = ema1; ema.e[2] = ema2; ema.e[3] = ema3;
+  ema.rate[0] = rate0; ema.rate[1] = rate1; ema.rate[2] = rate2; ema.rate[3] = rate3;
+  return mmd_launch<adamw_guarded_kernel>("adamw_step_guarded", dim3(ew_grid_b(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, n, lr, beta1,
+                                          beta2, eps, weight_decay, ctrl);
 }
 
 // ----------------------------------------------------------------------------- weight packing for the training step

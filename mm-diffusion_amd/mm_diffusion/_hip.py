@@ -100,6 +100,10 @@ _PROTOS = {
     "mmd_dropout": (i32, [i32, vp, vp, f32, vp, i64, vp]),
     "mmd_mse_grad": (i32, [vp, vp, vp, vp, i32, i64, vp]),
     "mmd_adamw_step": (i32, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, vp]),
+    "mmd_step_ctrl_bytes": (i32, []),
+    "mmd_sumsq_chunks": (i32, [vp, vp, i64, vp, vp, i32, vp, vp]),
+    "mmd_step_control": (i32, [vp, vp, i32, vp, f32, f32, f32, vp, vp]),
+    "mmd_adamw_step_guarded": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, f32, i64, f32, f32, f32, f32, f32, vp, vp]),
     "mmd_q_sample": (i32, [vp, vp, vp, vp, vp, i32, i32, i64, vp]),
     "mmd_vlb_workspace_bytes": (i64, [i32]),
     "mmd_vlb_terms": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp]),

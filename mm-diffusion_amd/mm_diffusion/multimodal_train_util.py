@@ -10,30 +10,60 @@ MI355X-first differences:
     last microbatch (that is also the reference's `no_sync()` behaviour, mtu:300-305), the initial parameter sync one
     broadcast (the reference: DDP with 128 MB buckets + 1046 per-tensor broadcasts)
   * `use_fp16` selects bf16 activations / conv weights with fp32 master parameters: bf16 has fp32's exponent range, so
-    the reference's dynamic loss scaling (fp16_util.py:149-245) has nothing to do and `took_step` is always true
+    the reference's dynamic loss scaling (fp16_util.py:149-245) has nothing to do.  Its other half is kept: with
+    `guard_nonfinite` (the default) the squared norms of the flat gradient and parameters are reduced on the device every
+    step, a step whose gradient holds an inf / nan is skipped - parameters, moments and EVERY EMA copy stay bitwise what they
+    were, `took_step` = 0, the step count does not advance - and `max_grad_norm > 0` clips by the global norm
+    (`clip_grad_norm_`'s rule).  The decision lives in device memory and is read by the optimizer kernel
+    (optim.FlatAdamW(guard=True)), so it costs no host sync and works beside the graph-replayed step; the host reads the
+    control block only on logging steps (`_log_norms`): `grad_norm` / `param_norm` (means over the taken steps since the last
+    read), `current_grad_norm` / `current_param_norm`, `skipped_steps`, and `grad_norm_v` / `grad_norm_a` (see `param_group`)
   * the periodic sample dump (`save_video`, mtu:348-467) samples from the first EMA copy WITHOUT touching the master parameters
     (the reference loads the EMA weights into the model), gathers every rank's samples with one RCCL all-gather per stream and
     writes a png grid of frame strips + wav files (no gif / mp4 muxer in this build)
 Out of scope here (out of the hot path): wandb logging.
 """
 import glob
+import math
 import os
 
 import torch as th
 import torch.distributed as dist
 
 from . import dist_util, logger
+from ._hip import MMDError
 from .optim import FlatAdamW
 from .resample import LossAwareSampler, UniformSampler
 
 
+_AUDIO_PARTS, _VIDEO_PARTS = ("a_norm", "a_qkv"), ("spatial_attention_block", "temporal_attention_block", "v_norm", "v_qkv")
+
+
+def param_group(name):
+    """"video" | "audio" | "shared" for a parameter name of the coupled U-Net (the groups of `grad_norm_v` / `grad_norm_a`; the
+    reference's wandb branch reads these two keys, multimodal_train_util.py:240-241, and never defines them).  The name is split at
+    the dots: audio = a component that starts with `audio_`, or is `a_norm` / `a_qkv` (the audio side of a cross-attention block);
+    video = a component that starts with `video_`, or is `spatial_attention_block`, `temporal_attention_block`, `v_norm` or `v_qkv`;
+    everything else (`time_embed`, the `emb_layers` both streams of a block share) is shared and counts in neither norm."""
+    parts = name.split(".")
+    if any(c.startswith("audio_") or c in _AUDIO_PARTS for c in parts):
+        return "audio"
+    if any(c.startswith("video_") or c in _VIDEO_PARTS for c in parts):
+        return "video"
+    return "shared"
+
+
 class TrainLoop:
+    log_stream_norms = True       # grad_norm_v / grad_norm_a: the coupled U-Net only (the SR loop turns it off)
+
     def __init__(self, *, model, diffusion, data, batch_size, microbatch, ema_rate, log_interval, save_interval, resume_checkpoint,
                  lr=0, t_lr=1e-4, save_type="mp4", use_fp16=False, fp16_scale_growth=1e-3, schedule_sampler=None, weight_decay=0.0,
                  lr_anneal_steps=0, class_cond=False, use_db=False, sample_fn="dpm_solver", num_classes=0, save_row=2, video_fps=16,
-                 audio_fps=16000, use_graph=False):
+                 audio_fps=16000, use_graph=False, guard_nonfinite=True, max_grad_norm=0.0):
         """use_graph (extension): replay forward + backward from one captured graph (train_graph.GraphedTrainStep) when a step is
-        a single microbatch of constant shape; ~10 % faster at per-GPU batch 8, identical gradients."""
+        a single microbatch of constant shape; ~10 % faster at per-GPU batch 8, identical gradients.
+        guard_nonfinite / max_grad_norm (extension): the on-device step guard of the module docstring; False / 0 is the
+        unguarded one-launch AdamW step, which logs no norms."""
         self.model, self.diffusion, self.data = model, diffusion, data
         self.save_type = save_type
         self.batch_size = batch_size
@@ -55,9 +85,14 @@ class TrainLoop:
         if use_db:
             raise NotImplementedError("wandb logging (use_db) is not built")
         self._load_and_sync_parameters()
+        self.guard_nonfinite, self.max_grad_norm = bool(guard_nonfinite), float(max_grad_norm)
+        if self.max_grad_norm > 0 and not self.guard_nonfinite:
+            raise ValueError("max_grad_norm needs guard_nonfinite=True: the clip coefficient comes from the guard's on-device norm")
         self.opt = FlatAdamW(self.model.parameters(), lr=self.lr, weight_decay=self.weight_decay, ema_rates=self.ema_rate,
-                             pack_dtype=getattr(self.model, "dtype", None))
+                             pack_dtype=getattr(self.model, "dtype", None), guard=self.guard_nonfinite, max_grad_norm=self.max_grad_norm)
         self._names = [n for n, p in self.model.named_parameters() if p.requires_grad]
+        self._norm_prev = None        # control block at the previous _log_norms() read, and the step it was read at
+        self.last_skip_message = None
         if self.resume_step:
             self._load_optimizer_state()
             for i, rate in enumerate(self.ema_rate):
@@ -117,9 +152,10 @@ class TrainLoop:
         """th.optim.AdamW-shaped state dict ({'state': {i: {step, exp_avg, exp_avg_sq}}, 'param_groups': [...]}) so the
         reference's `opt.load_state_dict` accepts it (mtu:207-220); parameter order = model.parameters()."""
         state, off = {}, 0
+        steps = self.opt.steps                                # the steps TAKEN (guarded: one read of the control block)
         for i, p in enumerate(self.opt.params):
             k = p.numel()
-            state[i] = {"step": th.tensor(float(self.opt.steps)), "exp_avg": self.opt.m[off:off + k].view_as(p).clone(),
+            state[i] = {"step": th.tensor(float(steps)), "exp_avg": self.opt.m[off:off + k].view_as(p).clone(),
                         "exp_avg_sq": self.opt.v[off:off + k].view_as(p).clone()}
             off += k
         group = {"lr": self.opt.lr, "betas": self.opt.betas, "eps": self.opt.eps, "weight_decay": self.opt.weight_decay, "amsgrad": False,
@@ -128,15 +164,17 @@ class TrainLoop:
         return {"state": state, "param_groups": [group]}
 
     def load_opt_state_dict(self, sd):
-        off = 0
+        off, steps = 0, None
         for i, p in enumerate(self.opt.params):
             k = p.numel()
             st = sd["state"].get(i)
             if st is not None:
                 self.opt.m[off:off + k].copy_(st["exp_avg"].reshape(-1).float())
                 self.opt.v[off:off + k].copy_(st["exp_avg_sq"].reshape(-1).float())
-                self.opt.steps = int(st["step"])
+                steps = int(st["step"])
             off += k
+        if steps is not None:
+            self.opt.steps = steps
 
     # ------------------------------------------------------------------ loop
     def run_loop(self):
@@ -162,10 +200,11 @@ class TrainLoop:
         t, weights = self.schedule_sampler.sample(batch["video"].shape[0], dist_util.dev())
         losses = self._gstep.step(batch, t, weights)          # zero_grad + forward + backward replayed, then all-reduce + AdamW/EMA
         if isinstance(self.schedule_sampler, LossAwareSampler):
-            self.schedule_sampler.update_with_local_losses(t, losses["loss"])
+            self.schedule_sampler.update_with_local_losses(*finite_pairs(t, losses["loss"]))
         log_loss_dict(self.diffusion, t, {k: v * weights for k, v in losses.items()})
         self._anneal_lr()
         self.log_step()
+        self._log_norms()
         return losses
 
     def run_step(self, batch, cond={}):
@@ -177,6 +216,7 @@ class TrainLoop:
         self.opt.step()                                       # AdamW + every EMA copy
         self._anneal_lr()
         self.log_step()
+        self._log_norms()
         return loss
 
     def forward_backward(self, batch, cond):
@@ -193,7 +233,7 @@ class TrainLoop:
                 self.opt.arm_overlap()                        # (the reference: DDP buckets + no_sync() on the earlier ones, mtu:289-319)
             loss.backward()                                   # accumulates straight into the flat gradient buffer
         if isinstance(self.schedule_sampler, LossAwareSampler):
-            self.schedule_sampler.update_with_local_losses(t, losses["loss"].detach())
+            self.schedule_sampler.update_with_local_losses(*finite_pairs(t, losses["loss"].detach()))
         log_loss_dict(self.diffusion, t, {k: v * weights for k, v in losses.items()})
         return losses
 
@@ -206,6 +246,43 @@ class TrainLoop:
     def log_step(self):
         logger.logkv("step", self.step + self.resume_step)
         logger.logkv("samples", (self.step + self.resume_step + 1) * self.global_batch)
+
+    def _log_norms(self):
+        """The reference's norm logging (fp16_util.py:188-236) from the optimizer's device control block, read ONLY on the steps that
+        are logged (`step % log_interval == 0`): `grad_norm` / `param_norm` = means over the steps taken since the previous read
+        (differences of the never-reset device sums), `current_*` = this step's, `skipped_steps` = the total; for the coupled
+        U-Net also `grad_norm_v` / `grad_norm_a`, this step's gradient norm over the video / audio parameters (`param_group`).
+        Steps skipped since the previous read are reported in one log line; a non-finite PARAMETER norm raises."""
+        if not self.guard_nonfinite or self.step % self.log_interval != 0:
+            return
+        c = self.opt.read_control()
+        prev, at = self._norm_prev or ({"cum_grad_norm": 0.0, "cum_param_norm": 0.0, "cum_count": 0, "skipped_total": 0}, 0)
+        self._norm_prev = (c, self.step + self.resume_step)
+        if not math.isfinite(c["param_norm"]):
+            raise MMDError(f"step {self.step + self.resume_step}: the parameter norm is {c['param_norm']} - the parameters hold an inf / nan "
+                           "(a poisoned checkpoint?); no later step can repair them")
+        taken = c["cum_count"] - prev["cum_count"]
+        logger.logkv("grad_norm", (c["cum_grad_norm"] - prev["cum_grad_norm"]) / taken if taken else c["grad_norm"])
+        logger.logkv("param_norm", (c["cum_param_norm"] - prev["cum_param_norm"]) / taken if taken else c["param_norm"])
+        logger.logkv("current_grad_norm", c["grad_norm"])
+        logger.logkv("current_param_norm", c["param_norm"])
+        logger.logkv("skipped_steps", c["skipped_total"])
+        if self.log_stream_norms:
+            if not hasattr(self, "_stream_masks"):
+                groups = [param_group(n) for n in self._names]
+                self._stream_masks = [th.tensor([g == which for g in groups], dtype=th.float64, device=self.opt.param_sumsq.device)
+                                      for which in ("video", "audio")]
+            gsq = self.opt.param_sumsq[:, 0]
+            v, a = th.stack([(gsq * m).sum() for m in self._stream_masks]).sqrt().tolist()      # one more device-to-host copy
+            logger.logkv("grad_norm_v", v)
+            logger.logkv("grad_norm_a", a)
+        skipped = c["skipped_total"] - prev["skipped_total"]
+        if skipped:
+            bad = c["last_bad_param"]
+            name = self._names[bad] if 0 <= bad < len(self._names) else "?"
+            self.last_skip_message = (f"skipped {skipped} optimizer step(s) in steps {at + 1}..{self.step + self.resume_step}: non-finite "
+                                      f"gradient, last seen in {name} (parameter {bad}); parameters, moments and EMA copies were left unchanged")
+            logger.log(self.last_skip_message)
 
     def save_video(self):
         """Periodic sample dump (mtu:348-467): save_row^2 video+audio pairs from the first EMA copy with the configured sampler
@@ -319,6 +396,13 @@ def find_ema_checkpoint(main_checkpoint, step, rate):
         return None
     path = os.path.join(os.path.dirname(main_checkpoint), f"ema_{rate}_{step:06d}.pt")
     return path if os.path.exists(path) else None
+
+
+def finite_pairs(ts, losses):
+    """The (t, loss) pairs with a finite loss: what the loss-aware sampler may remember (a skipped step's inf / nan would poison its
+    loss-second-moment history for good)."""
+    keep = th.isfinite(losses.detach().reshape(-1))
+    return ts.reshape(-1)[keep], losses.detach().reshape(-1)[keep]
 
 
 def log_loss_dict(diffusion, ts, losses):

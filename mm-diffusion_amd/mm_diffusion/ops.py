@@ -1201,6 +1201,34 @@ def adamw_step(p, g, m, v, ema, lr, beta1, beta2, eps, weight_decay, step, ema_r
               float(beta2), float(eps), float(weight_decay), int(step), float(ema_rate), meta=("adamw", 0, 28 * p.numel()))
 
 
+def sumsq_chunks(g, p, chunk_lo, chunk_len, partial):
+    """partial [nchunks, 2] fp64 = (sum g^2, sum p^2) over each chunk of the flat fp32 buffers (include/mmd.h: mmd_sumsq_chunks); p may be None."""
+    H.require_cuda(g, p, chunk_lo, chunk_len, partial)
+    _dispatch("mmd_sumsq_chunks", g.data_ptr(), H.ptr(p), g.numel(), chunk_lo.data_ptr(), chunk_len.data_ptr(), chunk_lo.numel(), partial.data_ptr(),
+              meta=("sumsq_chunks", 0, (4 if p is None else 8) * g.numel()))
+    return partial
+
+
+def step_control(partial, param_first_chunk, param_sumsq, max_grad_norm, beta1, beta2, ctrl):
+    """Fold the chunk sums per parameter and advance the step control block (include/mmd.h: mmd_step_control, struct mmd_step_ctrl)."""
+    H.require_cuda(partial, param_first_chunk, param_sumsq, ctrl)
+    _dispatch("mmd_step_control", partial.data_ptr(), param_first_chunk.data_ptr(), param_first_chunk.numel() - 1, param_sumsq.data_ptr(),
+              float(max_grad_norm), float(beta1), float(beta2), ctrl.data_ptr(), meta=("step_control", 0, 16 * partial.shape[0]))
+    return ctrl
+
+
+def adamw_step_guarded(p, g, m, v, emas, rates, lr, beta1, beta2, eps, weight_decay, ctrl):
+    """AdamW + every EMA copy (at most 4) in one launch, on g * clip_coef, skipped entirely when the control block says so
+    (include/mmd.h: mmd_adamw_step_guarded)."""
+    if len(emas) > 4 or len(emas) != len(rates):
+        raise H.MMDError("adamw_step_guarded: at most 4 EMA copies, one rate each")
+    H.require_cuda(p, g, m, v, ctrl, *emas)
+    ep = [e.data_ptr() for e in emas] + [None] * (4 - len(emas))
+    er = [float(r) for r in rates] + [0.0] * (4 - len(rates))
+    _dispatch("mmd_adamw_step_guarded", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), *ep, *er, p.numel(), float(lr), float(beta1),
+              float(beta2), float(eps), float(weight_decay), ctrl.data_ptr(), meta=("adamw_guarded", 0, (28 + 8 * len(emas)) * p.numel()))
+
+
 def timestep_embedding(t, dim, out):
     _dispatch("mmd_timestep_embedding", t.data_ptr(), _t_kind(t), t.shape[0], dim, out.data_ptr())
     return out

@@ -1,7 +1,8 @@
 """Flat-buffer AdamW + EMA for the training step (reference: th.optim.AdamW in TrainLoop, multimodal_train_util.py:151-160,
 EMA update nn.py:128-138).  All parameters live as views of ONE fp32 buffer, so the optimizer step is one kernel launch
 (mmd_adamw_step) and the data-parallel gradient all-reduce is one RCCL call on one flat buffer (the reference's DDP
-issues 5 buckets; its sync_params 1046 broadcasts)."""
+issues 5 buckets; its sync_params 1046 broadcasts).  With guard=True the step is three launches: squared norms per chunk, the
+skip / clip decision into a device control block, AdamW + every EMA copy reading it (the reference: fp16_util.py:188-236)."""
 import ctypes
 
 import torch
@@ -96,16 +97,72 @@ class WeightPacker:
                    H.stream_handle())
 
 
+STEP_CHUNK = 16384      # include/mmd.h: MMD_STEP_CHUNK, the longest chunk of the step guard's chunk table
+MAX_GUARD_EMA = 4       # include/mmd.h: MMD_STEP_MAX_EMA
+
+
+class StepCtrl(ctypes.Structure):
+    """include/mmd.h: struct mmd_step_ctrl (64 bytes of device memory, advanced by mmd_step_control)."""
+    _fields_ = [("cum_grad_norm", ctypes.c_double), ("cum_param_norm", ctypes.c_double), ("cum_count", ctypes.c_int64),
+                ("grad_norm", ctypes.c_float), ("param_norm", ctypes.c_float), ("clip_coef", ctypes.c_float), ("bc1", ctypes.c_float),
+                ("bc2", ctypes.c_float), ("took_step", ctypes.c_int32), ("steps_taken", ctypes.c_int32), ("skipped_total", ctypes.c_int32),
+                ("first_bad_param", ctypes.c_int32), ("last_bad_param", ctypes.c_int32)]
+
+
+def new_step_ctrl(device):
+    """A fresh control block in device memory (an int32 tensor over the struct's 64 bytes): no step taken or skipped yet."""
+    if H.lib().mmd_step_ctrl_bytes() != ctypes.sizeof(StepCtrl):
+        raise H.MMDError("struct mmd_step_ctrl: the library and optim.StepCtrl disagree on its size")
+    init = StepCtrl(clip_coef=1.0, bc1=1.0, bc2=1.0, first_bad_param=-1, last_bad_param=-1)
+    return torch.frombuffer(bytearray(bytes(init)), dtype=torch.int32).to(device)
+
+
+def read_step_ctrl(ctrl):
+    """The control block as a dict, in ONE device-to-host copy."""
+    c = StepCtrl.from_buffer_copy(ctrl.cpu().numpy().tobytes())
+    return {name: getattr(c, name) for name, _ in StepCtrl._fields_}
+
+
+def chunk_table(sizes, chunk_len=STEP_CHUNK):
+    """The static chunk table of the step guard for parameters of `sizes` elements laid out back to back: chunks tile [0, sum(sizes)),
+    are cut at every parameter boundary and hold at most chunk_len elements.  Returns numpy arrays (chunk_lo int64 [nchunks],
+    chunk_len int32 [nchunks], param_first_chunk int32 [P + 1]); parameter i owns chunks param_first_chunk[i] .. [i + 1] - 1."""
+    import numpy as np
+    chunk_len = int(chunk_len)
+    if chunk_len <= 0:
+        raise ValueError("chunk_len must be positive")
+    los, lens, first, off = [], [], [0], 0
+    for k in sizes:
+        k = int(k)
+        starts = np.arange(0, k, chunk_len, dtype=np.int64)
+        los.append(off + starts)
+        lens.append(np.minimum(chunk_len, k - starts).astype(np.int32))
+        first.append(first[-1] + len(starts))
+        off += k
+    lo = np.concatenate(los) if los else np.zeros(0, dtype=np.int64)
+    ln = np.concatenate(lens) if lens else np.zeros(0, dtype=np.int32)
+    return lo.astype(np.int64), ln.astype(np.int32), np.asarray(first, dtype=np.int32)
+
+
 class FlatAdamW:
     def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, ema_rates=(), pack_dtype=None, grad_buckets=4,
-                 grad_payload="fp32"):
+                 grad_payload="fp32", guard=False, max_grad_norm=0.0):
         """pack_dtype: the model's activation dtype (model.dtype) - enables the one-launch conv-weight re-pack after every step.
         grad_buckets: the flat gradient is reduced over the ranks in this many contiguous buckets (parameter order = forward order,
         so backward completes the LAST bucket first); with overlap armed (arm_overlap) a bucket's all-reduce is issued on a side
         stream as soon as the backward has passed its last parameter, under the rest of the backward (the reference: DDP with
-        128 MB buckets, multimodal_train_util.py:127-136).  grad_payload "bf16": buckets travel as bf16 (half the xGMI bytes)."""
+        128 MB buckets, multimodal_train_util.py:127-136).  grad_payload "bf16": buckets travel as bf16 (half the xGMI bytes).
+        guard (device tensors only): step() first reduces the squared norms of the flat gradient and parameters on the device
+        (mmd_sumsq_chunks + mmd_step_control), and the optimizer kernel (mmd_adamw_step_guarded: AdamW and EVERY EMA copy) reads the
+        decision from device memory - a step whose gradient holds an inf / nan changes nothing, and with max_grad_norm > 0 the gradient
+        is scaled by the clip_grad_norm_ coefficient.  step() makes no host read; read_control() / grad_param_norms() do."""
         self.params = [p for p in params if p.requires_grad]
         dev = self.params[0].device
+        self.guard, self.max_grad_norm = bool(guard), float(max_grad_norm)
+        if self.guard and dev.type != "cuda":
+            raise H.MMDError("FlatAdamW(guard=True) needs device tensors: the step guard runs in libmmd, there is no CPU fallback")
+        if self.guard and len(list(ema_rates)) > MAX_GUARD_EMA:
+            raise H.MMDError(f"FlatAdamW(guard=True) updates at most {MAX_GUARD_EMA} EMA copies in its one launch")
         n = sum(p.numel() for p in self.params)
         self.flat = torch.empty(n, dtype=torch.float32, device=dev)
         self.grad = torch.zeros(n, dtype=torch.float32, device=dev)
@@ -121,7 +178,14 @@ class FlatAdamW:
         self.ema_rates = list(ema_rates)
         self.ema_params = [self.flat.clone() for _ in self.ema_rates]
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
-        self.steps = 0
+        self._steps = 0
+        if self.guard:
+            lo, ln, first = chunk_table([p.numel() for p in self.params])
+            self.chunk_lo, self.chunk_len = torch.from_numpy(lo).to(dev), torch.from_numpy(ln).to(dev)
+            self.param_first_chunk = torch.from_numpy(first).to(dev)
+            self.partial = torch.zeros(len(lo), 2, dtype=torch.float64, device=dev)
+            self.param_sumsq = torch.zeros(len(self.params), 2, dtype=torch.float64, device=dev)
+            self.ctrl = new_step_ctrl(dev)
         # ---- gradient buckets: contiguous ranges of the flat buffer cut at parameter boundaries, ~equal sizes
         sizes = [p.numel() for p in self.params]
         nb = max(1, min(int(grad_buckets), len(self.params)))
@@ -141,6 +205,34 @@ class FlatAdamW:
         for i, p in enumerate(self.params):
             p._mmd_opt = (self, i)                     # train_ops._grad_slot reports "this parameter's gradient kernel is enqueued"
         self.packer = WeightPacker(self.params, pack_dtype, self.bucket_of) if pack_dtype is not None and self.params[0].is_cuda else None
+
+    # ------------------------------------------------------------------ step count / control block
+    _STEPS_WORD = StepCtrl.steps_taken.offset // 4
+
+    @property
+    def steps(self):
+        """Optimizer steps TAKEN (an int).  Guarded: read from the device control block (one small device-to-host copy)."""
+        if self.guard:
+            return int(self.ctrl[self._STEPS_WORD].item())
+        return self._steps
+
+    @steps.setter
+    def steps(self, value):
+        self._steps = int(value)
+        if self.guard:
+            self.ctrl[self._STEPS_WORD:self._STEPS_WORD + 1].fill_(int(value))
+
+    def read_control(self):
+        """The control block (struct mmd_step_ctrl) as a dict, in ONE device-to-host copy."""
+        if not self.guard:
+            raise H.MMDError("read_control: this FlatAdamW was built with guard=False")
+        return read_step_ctrl(self.ctrl)
+
+    def grad_param_norms(self):
+        """fp64 [P, 2] on the device: (gradient norm, parameter norm) of every parameter as of the latest step()."""
+        if not self.guard:
+            raise H.MMDError("grad_param_norms: this FlatAdamW was built with guard=False")
+        return self.param_sumsq.sqrt()
 
     def zero_grad(self):
         self.grad.zero_()
@@ -257,17 +349,23 @@ class FlatAdamW:
 
     def step(self):
         self.fold_grads()             # no-op when all_reduce_grads already folded (the accumulators are cleared by the fold)
-        self.steps += 1
         # autograd accumulates into p.grad in place, so self.grad already holds the flat gradient
         lo, hi = self.grad.data_ptr(), self.grad.data_ptr() + self.grad.numel() * 4
         for p in self.params:
             if p.grad is None or not (lo <= p.grad.data_ptr() < hi):
                 raise RuntimeError("a parameter's .grad was replaced or dropped; FlatAdamW needs in-place gradient accumulation")
-        ema0 = self.ema_params[0] if self.ema_params else None
-        ops.adamw_step(self.flat, self.grad, self.m, self.v, ema0, self.lr, self.betas[0], self.betas[1], self.eps,
-                       self.weight_decay, self.steps, ema_rate=self.ema_rates[0] if self.ema_rates else 0.0)
-        for rate, ema in zip(self.ema_rates[1:], self.ema_params[1:]):
-            ema.mul_(rate).add_(self.flat, alpha=1 - rate)
+        if self.guard:                # norms -> decision in device memory -> AdamW + every EMA copy, or nothing at all
+            ops.sumsq_chunks(self.grad, self.flat, self.chunk_lo, self.chunk_len, self.partial)
+            ops.step_control(self.partial, self.param_first_chunk, self.param_sumsq, self.max_grad_norm, self.betas[0], self.betas[1], self.ctrl)
+            ops.adamw_step_guarded(self.flat, self.grad, self.m, self.v, self.ema_params, self.ema_rates, self.lr, self.betas[0], self.betas[1],
+                                   self.eps, self.weight_decay, self.ctrl)
+        else:
+            self._steps += 1
+            ema0 = self.ema_params[0] if self.ema_params else None
+            ops.adamw_step(self.flat, self.grad, self.m, self.v, ema0, self.lr, self.betas[0], self.betas[1], self.eps,
+                           self.weight_decay, self._steps, ema_rate=self.ema_rates[0] if self.ema_rates else 0.0)
+            for rate, ema in zip(self.ema_rates[1:], self.ema_params[1:]):
+                ema.mul_(rate).add_(self.flat, alpha=1 - rate)
         if self.packer is not None:
             self.packer.refresh()
         self._folded = False
@@ -276,3 +374,4 @@ class FlatAdamW:
         bump = getattr(torch._C, "_increment_version", None)
         if bump is not None:
             bump(self.params)      # ONE call on the list: handed a single tensor it iterates over it (unbind per row: 0.27 s per step)
+

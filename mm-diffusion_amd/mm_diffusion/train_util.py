@@ -4,7 +4,8 @@ microbatched forward / backward of `diffusion.training_losses(model, batch, t, m
 EMA copies, lr anneal, `modelNNNNNN.pt` / `ema_<rate>_NNNNNN.pt` / `optNNNNNN.pt` checkpoints with the reference's keys, and resume.
 
 Everything but the batch handling is multimodal_train_util.TrainLoop (flat fp32 parameter / gradient / moment buffers, one-kernel
-AdamW + EMA, one all-reduce per step, bf16 activations without loss scaling); this class only replaces what depends on the batch
+AdamW + EMA, one all-reduce per step, bf16 activations without loss scaling, the on-device non-finite skip / norm logging /
+clipping of `guard_nonfinite` and `max_grad_norm`); this class only replaces what depends on the batch
 being one image tensor instead of a {"video", "audio"} dict.
 
 Deviation from the reference, on purpose: its `forward_backward` returns from INSIDE the microbatch loop (train_util.py:380), so
@@ -20,15 +21,17 @@ import torch.distributed as dist
 
 from . import dist_util, logger
 from .multimodal_train_util import (TrainLoop as _MultimodalTrainLoop, find_ema_checkpoint, find_resume_checkpoint,  # noqa: F401
-                                    get_blob_logdir, log_loss_dict, parse_resume_step_from_filename)
+                                    finite_pairs, get_blob_logdir, log_loss_dict, parse_resume_step_from_filename)
 from .resample import LossAwareSampler
 
 
 class TrainLoop(_MultimodalTrainLoop):
+    log_stream_norms = False      # one image stream: no grad_norm_v / grad_norm_a
+
     def __init__(self, *, model, diffusion, data, batch_size, microbatch, ema_rate, log_interval, save_interval, resume_checkpoint,
                  lr=0, t_lr=1e-4, train_type=None, save_type="png", use_fp16=False, fp16_scale_growth=1e-3, schedule_sampler=None,
                  weight_decay=0.0, lr_anneal_steps=0, class_cond=False, use_db=False, sample_fn="ddpm", audio_fps=16000, num_classes=0,
-                 save_row=8):
+                 save_row=8, guard_nonfinite=True, max_grad_norm=0.0):
         if class_cond:
             raise NotImplementedError("class-conditional SR training is not built")
         self.train_type = train_type
@@ -37,7 +40,8 @@ class TrainLoop(_MultimodalTrainLoop):
                          log_interval=log_interval, save_interval=save_interval, resume_checkpoint=resume_checkpoint, lr=lr, t_lr=t_lr,
                          save_type=save_type, use_fp16=use_fp16, fp16_scale_growth=fp16_scale_growth, schedule_sampler=schedule_sampler,
                          weight_decay=weight_decay, lr_anneal_steps=lr_anneal_steps, class_cond=class_cond, use_db=use_db,
-                         sample_fn=sample_fn, num_classes=num_classes, save_row=save_row, audio_fps=audio_fps, use_graph=False)
+                         sample_fn=sample_fn, num_classes=num_classes, save_row=save_row, audio_fps=audio_fps, use_graph=False,
+                         guard_nonfinite=guard_nonfinite, max_grad_norm=max_grad_norm)
 
     def run_loop(self):
         while not self.lr_anneal_steps or self.step + self.resume_step < self.lr_anneal_steps:
@@ -68,7 +72,7 @@ class TrainLoop(_MultimodalTrainLoop):
             ts, weights = self.schedule_sampler.sample(micro.shape[0], dev)
             losses = self.diffusion.training_losses(self.model, micro, ts, model_kwargs=micro_cond)
             if isinstance(self.schedule_sampler, LossAwareSampler):
-                self.schedule_sampler.update_with_local_losses(ts, losses["loss"].detach())
+                self.schedule_sampler.update_with_local_losses(*finite_pairs(ts, losses["loss"].detach()))
             loss = (losses["loss"] * weights).mean() * (micro.shape[0] / n)
             log_loss_dict(self.diffusion, ts, {k: v * weights for k, v in losses.items()})
             if i + self.microbatch >= n:                      # last microbatch: gradient buckets are reduced while it is still running

@@ -3,7 +3,11 @@
 2 ResBlocks per level, attention at ds 8 / 16 / 32, learned sigma, FiLM; 311.0 M parameters), timed eager and warm:
 diffusion.training_losses forward + backward + flat AdamW / EMA at per-GPU batch --batch (6 in the script), bf16 activations.
 
-    python tools/sr_train_bench.py [--batch 6] [--steps 10] [--warmup 3] [--dtype bf16] [--no-breakdown]
+    python tools/sr_train_bench.py [--batch 6] [--steps 10] [--warmup 3] [--dtype bf16] [--no-breakdown] [--guard {0,1}]
+
+--guard 1 times the step with the on-device step guard (FlatAdamW(guard=True): mmd_sumsq_chunks + mmd_step_control +
+mmd_adamw_step_guarded in place of mmd_adamw_step); 0, the default, is the unguarded step.  For an A/B run both arms in one job, one
+process per arm; the breakdown lists the three launches by name.
 
 Prints one JSON line: median / min / max step time over --steps steps (each step fenced by a device synchronize), images per second,
 and - from ONE extra step in which every libmmd entry point is bracketed by HIP events on the launch stream - the time per entry point
@@ -79,6 +83,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--dtype", choices=["bf16", "fp32"], default="bf16")
     ap.add_argument("--no-breakdown", action="store_true")
+    ap.add_argument("--guard", type=int, choices=[0, 1], default=0)
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -94,7 +99,7 @@ def main():
     model.load_state_dict({k: synth_tensor(k, v.shape) for k, v in model.state_dict().items()})
     model.to(dev).train()
     nparam = sum(p.numel() for p in model.parameters())
-    opt = FlatAdamW(model.parameters(), lr=1e-4, weight_decay=0.0, ema_rates=[0.9999], pack_dtype=model.dtype)
+    opt = FlatAdamW(model.parameters(), lr=1e-4, weight_decay=0.0, ema_rates=[0.9999], pack_dtype=model.dtype, guard=bool(args.guard))
     g = torch.Generator().manual_seed(4321)
     torch.manual_seed(4321)
     B, L, S = args.batch, d["large_size"], d["small_size"]
@@ -123,7 +128,7 @@ def main():
         times.append(1000.0 * (time.perf_counter() - t0))
     med = statistics.median(times)
     res = {"metric": "SR training step (training_losses fwd + bwd + AdamW/EMA), 64 -> 256, eager", "ms_per_step_median": med,
-           "ms_per_step_min": min(times), "ms_per_step_max": max(times), "steps": args.steps, "warmup": args.warmup, "batch": B,
+           "ms_per_step_min": min(times), "ms_per_step_max": max(times), "steps": args.steps, "warmup": args.warmup, "batch": B, "guard": args.guard,
            "images_per_s": 1000.0 * B / med, "dtype": args.dtype, "parameters_M": nparam / 1e6, "loss_finite": bool(torch.isfinite(loss)),
            "peak_memory_GB": torch.cuda.max_memory_allocated() / 2 ** 30, "data": "synthetic", "weights": "key-seeded synthetic (mm_diffusion.synth)"}
     if not args.no_breakdown:
