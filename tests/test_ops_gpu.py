@@ -4,7 +4,10 @@ Tolerances (rel-L2 against the fp32 CPU oracle on the same inputs):
   fp32 kernels : 2e-5   (exact-fp32 MFMA / fp32 VALU; differences are summation order only)
   bf16 kernels : 1e-2   (inputs are rounded to bf16 first and the oracle sees the ROUNDED values, so the
                          budget covers bf16 output rounding + bf16 P in the attention MFMA only)
-Index/window/padding errors produce O(1) errors, far above either bound.
+Index/window/padding errors produce O(1) errors in the elements they touch; the whole-tensor rel-L2 used here sees them only when
+they touch many - an error confined to a few rows, one border or one tap, or a small systematic one, stays below either bound
+(tests/test_errbound_cpu.py shows four such defects passing 1e-2).  tests/test_elementwise_gpu.py checks the conv-GEMM and attention
+kernels element by element.
 """
 import math
 import os
