@@ -333,7 +333,9 @@ int mmd_gn_bwd(int dtype, const void* x, int64_t ldx, const void* dy, int64_t ld
                float* dbeta, float* dfilm, int64_t dfilm_ld, float* workspace, void* stream);
 /* The same with a CALLER-KEPT workspace whose first S*C*2 floats are zero on entry; they are zero again on exit (the parameter stage
  * clears what it read), so the fill launch in front of every norm's backward is gone (243 per training step, mtu:280-330).  One
- * workspace per stream; zero it once after allocation. */
+ * workspace per stream and per value of S*C; zero it once after allocation.  The group means are left behind the accumulators, at
+ * workspace + S*C*2: a kept workspace may be reused only for calls with the same S*C (a call with another S*C and the same total
+ * length S*(2C+64) would accumulate onto those means). */
 int mmd_gn_bwd_ws0(int dtype, const void* x, int64_t ldx, const void* dy, int64_t lddy, void* dx, int64_t lddx, int64_t rows, int C, int S,
                    int Tn, int inner, int64_t outer_stride, int64_t inner_stride, int64_t tstride, const float* a, const float* b,
                    const float* mr, const float* gamma, const float* beta, const float* film, int64_t film_ld, int act, float* dgamma,

@@ -1000,7 +1000,9 @@ extern "C" int mmd_gn_bwd(int dtype, const void* x, int64_t ldx, const void* dy,
                      film_ld, act, dgamma, dbeta, dfilm, dfilm_ld, workspace, stream, false);
 }
 // The same with a workspace the CALLER keeps: its first S * C * 2 floats are zero on entry and zero again on exit (the parameter stage
-// clears what it has read), so a training step's 243 norms do not pay a fill launch each.  One workspace per stream.
+// clears what it has read), so a training step's 243 norms do not pay a fill launch each.  One workspace per stream AND per S * C:
+// the group means live behind the accumulators, at workspace + S * C * 2, and are NOT cleared, so a buffer of the same total length
+// handed to a norm with another S * C (S = 6, C = 32 and S = 2, C = 160 are both 768 floats) is not zero where that norm accumulates.
 extern "C" int mmd_gn_bwd_ws0(int dtype, const void* x, int64_t ldx, const void* dy, int64_t lddy, void* dx, int64_t lddx, int64_t rows, int C,
                               int S, int Tn, int inner, int64_t outer_stride, int64_t inner_stride, int64_t tstride, const float* a,
                               const float* b, const float* mr, const float* gamma, const float* beta, const float* film, int64_t film_ld,

@@ -1111,7 +1111,9 @@ def conv_wgrad(dy, x, dW, db, taps, dims, torch_layout=False):
               meta=("conv_wgrad", 2 * dy.shape[0] * dy.shape[1] * x.shape[1] * nt, 0))
 
 
-# GroupNorm backward workspaces kept zero between calls (mmd_gn_bwd_ws0): one per (device, launch stream, size); MMD_GN_BWD_WS0=0 = the
+# GroupNorm backward workspaces kept zero between calls (mmd_gn_bwd_ws0): one per (device, launch stream, S * C, size) - the kernel leaves
+# the FIRST S * C * 2 floats zero and the S * 64 group means behind them, so two norms of equal size but different S * C (S = 6, C = 32 and
+# S = 2, C = 160 are both 768 floats) must not share one: the second would start from the first one's means; MMD_GN_BWD_WS0=0 = the
 # per-call workspace with its fill launch (A/B)
 _GN_BWD_WS0 = _flag("MMD_GN_BWD_WS0")
 _gn_bwd_ws = {}
@@ -1122,7 +1124,7 @@ def gn_bwd(x, dy, dx, geom: Geom, a, b, mr, gamma, beta, film, act, dgamma, dbet
     C = x.shape[1]
     n = geom.S * C * 2 + geom.S * 64
     if _GN_BWD_WS0 and _recorder is None:
-        key = (str(x.device), H.stream_handle(), n)
+        key = (str(x.device), H.stream_handle(), geom.S * C, n)
         ws = _gn_bwd_ws.get(key)
         if ws is None:
             ws = _gn_bwd_ws[key] = torch.zeros(n, dtype=torch.float32, device=x.device)

@@ -1,6 +1,13 @@
 """Backward kernels (training step) through the C-ABI against torch autograd of the oracle's fp32 primitives.
 
-Tolerances: fp32 kernels rel-L2 <= 5e-5 (fp32 atomics order), bf16 <= 2e-2 (bf16 activations/grad tensors, fp32 accumulate).
+What this file proves: the autograd wrappers of train_ops wire every backward kernel to the right operands - layouts, geometries,
+window arithmetic, parameter gradients landing on the parameters - at one shape per op, as a WHOLE-TENSOR rel-L2 against torch's own
+backward in fp32: <= 5e-5 for the fp32 kernels (fp32 atomics order), <= 2e-2 in bf16 (bf16 activations / gradient tensors, fp32
+accumulation).  A rel-L2 of 1e-2 cannot see an error confined to one border, tap, row split, tile or head, nor a second rounding:
+tests/test_errbound_bwd_cpu.py shows seeded defects of that kind passing these tolerances.  The kernels themselves - every row split
+and block order of the weight gradient, both layouts, the GroupNorm thread shapes, the attention tiles, windows and head widths -
+meet a float64 reference element by element, with zero violations allowed, in tests/test_elementwise_bwd_gpu.py (bounds:
+tests/errbound_bwd.py).
 """
 import pytest
 import torch
