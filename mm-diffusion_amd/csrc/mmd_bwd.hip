@@ -694,7 +694,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
 }
 
 // ----------------------------------------------------------------------------- training step guard (include/mmd.h: mmd_step_ctrl)
-// Three launches in stream order, the reduction pattern of loss_terms_kernel / loss_finalize_kernel (mmd_misc.hip): per-block partials
+// Three launches in stream order, the reduction pattern of loss_terms_kernel / loss_finalize_kernel (mmd_diffusion.hip): per-block partials
 // in double, folded in ascending order by a second launch.  No block waits for or signals another one.
 // One block per chunk: every thread sums its elements in ascending order, then a fixed tree over the 256 threads.  The chunk start is
 // only element aligned (chunks are cut at parameter boundaries): up to 3 head elements, 16-byte vectors, up to 3 tail elements.
@@ -741,11 +741,7 @@ __global__ __launch_bounds__(256) void sumsq_chunks_kernel(const float* __restri
   }
   s_g[tid] = sg;
   s_p[tid] = sp;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) { s_g[tid] += s_g[tid + o]; s_p[tid] += s_p[tid + o]; }
-    __syncthreads();
-  }
+  block_tree_sum256(tid, s_g, s_p);
   if (tid == 0) {
     partial[(int64_t)blockIdx.x * 2] = s_g[0];
     partial[(int64_t)blockIdx.x * 2 + 1] = s_p[0];
@@ -778,7 +774,7 @@ __global__ __launch_bounds__(256) void step_control_kernel(const double* __restr
   s_p[tid] = tp;
   s_bad[tid] = bad;
   __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
+  for (int o = 128; o > 0; o >>= 1) {      // block_tree_sum256's order, written out: the first bad parameter folds with min in the same levels
     if (tid < o) {
       s_g[tid] += s_g[tid + o];
       s_p[tid] += s_p[tid + o];
@@ -833,8 +829,6 @@ __global__ __launch_bounds__(256) void adamw_guarded_kernel(float* __restrict__ 
 }
 
 // ============================================================================= C-ABI
-static inline int ew_grid_b(int64_t total) { return (int)min((int64_t)4096, (total + 255) / 256); }
-
 // dW (fp32 [Cout][ntaps*Cin], caller zeroes it) += dY^T * gather(X); db (nullable, fp32 [Cout], zeroed) += colsum(dY).
 extern "C" int mmd_conv_wgrad(int dtype, const void* dY, int64_t lddy, const void* X, int64_t ldx, float* dW, float* db, int M, int Cout,
                               int Cin, int ntaps, const int* taps, int D0, int D1, int D2, int torch_layout, void* stream) {
@@ -968,7 +962,7 @@ static int gn_bwd_impl(int dtype, const void* x, int64_t ldx, const void* dy, in
   // zeroed by a kernel, not hipMemsetAsync: memset nodes of a captured graph were observed to lose their ordering against the
   // neighbouring kernel nodes on replay (train_graph.py), a fill kernel is an ordinary node of the chain
   if (!ws0) {
-    if (int zrc = mmd_launch<zero_f32_kernel>("gn_bwd_zero", dim3(ew_grid_b((int64_t)S * C * 2)), dim3(256), 0, st, PQ, (int64_t)S * C * 2)) return zrc;
+    if (int zrc = mmd_launch<zero_f32_kernel>("gn_bwd_zero", dim3(ew_grid((int64_t)S * C * 2)), dim3(256), 0, st, PQ, (int64_t)S * C * 2)) return zrc;
   }
   const int rpp = max(1, 256 / (CW / epv));
   int R = 4 * rpp;
@@ -1017,7 +1011,7 @@ extern "C" int mmd_silu(int dtype, const void* x, const void* dy, void* out, int
   MMD_REQUIRE((dtype == MMD_BF16 || dtype == MMD_F32) && x && out && n > 0 && n % epv == 0, "silu: bad argument");
   hipStream_t st = (hipStream_t)stream;
   return mmd_by_dtype(dtype, [&](auto t) {
-    return mmd_launch<silu_kernel<typename decltype(t)::type>>("silu", dim3(ew_grid_b(n / epv)), dim3(256), 0, st, (const char*)x, (const char*)dy, (char*)out,
+    return mmd_launch<silu_kernel<typename decltype(t)::type>>("silu", dim3(ew_grid(n / epv)), dim3(256), 0, st, (const char*)x, (const char*)dy, (char*)out,
                                                                n / epv);
   });
 }
@@ -1027,7 +1021,7 @@ extern "C" int mmd_dropout(int dtype, const void* x, const uint8_t* mask, float 
   MMD_REQUIRE((dtype == MMD_BF16 || dtype == MMD_F32) && x && mask && out && n > 0 && n % epv == 0, "dropout: bad argument");
   hipStream_t st = (hipStream_t)stream;
   return mmd_by_dtype(dtype, [&](auto t) {
-    return mmd_launch<dropout_kernel<typename decltype(t)::type>>("dropout", dim3(ew_grid_b(n / epv)), dim3(256), 0, st, (const char*)x, mask, scale,
+    return mmd_launch<dropout_kernel<typename decltype(t)::type>>("dropout", dim3(ew_grid(n / epv)), dim3(256), 0, st, (const char*)x, mask, scale,
                                                                   (char*)out, n / epv);
   });
 }
@@ -1035,14 +1029,14 @@ extern "C" int mmd_dropout(int dtype, const void* x, const uint8_t* mask, float 
 extern "C" int mmd_mse_grad(const float* out, const float* target, const float* w, float* g, int N, int64_t per_sample, void* stream) {
   MMD_REQUIRE(out && target && w && g && N > 0 && per_sample > 0, "mse_grad: bad argument");
   const int64_t total = per_sample * N;
-  return mmd_launch<mse_grad_kernel>("mse_grad", dim3(ew_grid_b(total)), dim3(256), 0, (hipStream_t)stream, out, target, w, g, per_sample, total);
+  return mmd_launch<mse_grad_kernel>("mse_grad", dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, out, target, w, g, per_sample, total);
 }
 
 extern "C" int mmd_adamw_step(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr, float beta1, float beta2,
                               float eps, float weight_decay, int step, float ema_rate, void* stream) {
   MMD_REQUIRE(p && g && m && v && n > 0 && step >= 1, "adamw_step: bad argument");
   const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
-  return mmd_launch<adamw_kernel>("adamw_step", dim3(ew_grid_b(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, n, lr, beta1, beta2, eps, weight_decay,
+  return mmd_launch<adamw_kernel>("adamw_step", dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, n, lr, beta1, beta2, eps, weight_decay,
                                   bc1, bc2, ema_rate);
 }
 
@@ -1072,7 +1066,7 @@ extern "C" int mmd_adamw_step_guarded(float* p, const float* g, float* m, float*
   EmaSet ema;
   ema.e[0] = ema0; ema.e[1] = ema1; ema.e[2] = ema2; ema.e[3] = ema3;
   ema.rate[0] = rate0; ema.rate[1] = rate1; ema.rate[2] = rate2; ema.rate[3] = rate3;
-  return mmd_launch<adamw_guarded_kernel>("adamw_step_guarded", dim3(ew_grid_b(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, n, lr, beta1,
+  return mmd_launch<adamw_guarded_kernel>("adamw_step_guarded", dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, n, lr, beta1,
                                           beta2, eps, weight_decay, ctrl);
 }
 

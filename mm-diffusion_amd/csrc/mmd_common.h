@@ -119,8 +119,22 @@ __device__ __forceinline__ float halfwave_total(float v) {
   return dpp_add<0x142, 0xa>(v);   // row_bcast:15 into rows 1 and 3
 }
 
+// Fixed-order sum over the 256 threads of a block, of any number of LDS arrays at once: the caller has stored its value at s[tid];
+// s[tid] += s[tid + o] for o = 128 ... 1, one barrier per level.  On return s[0] holds the total and every thread may read it.  The
+// order never depends on the grid, so the per-sample reductions built on it (loss_terms, vlb_terms, dpm_err, sumsq_chunks) are
+// bitwise repeatable.
+template <class... T>
+__device__ __forceinline__ void block_tree_sum256(int tid, T*... s) {
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) ((s[tid] += s[tid + o]), ...);
+    __syncthreads();
+  }
+}
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+// grid of a 256-thread grid-stride element-wise kernel: one thread per element up to 4096 blocks
+static inline int ew_grid(int64_t total) { return (int)min((int64_t)4096, (total + 255) / 256); }
 
 #define MMD_MAX_DEVICES 16
 static inline int mmd_device_slot() {

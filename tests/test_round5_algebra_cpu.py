@@ -4,7 +4,7 @@ the reference by tests/test_oracle_golden.py): the algebra the engine relies on,
   * up ResBlocks: everything behind the nearest upsample is pointwise, so the block at the INPUT resolution followed by one upsample
     equals the reference order (engine.py `_UP_LOWRES`; reference unet:441-448, 457-476)
   * the video head 3x3x3 conv 128 -> 3 as product planes P[tap, co][m] = W . act(norm(x[m])) plus a 27-tap gather with the index
-    arithmetic of csrc/mmd_misc.hip head_gather_kernel (unet:1003-1012), and the (hi, lo) bf16 weight image of ops.head_gemm_pack
+    arithmetic of csrc/mmd_edge.hip head_gather_kernel (unet:1003-1012), and the (hi, lo) bf16 weight image of ops.head_gemm_pack
   * GroupNorm statistics from 64-row x 4-channel (sum, sum of squares) records - what mmd_resample_stats and the GEMM epilogues emit and
     mmd_gn_finalize_stats folds (nn:16-33)
 """

@@ -1,4 +1,4 @@
-"""Lane-level model of the head GEMM (mm-diffusion_amd/csrc/mmd_misc.hip: head_gemm_kernel<8>) + its host-side weight image
+"""Lane-level model of the head GEMM (mm-diffusion_amd/csrc/mmd_edge.hip: head_gemm_kernel<8>) + its host-side weight image
 (ops.head_gemm_pack): checks, on the CPU, that
 
   * the image [hl][ob][cg][half][l31][8] read as `sW + (((hl * 3 + ob) * KS + cg) * 64 + lane) * 16` hands lane (l31, half) the A
