@@ -9,14 +9,22 @@
 //   * the last query group owns the remainder rows (unet:547-548)
 // q/k/v live in the qkv GEMM output rows: q at column q_off + h*ch, k at k_off + h*ch, v at v_off + h*ch.
 //
-// attn_mfma_kernel (bf16, ch in {16,32,48,64,96,128}): flash-style, 4 waves x 32 queries, 64-key tiles.
-//   S^T = K Q^T on v_mfma_f32_32x32x16_bf16 (keys = D rows, queries = D cols: every lane owns ONE query,
-//   so running max / sum / rescale are lane-local plus one lane^32 exchange), P stays in registers and is
-//   the B operand of O^T = V^T P^T (the 32x32 C layout of S^T is exactly the k-slot order we feed, with V^T
-//   staged key-permuted to match), K row-major / V transposed in LDS with conflict-free strides.
+// Four bf16 MFMA flash kernels with ONE register layout and one arithmetic (mmd_attn_common.h holds what the layout dictates:
+// S^T = K Q^T on v_mfma_f32_32x32x16_bf16 with keys = D rows, queries = D cols, so every lane owns ONE query and running max / sum /
+// rescale are lane-local plus one lane^32 exchange; P stays in registers and is the B operand of O^T = V^T P^T).  They differ in
+// how K / V reach the MFMAs and in who orders the instructions:
+//   attn_mfma_kernel (impl 2; ch in {16,32,48,64,96,128,192}): 4 waves x 32 queries, 64-key tiles staged through registers, K row-major /
+//     V transposed and key-permuted in LDS with conflict-free strides, two barriers per tile.
+//   attn_dma_kernel (impl 4; ch 64): K / V tiles by descriptor DMA into swizzled row-major LDS, V^T by transposing reads, one barrier
+//     per tile.  Bitwise attn_mfma_kernel.
+//   attn_pipe_kernel (impl 5; ch 64): the DMA kernel software-pipelined over key tiles, one iteration = one generated asm statement
+//     (tools/gen_attn_pipe.py).  Bitwise attn_mfma_kernel.
+//   attn_stage_kernel (impl 3; ch % 32 == 0): 8 waves, 256-key stages, three fenced phases per 64-key sub-tile, row max / sum in four chains.
 // attn_generic_kernel (fp32 math, any ch <= 192): LDS-tiled VALU flash attention - fp32 mode and odd shapes.
-// attn_small_kernel: one wave per (slice, head) for short sequences (temporal attention, T = F <= 32).
-#include "mmd_common.h"
+// attn_small_kernel: one wave per (slice, head) for short sequences (temporal attention, T = F <= 32), VALU.
+// attn_small_mfma_kernel: the same sequences on the MFMA, P as a bf16 hi + lo pair.
+// attn_fwd_impl at the end of the file chooses among them (`impl`, MMD_ATTN_* switches).
+#include "mmd_attn_common.h"
 #include <type_traits>
 
 struct AttnParams {
@@ -35,54 +43,8 @@ struct AttnParams {
   float* lse2;                // optional [q rows, heads]: log2-domain log-sum-exp of scale*log2e*scores (training forward)
 };
 
-struct GroupInfo {
-  int64_t q_row0, k_row0;
-  int q_count, k_count, k_start;
-  int k_mod;
-};
-
-__device__ __forceinline__ GroupInfo group_info(const AttnParams& p, int bg) {
-  GroupInfo gi;
-  const int n = bg / p.G, g = bg % p.G;
-  gi.q_row0 = (int64_t)n * p.q_rows_per_batch + (int64_t)g * p.q_per_group;
-  gi.q_count = (g == p.G - 1) ? (int)(p.q_rows_per_batch - (int64_t)g * p.q_per_group) : p.q_per_group;
-  gi.k_row0 = (int64_t)n * p.k_rows_per_batch;
-  gi.k_mod = (int)p.k_rows_per_batch;
-  gi.k_count = p.win * p.k_per_group;
-  const int shift = p.shift_ptr ? *p.shift_ptr : 0;
-  gi.k_start = (int)(((int64_t)(g + shift) * p.k_per_group) % gi.k_mod);
-  return gi;
-}
-// XCD-aware block remap.  Workgroups are dealt round-robin to the 8 XCDs by flat id, and blockIdx.x (the query tile) is
-// the fastest index: by default the query tiles of one (head, group) land on 8 DIFFERENT XCDs and each private L2 fetches
-// the same K/V window from HBM again.  Remap so all query tiles of a (head, group) share flat-id mod 8 (same XCD, and
-// adjacent in dispatch order).  Returns (query tile, head, batch-group).
-__device__ __forceinline__ void attn_block_coords(int& qt, int& h, int& bg) {
-  const int nx = gridDim.x, ny = gridDim.y, nz = gridDim.z;
-  const int hz_count = ny * nz;
-  int hz;
-  if ((hz_count & 7) == 0 && nx > 1) {
-    const int f = blockIdx.x + nx * (blockIdx.y + ny * blockIdx.z);
-    const int k = f >> 3, r = f & 7;
-    qt = k % nx;
-    hz = r + 8 * (k / nx);
-  } else {
-    qt = blockIdx.x;
-    hz = blockIdx.y + ny * blockIdx.z;
-  }
-  h = hz % ny;
-  bg = hz / ny;
-}
-
-__device__ __forceinline__ int64_t key_row(const GroupInfo& gi, int kk) {
-  int r = gi.k_start + kk;
-  if (r >= gi.k_mod) r -= gi.k_mod;
-  return gi.k_row0 + r;
-}
-
 // ============================================================================= MFMA flash attention (bf16)
 __device__ __attribute__((aligned(16))) uint32_t g_attn_zero[4] = {0, 0, 0, 0};   // (-DATTN_BRANCHFREE_KV) what a key past the window reads
-#define SVT_STRIDE 136   // bytes per V^T row (64 keys * 2 B + 8): (stride/8) odd -> conflict-free ds_read_b64
 
 // launch bound 2 waves/SIMD (<= 256 registers): keeps the S / O accumulators in the unified VGPR file - with the default
 // bound hipcc parks them in AGPRs and every softmax / rescale touch costs a v_accvgpr_read + write pair (224 moves per tile).
@@ -95,7 +57,7 @@ __global__ __launch_bounds__(256, (D <= 96 ? 2 : 1)) void attn_mfma_kernel(const
   constexpr int NK = (64 * DV + 255) / 256;   // staged vecs per thread per operand
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* sK = smem;                     // [64][SK]
-  char* sVt = smem + 64 * SK;          // [DT*32][SVT_STRIDE]
+  char* sVt = smem + 64 * SK;          // [DT*32][TSTRIDE]
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int half = lane >> 5, l31 = lane & 31;
@@ -107,28 +69,16 @@ __global__ __launch_bounds__(256, (D <= 96 ? 2 : 1)) void attn_mfma_kernel(const
 
   // zero the V^T rows beyond D once (D=16/48: upper half of a 32-row tile is never staged)
   if (D % 32 != 0) {
-    for (int i = tid; i < (DT * 32 - D) * SVT_STRIDE / 4; i += 256) ((uint32_t*)(sVt + D * SVT_STRIDE))[i] = 0u;
+    for (int i = tid; i < (DT * 32 - D) * TSTRIDE / 4; i += 256) ((uint32_t*)(sVt + D * TSTRIDE))[i] = 0u;
   }
 
-  // ---- Q fragments (B operand of S^T = K Q^T): lane (q = l31, half) holds d = 16*s + 8*half + [0,8)
   const int qi = q0 + wave * 32 + l31;
   const bool qok = qi < gi.q_count;
   u32x4 qf[KST];
-  {
-    const char* qp = p.Q + ((gi.q_row0 + qi) * p.ldq + p.q_off + h * D) * 2;
 #pragma unroll
-    for (int s = 0; s < KST; ++s) {
-      u32x4 v = {0u, 0u, 0u, 0u};
-      if (qok) v = *(const u32x4*)(qp + (s * 16 + half * 8) * 2);
-      qf[s] = v;
-    }
-  }
-
+  for (int s = 0; s < KST; ++s) qf[s] = q_frag(p.Q + ((gi.q_row0 + qi) * p.ldq + p.q_off + h * D) * 2, s, half, qok);
   f32x16 o[DT];
-#pragma unroll
-  for (int t = 0; t < DT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[t][r] = 0.f;
+  zero_acc(o);
   float m_run = -1e30f, l_run = 0.f;
   const float sc = p.scale * 1.4426950408889634f;   // scores kept in log2 domain
 
@@ -170,10 +120,10 @@ __global__ __launch_bounds__(256, (D <= 96 ? 2 : 1)) void attn_mfma_kernel(const
         {
           const int j = (id & 31) + 32 * ((id >> 6) & 1);
           const int v = 2 * (id >> 7) + ((id >> 5) & 1);
-          uint16_t* dst = (uint16_t*)(sVt + (8 * v) * SVT_STRIDE + 2 * j);
+          uint16_t* dst = (uint16_t*)(sVt + (8 * v) * TSTRIDE + 2 * j);
 #pragma unroll
           for (int e = 0; e < 8; ++e)
-            dst[e * (SVT_STRIDE / 2)] = (uint16_t)((rv[i][e >> 1] >> ((e & 1) * 16)) & 0xffffu);
+            dst[e * (TSTRIDE / 2)] = (uint16_t)((rv[i][e >> 1] >> ((e & 1) * 16)) & 0xffffu);
         }
       }
     }
@@ -190,78 +140,32 @@ __global__ __launch_bounds__(256, (D <= 96 ? 2 : 1)) void attn_mfma_kernel(const
 
     // ---- S^T = K Q^T : two 32-key sub-tiles
     f32x16 s[2];
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s[kt][r] = 0.f;
+    zero_acc(s);
 #pragma unroll
     for (int st = 0; st < KST; ++st)
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt) {      // two independent accumulator chains interleaved
         const u32x4 kf = *(const u32x4*)(sK + (kt * 32 + l31) * SK + half * 16 + st * 32);
-        s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf), __builtin_bit_cast(bf16x8, qf[st]), s[kt], 0, 0, 0);
+        s[kt] = MFMA_BF16(kf, qf[st], s[kt]);
       }
-    // ---- online softmax (lane-local row; partner lane^32 holds the other 32 keys).  VALU diet: the key mask is applied only
-    //      in the (wave-uniform) ragged last tile, the softmax scale rides in the exp2 fma, and the O rescale is skipped
-    //      when no lane's running max moved (alpha == 1 for the whole wave).
-    if constexpr (decltype(ragged)::value) {
-      const int kbase = t * 64 + 4 * half;
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int kk = kbase + 32 * kt + (r & 3) + 8 * (r >> 2);
-          s[kt][r] = kk < gi.k_count ? s[kt][r] : -3e38f;
-        }
-    }
-    float mx = -3e38f;
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[kt][r]);
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float m_new = fmaxf(m_run, mx * sc);        // sc > 0: max commutes with the scale
-    const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-    float ps = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(s[kt][r], sc, -m_new));
-        s[kt][r] = e;
-        ps += e;
-      }
-    ps += __shfl_xor(ps, 32, 64);
-    l_run = l_run * alpha + ps;
-    if (__any(m_new != m_run)) {
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
-    }
-    m_run = m_new;
-    // ---- O^T += V^T P^T : P fragments straight from the S^T registers (k-slot j <-> reg 8*st + j)
+    // ---- online softmax; the key mask is applied only in the (wave-uniform) ragged last tile
+    if constexpr (decltype(ragged)::value) mask_ragged(s, t * 64 + 4 * half, gi.k_count);
+    softmax_step<1, false, false>(s, o, m_run, l_run, sc);
+    // ---- O^T += V^T P^T
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
       for (int st = 0; st < 2; ++st) {
-        bf16x8 pf;
+        const bf16x8 pf = p_frag(s, kt, st);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) pf[j] = (__bf16)s[kt][8 * st + j];
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) {
-          const char* vb = sVt + (dt * 32 + l31) * SVT_STRIDE + (32 * kt + 16 * st + 4 * half) * 2;
-          const u32x2 v0 = *(const u32x2*)(vb);
-          const u32x2 v1 = *(const u32x2*)(vb + 16);
-          u32x4 vf = {v0[0], v0[1], v1[0], v1[1]};
-          o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vf), pf, o[dt], 0, 0, 0);
-        }
+        for (int dt = 0; dt < DT; ++dt) o[dt] = MFMA_BF16(tr_frag(sVt, dt * 32 + l31, kt, st, half), pf, o[dt]);
       }
   };
   const int nfull = gi.k_count >> 6;
   for (int t = 0; t < nfull; ++t) tile_body(t, std::false_type{});
   if (nfull < ntiles) tile_body(nfull, std::true_type{});
-  // ---- normalise and store: lane owns query qi, d = 32*dt + (r&3) + 8*(r>>2) + 4*half
+  // ---- normalise and store: lane owns query qi, d = 32*dt + (r&3) + 8*(r>>2) + 4*half.  Direct 8-byte pieces, not
+  //      store_o_rows_via_lds: D = 16 / 48 leave columns out (d < D) and the rows of O need only 8-byte alignment here
   if (qok) {
     const float inv = 1.f / l_run;
     if (p.lse2 && half == 0) p.lse2[(gi.q_row0 + qi) * p.heads + h] = m_run + __builtin_amdgcn_logf(l_run);   // v_log_f32 = log2
@@ -281,17 +185,6 @@ __global__ __launch_bounds__(256, (D <= 96 ? 2 : 1)) void attn_mfma_kernel(const
   }
 }
 
-// max / sum over the two lanes (l, l ^ 32) that share a query: v_permlane32_swap (VALU) instead of ds_bpermute (an LDS round trip
-// queued behind the fragment reads).  swap(x, x) leaves {lower-half values, upper-half values} in the two results for every lane.
-__device__ __forceinline__ float half_pair_max(float x) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float half_pair_sum(float x) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
 // ============================================================================= DMA-staged MFMA attention (bf16, head width 64; round 3)
 // attn_mfma_kernel above issues ~360 instructions per 64-key tile and wave for its 16 MFMAs: ~110 of them stage K / V (per-lane 64-bit
 // addresses, bounds branches, register round trip, eight 2-byte transposing LDS writes per lane), 32 re-zero the score accumulators, and
@@ -300,10 +193,9 @@ __device__ __forceinline__ float half_pair_sum(float x) {
 //   * K and V tiles go global -> LDS by buffer_load ... lds through ONE descriptor: a lane-constant 32-bit offset per 8-row group
 //     (circular window row, bounds -> an out-of-range offset, which lands zeros), no register staging, no ds_write at all;
 //   * V stays ROW-MAJOR in LDS ([key][d], 16-byte chunks XOR-swizzled with bit 1 of the key so the four key rows of a transposing
-//     read fall on different bank quarters) and the V^T fragments of O^T += V^T P^T come out of ds_read_b64_tr_b16: lane i of a
-//     16-lane group supplies the 8 bytes V[key0 + i / 4][d0 + 4 (i % 4) ..] and receives V[key0 .. key0 + 3][d0 + i];
+//     read fall on different bank quarters) and the V^T fragments of O^T += V^T P^T come out of ds_read_b64_tr_b16 (read_vt_frags_tr);
 //   * K row-major with the GEMMs' swizzle (chunk ^ (row >> 1) & 7), fragments by ds_read_b128;
-//   * the first S^T MFMA of a tile takes a zero accumulator operand instead of 32 v_mov;
+//   * the first S^T MFMA of a tile takes a zero accumulator operand instead of 32 v_mov (s_tile_zero_acc);
 //   * tile t + 1 is in flight while tile t is consumed: one raw s_barrier per tile behind a counted s_waitcnt.
 // Same arithmetic as attn_mfma_kernel (S^T = K Q^T in the log2 domain, lane-local online softmax, P as the B operand straight from the
 // S^T registers): bitwise the same output.
@@ -329,207 +221,67 @@ __global__ __launch_bounds__(256, 2) void attn_dma_kernel(const AttnParams p) {
   if (q0 >= gi.q_count) return;        // uniform per block
   const float sc = p.scale * 1.4426950408889634f;   // scores kept in log2 domain
 
-  // ---- Q fragments (B operand of S^T = K Q^T): lane (q = l31, half) holds d = 16 s + 8 half + [0, 8)
   const int qi = q0 + wave * 32 + l31;
-  const bool qok = qi < gi.q_count;
   u32x4 qf[KST];
-  {
-    const char* qp = p.Q + ((gi.q_row0 + qi) * p.ldq + p.q_off + h * D) * 2;
 #pragma unroll
-    for (int s = 0; s < KST; ++s) {
-      u32x4 v = {0u, 0u, 0u, 0u};
-      if (qok) v = *(const u32x4*)(qp + (s * 16 + half * 8) * 2);
-      qf[s] = v;
-    }
-  }
+  for (int s = 0; s < KST; ++s) qf[s] = q_frag(p.Q + ((gi.q_row0 + qi) * p.ldq + p.q_off + h * D) * 2, s, half, qi < gi.q_count);
   f32x16 o[DT];
-#pragma unroll
-  for (int t = 0; t < DT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[t][r] = 0.f;
+  zero_acc(o);
   float m_run = -1e30f, l_run = 0.f;
 
-  // ---- DMA: wave w stages row groups {w, w + 4} of K and of V; lane L of a group covers row 8 g + L / 8, physical chunk L % 8
-  typedef __attribute__((address_space(3))) void* lptr_t;
-  const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.KV, 0, (int)((int64_t)p.nb * p.k_rows_per_batch * p.ldkv * 2), 0x00020000);
-  const int lrow = lane >> 3, pc = lane & 7;
-  int row_in_tile[2];
-  uint32_t kcol[2], vcol[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int row = 8 * (wave + 4 * i) + lrow;
-    row_in_tile[i] = row;
-    kcol[i] = (uint32_t)((p.k_off + h * D) * 2 + ((pc ^ ((row >> 1) & 7)) * 16));
-    vcol[i] = (uint32_t)((p.v_off + h * D) * 2 + ((pc ^ (((row >> 1) & 1) << 2)) * 16));
-  }
+  // ---- DMA of tile kt0.. into `stage`
+  const auto rsrc = kv_dma_rsrc(p);
+  const KvDmaLanes dl = kv_dma_lanes(wave, lane);
   const uint32_t ldb = (uint32_t)(p.ldkv * 2);
+  const uint32_t kcol_s = (uint32_t)((p.k_off + h * D) * 2), vcol_s = (uint32_t)((p.v_off + h * D) * 2);   // (scalar) column of this head
   auto issue = [&](int stage, int kt0) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      const int kk = kt0 + row_in_tile[i];
-      int r = gi.k_start + kk;
-      r = r >= gi.k_mod ? r - gi.k_mod : r;
-      const uint32_t rowoff = (uint32_t)(gi.k_row0 + r) * ldb;
-      const bool ok = kk < gi.k_count;
-      const uint32_t ko = ok ? rowoff + kcol[i] : 0xfffffff0u, vo = ok ? rowoff + vcol[i] : 0xfffffff0u;
+      const int kk = kt0 + dl.row_in_tile[i];
+      const uint32_t ko = kv_dma_offset(gi, kk, ldb, kcol_s + dl.kswz[i]), vo = kv_dma_offset(gi, kk, ldb, vcol_s + dl.vswz[i]);
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lptr_t)(sK + stage * TILE_B + (wave + 4 * i) * 1024), 16, ko, 0, 0, 0);
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lptr_t)(sV + stage * TILE_B + (wave + 4 * i) * 1024), 16, vo, 0, 0, 0);
     }
   };
-  // fragment addresses.  K: row 32 kt + l31, logical chunk 2 st + half.  V^T by transposing reads: group (kt, st, u) of 4 keys
-  // key0 = 32 kt + 16 st + 8 u + 4 half; this lane supplies row key0 + (lane & 15) / 4, columns dt * 32 + 16 ((lane >> 4) & 1) + 4 (lane & 3)
+  // fragment addresses (s_tile_zero_acc, read_vt_frags_tr)
   const int kx = (l31 >> 1) & 7;
   const char* kbase = sK + l31 * 128;
-  const int vrow0 = 4 * half + ((lane & 15) >> 2);                   // + 32 kt + 16 st + 8 u  (bit 1 of the row = bit 1 of vrow0's low part)
-  const int vcolb = (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;   // byte column inside a 64-byte d tile: chunk = vcolb / 16 + 4 dt
-  typedef __attribute__((ext_vector_type(4))) short s16x4;
-  typedef __attribute__((address_space(3))) s16x4* lp4;
+  const int vrow0 = 4 * half + ((lane & 15) >> 2);
+  const int vcolb = (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;
 
   const int ntiles = (gi.k_count + 63) >> 6;
   issue(0, 0);
-  // S^T = K Q^T of the tile in `stage`: two 32-key sub-tiles, the first k-step on a zero accumulator
-  auto compute_s = [&](int stage, f32x16 (&s)[2]) {
-    const char* kb = kbase + stage * TILE_B;
-    u32x4 kf[KST][2];
-#pragma unroll
-    for (int st = 0; st < KST; ++st)
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt) kf[st][kt] = *(const u32x4*)(kb + kt * 32 * 128 + (((2 * st + half) ^ kx) * 16));
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt) {
-      const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf[0][kt]), __builtin_bit_cast(bf16x8, qf[0]), z, 0, 0, 0);
-    }
-#pragma unroll
-    for (int st = 1; st < KST; ++st)
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
-        s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf[st][kt]), __builtin_bit_cast(bf16x8, qf[st]), s[kt], 0, 0, 0);
-  };
-  // V^T fragments of the tile in `stage` (transposing reads)
-  auto read_v = [&](int stage, bf16x8 (&vf)[2][2][DT]) {
-    const char* vb = sV + stage * TILE_B;
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-      for (int st = 0; st < 2; ++st)
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) {
-          s16x4 lo, hi;
-          {
-            const int row = 32 * kt + 16 * st + vrow0;
-            const int ch = ((vcolb >> 4) + 4 * dt) ^ (((row >> 1) & 1) << 2);
-            lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp4)(vb + row * 128 + ch * 16 + (vcolb & 15)));
-          }
-          {
-            const int row = 32 * kt + 16 * st + 8 + vrow0;
-            const int ch = ((vcolb >> 4) + 4 * dt) ^ (((row >> 1) & 1) << 2);
-            hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp4)(vb + row * 128 + ch * 16 + (vcolb & 15)));
-          }
-          typedef __attribute__((ext_vector_type(8))) short s16x8;
-          const s16x8 both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-          vf[kt][st][dt] = __builtin_bit_cast(bf16x8, both);
-        }
-  };
-  // online softmax of tile t (scores in s, lane-local row; partner lane ^ 32 holds the other 32 keys), then O^T += V^T P^T
-  auto softmax_pv = [&](int t, f32x16 (&s)[2], bf16x8 (&vf)[2][2][DT], auto ragged) {
-    if constexpr (decltype(ragged)::value) {
-      const int kbase2 = t * 64 + 4 * half;
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int kk = kbase2 + 32 * kt + (r & 3) + 8 * (r >> 2);
-          s[kt][r] = kk < gi.k_count ? s[kt][r] : -3e38f;
-        }
-    }
-    float ps = 0.f;
-    {
-      float mx = -3e38f;
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[kt][r]);
-      mx = half_pair_max(mx);       // (v_permlane32_swap: a ds_bpermute here drains lgkmcnt - the V fragment reads in flight - first)
-      const float m_new = fmaxf(m_run, mx * sc);        // sc > 0: max commutes with the scale
-      const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(s[kt][r], sc, -m_new));
-          s[kt][r] = e;
-          ps += e;
-        }
-      ps = half_pair_sum(ps);
-      l_run = l_run * alpha + ps;
-      if (__any(m_new != m_run)) {
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
-      }
-      m_run = m_new;
-    }
-    // P fragments straight from the S^T registers (k-slot j <-> reg 8*st + j)
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-      for (int st = 0; st < 2; ++st) {
-        bf16x8 pf;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) pf[j] = (__bf16)s[kt][8 * st + j];
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[kt][st][dt], pf, o[dt], 0, 0, 0);
-      }
-  };
   const int nfull = gi.k_count >> 6;
   auto tile_body = [&](int t, auto ragged) {
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");      // this tile's DMA (the only one in flight) has landed
     __builtin_amdgcn_s_barrier();                                    // ... for every wave; everyone is past the other stage's reads
     asm volatile("" ::: "memory");
     f32x16 s[2];
-    compute_s(t & 1, s);
+    s_tile_zero_acc(kbase + (t & 1) * TILE_B, half, kx, qf, s);
     bf16x8 vf[2][2][DT];
-    read_v(t & 1, vf);                                               // requested under the softmax
+    read_vt_frags_tr(sV + (t & 1) * TILE_B, vrow0, vcolb, vf);       // requested under the softmax
     // the next tile's DMA goes out BEHIND the transposing reads: hipcc cannot tell that ds_read_b64_tr_b16 does not touch the stage an
     // outstanding LDS-DMA writes and put s_waitcnt vmcnt(0) in front of the first one - the wave sat out the whole L2 round trip of
     // the tile it had just requested (round 3 ISA).  In flight during this tile's softmax and P V, and every other wave's tile.
     if (t + 1 < ntiles) issue((t + 1) & 1, (t + 1) * 64);
-    softmax_pv(t, s, vf, ragged);
+    if constexpr (decltype(ragged)::value) mask_ragged(s, t * 64 + 4 * half, gi.k_count);
+    softmax_step<1, true, false>(s, o, m_run, l_run, sc);
+#pragma unroll
+    for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+      for (int st = 0; st < 2; ++st) {
+        const bf16x8 pf = p_frag(s, kt, st);
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt) o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[kt][st][dt], pf, o[dt], 0, 0, 0);
+      }
   };
   for (int t = 0; t < nfull; ++t) tile_body(t, std::false_type{});
   if (nfull < ntiles) tile_body(nfull, std::true_type{});
-  // ---- normalise, transpose through LDS (stage 0 of K / V: free after the last tile) and store whole 128-byte head rows
+  // ---- epilogue through stage 0 of K / V: free after the last tile (4 x 4.6 KB < 32 KB)
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
-  {
-    constexpr int SO = D * 2 + 16;           // padded row of the transposed tile
-    const float inv = 1.f / l_run;
-    if (p.lse2 && half == 0 && qok) p.lse2[(gi.q_row0 + qi) * p.heads + h] = m_run + __builtin_amdgcn_logf(l_run);
-    char* so = smem + (wave * 32) * SO;      // this wave's 32 rows; written and read by this wave only (4 x 4.6 KB < 32 KB)
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int q4 = 0; q4 < 4; ++q4) {
-        const int d = dt * 32 + 8 * q4 + 4 * half;
-        bf16x4 w;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) w[e] = (__bf16)(o[dt][4 * q4 + e] * inv);
-        *(bf16x4*)(so + l31 * SO + d * 2) = w;
-      }
-    const int tq = q0 + wave * 32;
-#pragma unroll
-    for (int ps2 = 0; ps2 < 32 * (D / 8) / 64; ++ps2) {
-      const int idx = ps2 * 64 + lane;
-      const int row = idx / (D / 8), v = idx % (D / 8);
-      if (tq + row < gi.q_count) {
-        const u32x4 x = *(const u32x4*)(so + row * SO + v * 16);
-        *(u32x4*)(p.O + ((gi.q_row0 + tq + row) * p.ldo + h * D + v * 8) * 2) = x;
-      }
-    }
-  }
+  store_o_rows_via_lds<D>(p, gi, smem, wave, lane, q0 + wave * 32, h, o, m_run, l_run);
 }
 
 // ============================================================================= hand-placed pipelined attention (bf16, head width 64; round 6)
@@ -579,42 +331,24 @@ __global__ __launch_bounds__(256, 2) void attn_pipe_kernel(const AttnParams p) {
   const float sc = p.scale * 1.4426950408889634f;   // scores kept in log2 domain
   const bool active = q0 + wave * 32 < gi.q_count;  // (wave-uniform) a wave without queries stages its share of K / V and keeps the barriers
 
-  // ---- Q fragments (B operand of S^T = K Q^T): lane (q = l31, half) holds d = 16 s + 8 half + [0, 8)
   const int qi = q0 + wave * 32 + l31;
-  const bool qok = qi < gi.q_count;
   u32x4 qf[KST];
-  {
-    const char* qp = p.Q + ((gi.q_row0 + qi) * p.ldq + p.q_off + h * D) * 2;
 #pragma unroll
-    for (int s = 0; s < KST; ++s) {
-      u32x4 v = {0u, 0u, 0u, 0u};
-      if (qok) v = *(const u32x4*)(qp + (s * 16 + half * 8) * 2);
-      qf[s] = v;
-    }
-  }
+  for (int s = 0; s < KST; ++s) qf[s] = q_frag(p.Q + ((gi.q_row0 + qi) * p.ldq + p.q_off + h * D) * 2, s, half, qi < gi.q_count);
   f32x16 o[DT];
-#pragma unroll
-  for (int t = 0; t < DT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[t][r] = 0.f;
+  zero_acc(o);
   float m_run = -1e30f, l_run = 0.f;
 
-  // ---- DMA: wave w stages row groups {w, w + 4} of K and of V; lane L of a group covers row 8 g + L / 8, physical chunk L % 8
-  typedef __attribute__((address_space(3))) void* lptr_t;
-  const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.KV, 0, (int)((int64_t)p.nb * p.k_rows_per_batch * p.ldkv * 2), 0x00020000);
-  const int lrow = lane >> 3, pc = lane & 7;
+  // ---- DMA
+  const auto rsrc = kv_dma_rsrc(p);
+  const KvDmaLanes dl = kv_dma_lanes(wave, lane);
   const uint32_t ldb = (uint32_t)(p.ldkv * 2);
   const uint32_t kcol_s = (uint32_t)((p.k_off + h * D) * 2), vcol_s = (uint32_t)((p.v_off + h * D) * 2);   // (scalar) column of this head
-  int row_in_tile[2];
-  uint32_t kswz[2], vswz[2], kfast[2], vfast[2];
+  uint32_t kfast[2], vfast[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
-    const int row = 8 * (wave + 4 * i) + lrow;
-    row_in_tile[i] = row;
-    kswz[i] = (uint32_t)((pc ^ ((row >> 1) & 7)) * 16);
-    vswz[i] = (uint32_t)((pc ^ (((row >> 1) & 1) << 2)) * 16);
-    kfast[i] = (uint32_t)row * ldb + kswz[i];
-    vfast[i] = (uint32_t)row * ldb + vswz[i];
+    kfast[i] = (uint32_t)dl.row_in_tile[i] * ldb + dl.kswz[i];
+    vfast[i] = (uint32_t)dl.row_in_tile[i] * ldb + dl.vswz[i];
   }
   // tile T of the window into `stage`: K rows (which == 0) or V rows (which == 1)
   auto issue = [&](int which, int stage, int T) {
@@ -630,17 +364,13 @@ __global__ __launch_bounds__(256, 2) void attn_pipe_kernel(const AttnParams p) {
     } else {
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        const int kk = kt0 + row_in_tile[i];
-        int r = gi.k_start + kk;
-        r = r >= gi.k_mod ? r - gi.k_mod : r;
-        const uint32_t off = (uint32_t)(gi.k_row0 + r) * ldb + (which ? vcol_s + vswz[i] : kcol_s + kswz[i]);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lptr_t)(dst + (wave + 4 * i) * 1024), 16, kk < gi.k_count ? off : 0xfffffff0u, 0, 0, 0);
+        const uint32_t off = kv_dma_offset(gi, kt0 + dl.row_in_tile[i], ldb, which ? vcol_s + dl.vswz[i] : kcol_s + dl.kswz[i]);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lptr_t)(dst + (wave + 4 * i) * 1024), 16, off, 0, 0, 0);
       }
     }
   };
-  // fragment addresses (LDS byte addresses for the asm reads).  K: row 32 kt + l31, logical chunk 2 st + half.  V^T by transposing reads:
-  // group (kt, st, u) of 4 keys, key0 = 32 kt + 16 st + 8 u + 4 half; this lane supplies row key0 + (lane & 15) / 4, columns
-  // dt * 32 + 16 ((lane >> 4) & 1) + 4 (lane & 3); the chunk swizzle of a V row depends on bit 1 of the row = bit 1 of vrow0
+  // fragment addresses (LDS byte addresses for the asm reads; s_tile_zero_acc and read_vt_frags_tr for the compiler-scheduled ends):
+  // the chunk swizzle of a V row depends on bit 1 of the row = bit 1 of vrow0
   const int kx = (l31 >> 1) & 7;
   const char* kbase = sK + l31 * 128;
   const int vrow0 = 4 * half + ((lane & 15) >> 2);
@@ -652,8 +382,6 @@ __global__ __launch_bounds__(256, 2) void attn_pipe_kernel(const AttnParams p) {
 #pragma unroll
   for (int dt = 0; dt < DT; ++dt)
     va[dt] = lds0 + (uint32_t)(vrow0 * 128 + ((((vcolb >> 4) + 4 * dt) ^ ((vrow0 & 2) << 1)) * 16) + (vcolb & 15));
-  typedef __attribute__((ext_vector_type(4))) short s16x4;
-  typedef __attribute__((address_space(3))) s16x4* lp4;
 
   const int ntiles = (gi.k_count + 63) >> 6;
   issue(0, 0, 0);
@@ -665,21 +393,7 @@ __global__ __launch_bounds__(256, 2) void attn_pipe_kernel(const AttnParams p) {
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
   if (active) {
-    u32x4 kf[KST][2];
-#pragma unroll
-    for (int st = 0; st < KST; ++st)
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt) kf[st][kt] = *(const u32x4*)(kbase + kt * 32 * 128 + (((2 * st + half) ^ kx) * 16));
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt) {
-      const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      s0[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf[0][kt]), __builtin_bit_cast(bf16x8, qf[0]), z, 0, 0, 0);
-    }
-#pragma unroll
-    for (int st = 1; st < KST; ++st)
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
-        s0[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf[st][kt]), __builtin_bit_cast(bf16x8, qf[st]), s0[kt], 0, 0, 0);
+    s_tile_zero_acc(kbase, half, kx, qf, s0);
     // the loop's first statements read these accumulators from asm, where hipcc does not pad the MFMA -> VALU distance
     asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" : "+v"(s0[0]), "+v"(s0[1]));
   }
@@ -713,104 +427,24 @@ __global__ __launch_bounds__(256, 2) void attn_pipe_kernel(const AttnParams p) {
   asm volatile("" ::: "memory");
   if (active) {
     asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" : "+v"(o[0]), "+v"(o[1]), "+v"(s0[0]), "+v"(s0[1]));
-    const char* vb = sV + (t & 1) * TILE_B;
     bf16x8 vf[2][2][DT];
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-      for (int st = 0; st < 2; ++st)
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) {
-          s16x4 lo, hi;
-          {
-            const int row = 32 * kt + 16 * st + vrow0;
-            const int ch = ((vcolb >> 4) + 4 * dt) ^ (((row >> 1) & 1) << 2);
-            lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp4)(vb + row * 128 + ch * 16 + (vcolb & 15)));
-          }
-          {
-            const int row = 32 * kt + 16 * st + 8 + vrow0;
-            const int ch = ((vcolb >> 4) + 4 * dt) ^ (((row >> 1) & 1) << 2);
-            hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp4)(vb + row * 128 + ch * 16 + (vcolb & 15)));
-          }
-          typedef __attribute__((ext_vector_type(8))) short s16x8;
-          const s16x8 both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-          vf[kt][st][dt] = __builtin_bit_cast(bf16x8, both);
-        }
-    if (gi.k_count & 63) {                                           // (uniform) ragged last tile: keys beyond the window never win
-      const int kbase2 = t * 64 + 4 * half;
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int kk = kbase2 + 32 * kt + (r & 3) + 8 * (r >> 2);
-          s0[kt][r] = kk < gi.k_count ? s0[kt][r] : -3e38f;
-        }
-    }
-    float ps = 0.f;
-    float mx = -3e38f;
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s0[kt][r]);
-    mx = half_pair_max(mx);
-    const float m_new = fmaxf(m_run, mx * sc);
-    const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(s0[kt][r], sc, -m_new));
-        s0[kt][r] = e;
-        ps += e;
-      }
-    ps = half_pair_sum(ps);
-    l_run = l_run * alpha + ps;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
-    m_run = m_new;
+    read_vt_frags_tr(sV + (t & 1) * TILE_B, vrow0, vcolb, vf);
+    if (gi.k_count & 63) mask_ragged(s0, t * 64 + 4 * half, gi.k_count);      // (uniform) ragged last tile
+    softmax_step<1, true, true>(s0, o, m_run, l_run, sc);
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
       for (int st = 0; st < 2; ++st) {
-        bf16x8 pf;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) pf[j] = (__bf16)s0[kt][8 * st + j];
+        const bf16x8 pf = p_frag(s0, kt, st);
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[kt][st][dt], pf, o[dt], 0, 0, 0);
       }
   }
-  // ---- normalise, transpose through LDS (stage 0 of K / V: free after the last tile) and store whole 128-byte head rows
+  // ---- epilogue through stage 0 of K / V: free after the last tile (4 x 4.6 KB < 32 KB)
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
-  if (active) {
-    constexpr int SO = D * 2 + 16;           // padded row of the transposed tile
-    const float inv = 1.f / l_run;
-    if (p.lse2 && half == 0 && qok) p.lse2[(gi.q_row0 + qi) * p.heads + h] = m_run + __builtin_amdgcn_logf(l_run);
-    char* so = smem + (wave * 32) * SO;      // this wave's 32 rows; written and read by this wave only (4 x 4.6 KB < 32 KB)
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int q4 = 0; q4 < 4; ++q4) {
-        const int d = dt * 32 + 8 * q4 + 4 * half;
-        bf16x4 w;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) w[e] = (__bf16)(o[dt][4 * q4 + e] * inv);
-        *(bf16x4*)(so + l31 * SO + d * 2) = w;
-      }
-    const int tq = q0 + wave * 32;
-#pragma unroll
-    for (int ps2 = 0; ps2 < 32 * (D / 8) / 64; ++ps2) {
-      const int idx = ps2 * 64 + lane;
-      const int row = idx / (D / 8), v = idx % (D / 8);
-      if (tq + row < gi.q_count) {
-        const u32x4 x = *(const u32x4*)(so + row * SO + v * 16);
-        *(u32x4*)(p.O + ((gi.q_row0 + tq + row) * p.ldo + h * D + v * 8) * 2) = x;
-      }
-    }
-  }
+  if (active) store_o_rows_via_lds<D>(p, gi, smem, wave, lane, q0 + wave * 32, h, o, m_run, l_run);
 }
 
 // Round 4 also built a 64-queries-per-wave form of the kernel above (8 waves, two 32-query sub-tiles per wave sharing every K / V fragment
@@ -862,25 +496,14 @@ __global__ __launch_bounds__(512, 1) void attn_stage_kernel(const AttnParams p) 
   const int q0 = qc * 256;
   if (q0 >= gi.q_count) return;            // uniform per block
 
-  // ---- Q fragments (B operand of S^T = K Q^T): lane (q = l31, half) holds d = 16 s + 8 half + [0, 8)
   const int tq = q0 + wave * 32;
   const bool live = tq < gi.q_count;       // wave-uniform: a dead wave only helps staging
   const int qi = tq + l31;
   u32x4 qf[KST];
-  {
-    const char* qp = p.Q + ((gi.q_row0 + qi) * p.ldq + p.q_off + h * D) * 2;
 #pragma unroll
-    for (int s = 0; s < KST; ++s) {
-      u32x4 v = {0u, 0u, 0u, 0u};
-      if (qi < gi.q_count) v = *(const u32x4*)(qp + (s * 16 + half * 8) * 2);
-      qf[s] = v;
-    }
-  }
+  for (int s = 0; s < KST; ++s) qf[s] = q_frag(p.Q + ((gi.q_row0 + qi) * p.ldq + p.q_off + h * D) * 2, s, half, qi < gi.q_count);
   f32x16 o[DT];
-#pragma unroll
-  for (int t = 0; t < DT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[t][r] = 0.f;
+  zero_acc(o);
   float m_run = -1e30f, l_run = 0.f;
   const float sc = p.scale * 1.4426950408889634f;   // scores kept in log2 domain
 
@@ -944,15 +567,11 @@ __global__ __launch_bounds__(512, 1) void attn_stage_kernel(const AttnParams p) 
   auto sub_tile = [&](int k0, int sub, bool more, auto ragged) {
     // ---- phase 1: S^T = K Q^T, two independent accumulator chains, fragments already in registers
     f32x16 s[2];
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s[kt][r] = 0.f;
+    zero_acc(s);
 #pragma unroll
     for (int st = 0; st < KST; ++st)
 #pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
-        s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf[st * 2 + kt]), __builtin_bit_cast(bf16x8, qf[st]), s[kt], 0, 0, 0);
+      for (int kt = 0; kt < 2; ++kt) s[kt] = MFMA_BF16(kf[st * 2 + kt], qf[st], s[kt]);
     __builtin_amdgcn_sched_barrier(0);
     // ---- fetch under the softmax: V fragments of this sub-tile, K fragments of the next one
     u32x4 vf[4][DT];
@@ -962,55 +581,18 @@ __global__ __launch_bounds__(512, 1) void attn_stage_kernel(const AttnParams p) 
       for (int dt = 0; dt < DT; ++dt) vf[g][dt] = *(const u32x4*)(vbase + dt * 32 * ATS_VT_STRIDE + (sub * 64 + 16 * g) * 2);
     if (more) read_k(sub + 1);
     __builtin_amdgcn_sched_barrier(0);
-    // ---- phase 2: online softmax (lane-local row; partner lane^32 holds the other 32 keys)
-    if constexpr (decltype(ragged)::value) {
-      const int kb = k0 + sub * 64 + 4 * half;
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int kk = kb + 32 * kt + (r & 3) + 8 * (r >> 2);
-          s[kt][r] = kk < gi.k_count ? s[kt][r] : -3e38f;
-        }
-    }
-    float mxp[4] = {-3e38f, -3e38f, -3e38f, -3e38f};        // four independent chains (a single 32-deep chain is latency-bound)
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mxp[r & 3] = fmaxf(mxp[r & 3], s[kt][r]);
-    const float mx = half_pair_max(fmaxf(fmaxf(mxp[0], mxp[1]), fmaxf(mxp[2], mxp[3])));
-    const float m_new = fmaxf(m_run, mx * sc);
-    const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-    float psp[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(s[kt][r], sc, -m_new));
-        s[kt][r] = e;
-        psp[r & 3] += e;
-      }
-    const float ps = half_pair_sum((psp[0] + psp[1]) + (psp[2] + psp[3]));
-    l_run = l_run * alpha + ps;
-    if (__any(m_new != m_run)) {
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
-    }
-    m_run = m_new;
+    // ---- phase 2: online softmax, row max / sum in four independent chains
+    if constexpr (decltype(ragged)::value) mask_ragged(s, k0 + sub * 64 + 4 * half, gi.k_count);
+    softmax_step<4, true, false>(s, o, m_run, l_run, sc);
     bf16x8 pf[4];
 #pragma unroll
-    for (int g = 0; g < 4; ++g)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) pf[g][e] = (__bf16)s[g >> 1][8 * (g & 1) + e];
+    for (int g = 0; g < 4; ++g) pf[g] = p_frag(s, g >> 1, g & 1);
     __builtin_amdgcn_sched_barrier(0);
     // ---- phase 3: O^T += V^T P^T (k-slot group g = 2 kt + st)
 #pragma unroll
     for (int g = 0; g < 4; ++g)
 #pragma unroll
-      for (int dt = 0; dt < DT; ++dt)
-        o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vf[g][dt]), pf[g], o[dt], 0, 0, 0);
+      for (int dt = 0; dt < DT; ++dt) o[dt] = MFMA_BF16(vf[g][dt], pf[g], o[dt]);
   };
 
   load_stage(0);
@@ -1028,34 +610,9 @@ __global__ __launch_bounds__(512, 1) void attn_stage_kernel(const AttnParams p) 
     }
   }
 
-  // ---- normalise, transpose through LDS (the K region, free after the last stage) and store whole 128-byte head rows: a lane
-  //      owns a query ROW, so direct stores would be 8-byte pieces at a row stride (64 lines per wave instruction - the store tail
-  //      cost 15 % of the kernel); staged, 8 lanes cover one row and a wave instruction writes 8 complete rows
+  // ---- epilogue through the K region (free after the last stage): the direct store tail cost 15 % of the kernel
   __syncthreads();                         // every wave is past its last K / V^T read
-  {
-    const float inv = 1.f / l_run;
-    if (p.lse2 && half == 0 && qi < gi.q_count) p.lse2[(gi.q_row0 + qi) * p.heads + h] = m_run + __builtin_amdgcn_logf(l_run);
-    char* so = smem + (wave * 32) * SK;    // this wave's 32 rows x (D*2 + 16) bytes; written and read by this wave only
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int q4 = 0; q4 < 4; ++q4) {
-        const int d = dt * 32 + 8 * q4 + 4 * half;
-        bf16x4 w;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) w[e] = (__bf16)(o[dt][4 * q4 + e] * inv);
-        *(bf16x4*)(so + l31 * SK + d * 2) = w;
-      }
-#pragma unroll
-    for (int ps = 0; ps < 32 * DV / 64; ++ps) {
-      const int idx = ps * 64 + lane;
-      const int row = idx / DV, v = idx % DV;
-      if (tq + row < gi.q_count) {
-        const u32x4 x = *(const u32x4*)(so + row * SK + v * 16);
-        *(u32x4*)(p.O + ((gi.q_row0 + tq + row) * p.ldo + h * D + v * 8) * 2) = x;
-      }
-    }
-  }
+  store_o_rows_via_lds<D>(p, gi, smem, wave, lane, tq, h, o, m_run, l_run);
 }
 
 // ============================================================================= generic VALU flash attention
@@ -1420,7 +977,7 @@ template <int D>
 static int launch_mfma(const AttnParams& p, int qmax, hipStream_t st) {
   constexpr int SK = D * 2 + 16;
   constexpr int DT = (D + 31) / 32;
-  const size_t lds = 64 * SK + DT * 32 * SVT_STRIDE;
+  const size_t lds = 64 * SK + DT * 32 * TSTRIDE;
   dim3 grid(cdiv(qmax, 128), p.heads, p.nb * p.G);
   return mmd_launch<attn_mfma_kernel<D>>("attn_mfma", grid, dim3(256), lds, st, p);
 }

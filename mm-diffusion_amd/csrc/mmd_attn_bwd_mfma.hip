@@ -1,13 +1,13 @@
 // bf16 MFMA attention backward (training step) for contiguous-row attention: spatial / audio self-attention and the
 // random-shift windowed cross-modal attention (temporal attention, whose rows are strided, uses attn_small_bwd).
 //
-// Same register choreography as the forward kernel (mmd_attn.hip): every lane owns ONE query (dQ kernel) or ONE key
+// Same register choreography as the forward kernels (mmd_attn.hip; the shared pieces are mmd_attn_common.h): every lane owns ONE query (dQ kernel) or ONE key
 // (dK/dV kernel), so the softmax statistics, the dS = P (dP - D) product and the window mask are lane-local, and the
 // 32x32 C layout of the score tile is exactly the k-slot order of the following MFMA's B operand.
 //   dQ kernel : S^T = K Q^T, dP^T = V dO^T (A = row-major K / V tiles), dQ^T += K^T dS^T (A = K^T tile, key-permuted)
 //   dKV kernel: S = Q K^T, dP = dO V^T (A = row-major Q / dO tiles), dV^T += dO^T P, dK^T += Q^T dS (A = transposed tiles)
 // P is recomputed from the forward's log2-domain log-sum-exp; D_i = dO_i . O_i is produced by the dQ kernel.
-#include "mmd_common.h"
+#include "mmd_attn_common.h"
 
 struct AttnBwdMParams {
   const char* Q; int64_t ldq; int q_off;
@@ -23,16 +23,6 @@ struct AttnBwdMParams {
   const int* shift_ptr;
   float scale;
 };
-
-#define TSTRIDE 136     // bytes per row of a transposed [D][64] tile ((stride/8) odd: conflict-free ds_read_b64)
-
-__device__ __forceinline__ int bm_qcount(const AttnBwdMParams& p, int g) {
-  return g == p.G - 1 ? (int)(p.q_rows_per_batch - (int64_t)g * p.q_per_group) : p.q_per_group;
-}
-__device__ __forceinline__ int bm_kstart(const AttnBwdMParams& p, int g) {
-  const int shift = p.shift_ptr ? *p.shift_ptr : 0;
-  return (int)(((int64_t)(g + shift) * p.k_per_group) % p.k_rows_per_batch);
-}
 
 // Stage a [64 rows][D] bf16 tile: row-major into `rm` (row stride SK) and/or transposed into `tr` ([D][64], row-permuted
 // exactly like the forward's V^T so the MFMA k-slots line up with the score-tile registers).  row_ptr(j) gives the
@@ -66,36 +56,6 @@ __device__ __forceinline__ void stage_tile(char* rm, char* tr, int tid, F row_pt
   }
 }
 
-// A fragment (8 k-slots) of a transposed tile for MFMA step (kt, st): slots j<4 -> cols 32kt+16st+4half+j, j>=4 -> +8
-__device__ __forceinline__ u32x4 tr_frag(const char* tr, int row, int kt, int st, int half) {
-  const char* vb = tr + row * TSTRIDE + (32 * kt + 16 * st + 4 * half) * 2;
-  const u32x2 v0 = *(const u32x2*)(vb);
-  const u32x2 v1 = *(const u32x2*)(vb + 16);
-  return u32x4{v0[0], v0[1], v1[0], v1[1]};
-}
-
-#define MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0)
-
-// XCD-aware block order (round 6; the forward kernels' attn_block_coords, mmd_attn.hip): workgroups are dealt round-robin to the eight XCDs
-// by flat id and blockIdx.x (the query / key tile) is the fastest index, so the tiles of one (head, batch-group) land on eight different L2s
-// and each fetches the same K / V (dQ) or Q / dO (dK, dV) rows again.  Remapped so that all tiles of a (head, batch-group) share flat id % 8
-// and are adjacent in dispatch order.  Returns (tile, head, blockIdx.z-equivalent).
-__device__ __forceinline__ void bm_block_coords(int& tile, int& h, int& z) {
-  const int nx = gridDim.x, ny = gridDim.y, nz = gridDim.z;
-  int hz;
-  if (((ny * nz) & 7) == 0 && nx > 1) {
-    const int f = blockIdx.x + nx * (blockIdx.y + ny * blockIdx.z);
-    const int k = f >> 3, r = f & 7;
-    tile = k % nx;
-    hz = r + 8 * (k / nx);
-  } else {
-    tile = blockIdx.x;
-    hz = blockIdx.y + ny * blockIdx.z;
-  }
-  h = hz % ny;
-  z = hz / ny;
-}
-
 // ============================================================================= dQ
 template <int D>
 __global__ __launch_bounds__(256, (D <= 64 ? 2 : 1)) void attn_bwd_dq_mfma_kernel(const AttnBwdMParams p) {
@@ -106,21 +66,18 @@ __global__ __launch_bounds__(256, (D <= 64 ? 2 : 1)) void attn_bwd_dq_mfma_kerne
   char* sKt = smem + 128 * SK;              // [DT*32][TSTRIDE]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int half = lane >> 5, l31 = lane & 31;
-  int qtile, h, bz;
-  bm_block_coords(qtile, h, bz);
-  const int n = bz / p.G, g = bz % p.G;
-  const int qcount = bm_qcount(p, g);
+  int qtile, h, bg;
+  attn_block_coords(qtile, h, bg);
+  const GroupInfo gi = group_info(p, bg);
+  const int qcount = gi.q_count, kcount = gi.k_count;
   const int q0 = qtile * 128;
   if (q0 >= qcount) return;
-  const int64_t q_row0 = (int64_t)n * p.q_rows_per_batch + (int64_t)g * p.q_per_group;
-  const int64_t k_row0 = (int64_t)n * p.k_rows_per_batch;
-  const int k_mod = (int)p.k_rows_per_batch, kcount = p.win * p.k_per_group, kstart = bm_kstart(p, g);
   if (D % 32 != 0)
     for (int i = tid; i < (DT * 32 - D) * TSTRIDE / 4; i += 256) ((uint32_t*)(sKt + D * TSTRIDE))[i] = 0u;
 
   const int qi = q0 + wave * 32 + l31;
   const bool qok = qi < qcount;
-  const int64_t qrow = q_row0 + (qok ? qi : 0);
+  const int64_t qrow = gi.q_row0 + (qok ? qi : 0);
   u32x4 qf[KST], dof[KST];
   float Dq = 0.f;
   {
@@ -149,10 +106,7 @@ __global__ __launch_bounds__(256, (D <= 64 ? 2 : 1)) void attn_bwd_dq_mfma_kerne
   if (qok && half == 0) p.dsum[qrow * p.heads + h] = Dq;
 
   f32x16 dq[DT];
-#pragma unroll
-  for (int t = 0; t < DT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dq[t][r] = 0.f;
+  zero_acc(dq);
   const float sc = p.scale * 1.4426950408889634f;
   const int ntiles = (kcount + 63) >> 6;
   for (int t = 0; t < ntiles; ++t) {
@@ -160,25 +114,19 @@ __global__ __launch_bounds__(256, (D <= 64 ? 2 : 1)) void attn_bwd_dq_mfma_kerne
     auto kptr = [&](int j) -> const char* {
       const int kk = t * 64 + j;
       if (kk >= kcount) return nullptr;
-      int r = kstart + kk;
-      if (r >= k_mod) r -= k_mod;
-      return p.KV + ((k_row0 + r) * p.ldkv + p.k_off + h * D) * 2;
+      return p.KV + (key_row(gi, kk) * p.ldkv + p.k_off + h * D) * 2;
     };
     auto vptr = [&](int j) -> const char* {
       const int kk = t * 64 + j;
       if (kk >= kcount) return nullptr;
-      int r = kstart + kk;
-      if (r >= k_mod) r -= k_mod;
-      return p.KV + ((k_row0 + r) * p.ldkv + p.v_off + h * D) * 2;
+      return p.KV + (key_row(gi, kk) * p.ldkv + p.v_off + h * D) * 2;
     };
     stage_tile<D, true, true>(sK, sKt, tid, kptr);
     stage_tile<D, true, false>(sV, nullptr, tid, vptr);
     __syncthreads();
     f32x16 s[2], dp[2];
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { s[kt][r] = 0.f; dp[kt][r] = 0.f; }
+    zero_acc(s);
+    zero_acc(dp);
 #pragma unroll
     for (int st = 0; st < KST; ++st)
 #pragma unroll
@@ -201,14 +149,9 @@ __global__ __launch_bounds__(256, (D <= 64 ? 2 : 1)) void attn_bwd_dq_mfma_kerne
     for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
       for (int st = 0; st < 2; ++st) {
-        bf16x8 df;
+        const bf16x8 df = p_frag(s, kt, st);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) df[j] = (__bf16)s[kt][8 * st + j];
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) {
-          const u32x4 kf = tr_frag(sKt, dt * 32 + l31, kt, st, half);
-          dq[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf), df, dq[dt], 0, 0, 0);
-        }
+        for (int dt = 0; dt < DT; ++dt) dq[dt] = MFMA_BF16(tr_frag(sKt, dt * 32 + l31, kt, st, half), df, dq[dt]);
       }
   }
   if (qok) {
@@ -247,7 +190,7 @@ __global__ __launch_bounds__(256, (D <= 64 ? 2 : 1)) void attn_bwd_dkv_mfma_kern
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int half = lane >> 5, l31 = lane & 31;
   int ktile, h, n;
-  bm_block_coords(ktile, h, n);
+  attn_block_coords(ktile, h, n);
   const int split = NS > 1 ? h % NS : 0;
   if (NS > 1) h /= NS;
   const int k_mod = (int)p.k_rows_per_batch, kcount = p.win * p.k_per_group;
@@ -274,20 +217,18 @@ __global__ __launch_bounds__(256, (D <= 64 ? 2 : 1)) void attn_bwd_dkv_mfma_kern
     }
   }
   f32x16 dk[DT], dv[DT];
-#pragma unroll
-  for (int t = 0; t < DT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { dk[t][r] = 0.f; dv[t][r] = 0.f; }
+  zero_acc(dk);
+  zero_acc(dv);
   const float sc = p.scale * 1.4426950408889634f;
 
   for (int g = 0; g < p.G; ++g) {
-    const int kstart = bm_kstart(p, g);
-    int rel = kidx - kstart;
+    const GroupInfo gi = group_info(p, n, g);
+    int rel = kidx - gi.k_start;
     if (rel < 0) rel += k_mod;
     const bool inwin = kok && rel < kcount;
     if (!__syncthreads_or(inwin ? 1 : 0)) continue;          // no key of this 128-key tile is in group g's window
-    const int qcount = bm_qcount(p, g);
-    const int64_t q_row0 = (int64_t)n * p.q_rows_per_batch + (int64_t)g * p.q_per_group;
+    const int qcount = gi.q_count;
+    const int64_t q_row0 = gi.q_row0;
     for (int q0 = 0; q0 < qcount; q0 += 64) {
       __syncthreads();
       auto qptr = [&](int j) -> const char* {
@@ -315,10 +256,8 @@ __global__ __launch_bounds__(256, (D <= 64 ? 2 : 1)) void attn_bwd_dkv_mfma_kern
       }
       __syncthreads();
       f32x16 s[2], dp[2];
-#pragma unroll
-      for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { s[qt][r] = 0.f; dp[qt][r] = 0.f; }
+      zero_acc(s);
+      zero_acc(dp);
 #pragma unroll
       for (int st = 0; st < KST; ++st)
 #pragma unroll
@@ -344,15 +283,13 @@ __global__ __launch_bounds__(256, (D <= 64 ? 2 : 1)) void attn_bwd_dkv_mfma_kern
       for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
         for (int st = 0; st < 2; ++st) {
-          bf16x8 pf, df;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) { pf[j] = (__bf16)s[qt][8 * st + j]; df[j] = (__bf16)dp[qt][8 * st + j]; }
+          const bf16x8 pf = p_frag(s, qt, st), df = p_frag(dp, qt, st);
 #pragma unroll
           for (int dt = 0; dt < DT; ++dt) {
             const u32x4 gt = tr_frag(sdOt, dt * 32 + l31, qt, st, half);
             const u32x4 qtf = tr_frag(sQt, dt * 32 + l31, qt, st, half);
-            dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, gt), pf, dv[dt], 0, 0, 0);
-            dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, qtf), df, dk[dt], 0, 0, 0);
+            dv[dt] = MFMA_BF16(gt, pf, dv[dt]);
+            dk[dt] = MFMA_BF16(qtf, df, dk[dt]);
           }
         }
     }

@@ -29,27 +29,28 @@ attention (`attn_ref`, `attn_bound`)
     out[i, d] = sum_j p_ij v_jd, p = softmax_j(a_ij), a_ij = ch**-0.5 q_i . k_j.  With Sv[i, d] = sum_j p_ij |v_jd|:
     * weights perturbed by relative errors eps_ij move the ratio sum_j e_ij v_jd / sum_j e_ij by at most
       sum_j p_ij eps_ij |v_jd| + |out| sum_j p_ij eps_ij  (numerator and denominator).
-    * P in bf16 in front of the PV MFMA (mmd_attn.hip:250, 481, 779, 1006 `pf[j] = (__bf16)s[..]`; mmd_attn_pipe_body.inc:
-      the v_cvt_pk_bf16_f32 of the P registers): eps <= v on the NUMERATOR only, because every flash kernel sums the row
-      from the UNROUNDED fp32 exponentials (mmd_attn.hip:232, 462, 764 `ps += e`, :994 `l_run = l_run * alpha + ps`; the pipelined
-      body is bitwise the DMA-staged kernel).  So the P term is c v Sv with c = 1.  (A row sum taken from the rounded P would
-      add v |out| <= v Sv: c = 2.  Not what the kernels do, so not granted.)
-    * attn_small_mfma_kernel (mmd_attn.hip:1394-1395) feeds P as a bf16 hi + lo pair: lo = e - bf16(e), |lo| <= v e, and
+    * P in bf16 in front of the PV MFMA (mmd_attn_common.h: p_frag, `pf[j] = (__bf16)s[..]`, the one packing of all four flash
+      kernels; mmd_attn_pipe_body.inc: the v_cvt_pk_bf16_f32 of the P registers): eps <= v on the NUMERATOR only, because every
+      flash kernel sums the row from the UNROUNDED fp32 exponentials (mmd_attn_common.h: softmax_step, `psp[..] += e` and
+      `l_run = l_run * alpha + ps`; the pipelined body is bitwise the DMA-staged kernel).  So the P term is c v Sv with c = 1.
+      (A row sum taken from the rounded P would add v |out| <= v Sv: c = 2.  Not what the kernels do, so not granted.)
+    * attn_small_mfma_kernel (mmd_attn.hip: `lo4` / `pf`) feeds P as a bf16 hi + lo pair: lo = e - bf16(e), |lo| <= v e, and
       rounding lo to bf16 costs v |lo| <= v^2 e: P term v^2 Sv (p_round = 2**-16).
-    * the VALU kernels (attn_generic_kernel :1150-1182, attn_small_kernel :1288-1299) and fp32 mode keep P in fp32: no P term.
+    * the VALU kernels (attn_generic_kernel, attn_small_kernel: `__expf(..)` to the `oacc` / `o` sums) and fp32 mode keep P in
+      fp32: no P term.
     * fp32-level terms, returned by attn_ref as `e32` (absolute, per element), D = ch, n = keys, T = ceil(n / 32) key tiles (32 =
       the smallest key tile of any kernel: attn_generic_kernel<T, 32, 12>), A_ij = ch**-0.5 sum_d |q_id k_jd|,
       R_i = max_j a_ij - min_j a_ij:
-        score:     D products summed in fp32, the scale applied to q (:1089, :1264) or inside the exp2 fma with the constant
-                   scale * log2(e) rounded once (:133, :230): |da_ij| <= (D + 3) u A_ij
-        argument:  a_ij - m is rounded once (fma at :230 / subtraction at :1150), |a_ij - m| <= R_i, and __expf multiplies by
+        score:     D products summed in fp32, the scale applied to q (the VALU kernels' Q loads) or inside the exp2 fma with the
+                   constant scale * log2(e) rounded once (`sc`; softmax_step): |da_ij| <= (D + 3) u A_ij
+        argument:  a_ij - m is rounded once (softmax_step's fma / the VALU kernels' subtraction), |a_ij - m| <= R_i, and __expf multiplies by
                    log2(e) once more: 2 u R_i
         exp:       v_exp_f32 is accurate to 1 ulp = 2 u relative
         so         eps_ij = ((D + 3) A_ij + 2 R_i + 2) u, entering as in the first bullet;
-        rescale:   per key tile alpha = exp2(m_old - m_new) (:224) carries 2 u R_i + 2 u and o *= alpha (:240) one rounding; it
+        rescale:   per key tile alpha = exp2(m_old - m_new) carries 2 u R_i + 2 u and o *= alpha one rounding (softmax_step); it
                    reweights the earlier keys against the later ones: T (2 R_i + 3) u Sv
         PV, sums:  n products accumulated in fp32: (n + 1) u Sv; the row sum of n terms: n u |out| <= n u Sv
-        1 / l, o * inv (:266, :277): 3 u |out| <= 3 u Sv
+        1 / l, o * inv (the epilogues; store_o_rows_via_lds): 3 u |out| <= 3 u Sv
     bound, fp32 output: e32.  bf16 output, with eP = p_round * Sv:  v (|ref| + eP + e32) + eP + e32.
 
 GroupNorm fused into the GEMM loader (tests/test_elementwise_gpu.py: the tile-128 loader)

@@ -67,12 +67,12 @@ GroupNorm backward (`gn_fwd_ref` with its bounds e_a / e_b / e_mean / e_rstd, `g
 
 attention backward (`attn_bwd_ref`, `attn_out_bound`, `attn_bwd_bound_kv`, `attn_bwd_assemble`)
     Per (query set, key set) and head, float64: a = scale q k^T, p = softmax(a), dP = dO V^T, D_i = dO_i . O_i with O the STORED
-    forward output (mmd_attn_bwd_mfma.hip:140-149, mmd_attn_bwd_body.inc:40-49) or, mode 'small', D_i = sum_j p_ij dP_ij
+    forward output (mmd_attn_bwd_mfma.hip: `Dq` of attn_bwd_dq_mfma_kernel, mmd_attn_bwd_body.inc:40-49) or, mode 'small', D_i = sum_j p_ij dP_ij
     (mmd_attn_bwd.hip:247); dS = p (dP - D); dV = p^T dO, dQ = scale dS K, dK = scale dS^T Q.  dK / dV of a key sum over every
     query of every group whose window holds the key: the reference returns per-pair contributions and per-pair error terms that add.
     With A_ij = scale sum_d |q_id k_jd|, AP_ij = sum_d |dO_id v_jd|, R_i = max_j a_ij - min_j a_ij, n keys, T = ceil(n / 32):
       P:   the three kernels recompute p_ij = exp(a_ij - LSE_i).  The MFMA path takes LSE (log2 domain, lse2) from the forward
-           (`exp2(fma(s, scale * log2e, -lse2))`, :197 / :339), the VALU kernel from its own first pass (body.inc:52-84), the short
+           (`exp2(fma(s, scale * log2e, -lse2))`, `pr` in both kernels), the VALU kernel from its own first pass (body.inc:52-84), the short
            kernel divides by its own row sum (mmd_attn_bwd.hip:241-247).  LSE carries the forward's row-sum error, the terms of
            errbound.attn_ref:  e_L_i = sum_j p_ij eps_ij + (n + T (2 R_i + 3) + 4) u + 3 u |ln2 lse2_i|  (natural-log units; the
            last term: log2 / logf at 1 ulp, the add, the fp32 store), eps_ij = ((ch + 3) A_ij + 2 R_i + 2) u.  It enters EVERY p_ij
@@ -82,7 +82,7 @@ attention backward (`attn_bwd_ref`, `attn_out_bound`, `attn_bwd_bound_kv`, `attn
       dP:  ch products in fp32: (ch + 1) u AP_ij.   D: ch products: e_D_i = (ch + 1) u sum_d |dO_id O_id|; mode 'small':
            e_D_i = sum_j p_ij ((eps_P_ij + (n + 2) u) |dP_ij| + (ch + 1) u AP_ij).
       dS:  e_dS_ij = p_ij ((eps_P_ij + 2 u) |dP_ij - D_i| + (ch + 1) u AP_ij + e_D_i)
-      MFMA path only: P and dS each rounded ONCE to bf16 in front of the second MFMA (:206, :349):  E_dS = e_dS + v (|dS| + e_dS),
+      MFMA path only: P and dS each rounded ONCE to bf16 in front of the second MFMA (mmd_attn_common.h: p_frag):  E_dS = e_dS + v (|dS| + e_dS),
            E_P = p eps_P + v p (1 + eps_P).  The VALU kernels keep both in fp32: E_dS = e_dS, E_P = p eps_P.
       dQ:  n products accumulated in fp32 over the keys, one multiply by scale (itself rounded):
            e_dQ = scale (E_dS |K| + (n + 1) u |dS| |K|) + 3 u scale |dS| |K|

@@ -56,8 +56,9 @@ def main():
                 torch.save(out.cpu(), os.path.join(os.environ["ATTN_BENCH_SAVE"], f"s{si}_i{impl}.pt"))
             vs = ""
             if os.environ.get("ATTN_BENCH_CMP"):
-                base = torch.load(os.path.join(os.environ["ATTN_BENCH_CMP"], f"s{si}_i{impl}.pt")).cuda().float()
-                vs = f" vs-product {float((out.float() - base).norm() / base.norm()):.1e}"
+                base = torch.load(os.path.join(os.environ["ATTN_BENCH_CMP"], f"s{si}_i{impl}.pt")).cuda()
+                same = "bit-equal" if torch.equal(out, base) else "NOT bit-equal"      # the relative norm cannot show bit equality
+                vs = f" vs-product {float((out.float() - base.float()).norm() / base.float().norm()):.1e} {same}"
             H.call("mmd_event_record", ev[0], st)
             n = 10
             for _ in range(n):
