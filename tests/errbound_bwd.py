@@ -274,16 +274,26 @@ def gn_fwd_ref(x, gamma, beta, film, slices):
     e_mean = e_dm + U32 * mean.abs()
     e_var = (Tn + 4) * U32 * Sq / cnt + 2 * dm.abs() * e_dm
     e_rstd = rstd ** 3 * e_var / 2 + U32 * rstd
+    a, b, e_a, e_b = gn_affine(mean, rstd, e_mean, e_rstd, gamma, beta, film)
+    return dict(a=a, b=b, mean=mean, rstd=rstd, e_a=e_a, e_b=e_b, e_mean=e_mean, e_rstd=e_rstd)
+
+
+def gn_affine(mean, rstd, e_mean, e_rstd, gamma, beta, film):
+    """The fused affine a, b [S, C] in float64 from mean, rstd [S, 32] and its bounds e_a, e_b from theirs (module docstring): the
+    arithmetic every GroupNorm kernel shares (a = rstd gamma, b = beta - mean a, then a *= 1 + scale, b = b (1 + scale) + shift)."""
+    S = mean.shape[0]
+    C = gamma.shape[0]
+    cpg = C // 32
     rep = lambda t: t.repeat_interleave(cpg, dim=1)                              # [S, 32] -> [S, C]
-    sc = 1 + film[:, :C] if film is not None else torch.ones(S, C, dtype=torch.float64, device=x.device)
-    sh = film[:, C:2 * C] if film is not None else torch.zeros(S, C, dtype=torch.float64, device=x.device)
+    sc = 1 + film[:, :C] if film is not None else torch.ones(S, C, dtype=torch.float64, device=mean.device)
+    sh = film[:, C:2 * C] if film is not None else torch.zeros(S, C, dtype=torch.float64, device=mean.device)
     a0 = rep(rstd) * gamma
     a = a0 * sc
     b = (beta - rep(mean) * a0) * sc + sh
     e_a = (gamma * sc).abs() * rep(e_rstd) + 3 * U32 * a.abs()
     e_b = sc.abs() * (a0.abs() * rep(e_mean) + (rep(mean) * gamma).abs() * rep(e_rstd)) \
         + 4 * U32 * ((beta * sc).abs() + (rep(mean) * a0 * sc).abs() + sh.abs())
-    return dict(a=a, b=b, mean=mean, rstd=rstd, e_a=e_a, e_b=e_b, e_mean=e_mean, e_rstd=e_rstd)
+    return a, b, e_a, e_b
 
 
 def gn_bwd_ref(x, dy, gamma, beta, film, act, slices, stored=None, out_dtype=torch.float32):

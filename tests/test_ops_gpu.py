@@ -7,7 +7,10 @@ Tolerances (rel-L2 against the fp32 CPU oracle on the same inputs):
 Index/window/padding errors produce O(1) errors in the elements they touch; the whole-tensor rel-L2 used here sees them only when
 they touch many - an error confined to a few rows, one border or one tap, or a small systematic one, stays below either bound
 (tests/test_errbound_cpu.py shows four such defects passing 1e-2).  tests/test_elementwise_gpu.py checks the conv-GEMM and attention
-kernels element by element.
+kernels element by element; tests/test_elementwise_fwd_norm_gpu.py does so for mmd_gn_apply / gn_small / gn_group / gn_finalize_stats /
+add_rowbias against float64 with a per-element bound (tests/errbound_fwd.py), tests/test_elementwise_fwd_edge_gpu.py for mmd_stem_conv and
+mmd_head_conv in every kernel variant, tests/test_elementwise_fwd_misc_gpu.py for mmd_resample, the statistics records (record by record),
+mmd_bilinear_concat(_rows) and the chain producer -> records -> mmd_gn_finalize_stats.
 """
 import math
 import os

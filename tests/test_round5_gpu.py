@@ -3,7 +3,10 @@ out layers of the up ResBlocks at the input resolution, the serialised cross-att
 
 The kernel tests compare with fp32 torch restatements of the reference operators (unet:133-208 resampling, nn.py:16-33 GroupNorm32,
 unet:1003-1012 head); the plan tests compare the engine built with a switch on against the same engine with it off AND against the
-reference-generated fixtures (tests/golden)."""
+reference-generated fixtures (tests/golden).  mmd_head_gemm + mmd_head_gather (P, y from the stored P, end to end) and the direct
+head kernels meet float64 element by element in tests/test_elementwise_fwd_edge_gpu.py, mmd_resample(_stats) and its records in
+tests/test_elementwise_fwd_misc_gpu.py (bounds: tests/errbound_fwd.py).  The rel_l2(y, head_conv) < 2e-5 of test_head_gemm_gather stays the
+check that sees a dropped lo half of the weight pair: the element-wise bound on P cannot (tests/errbound_fwd.py)."""
 import os
 import subprocess
 import sys

@@ -5,7 +5,10 @@ hand-written asm statement (tools/gen_attn_pipe.py).  Same arithmetic in the sam
 tests/test_ops_gpu.py pins against the oracle's attention, unet:221-240, 507-564): the outputs must be BITWISE equal - on circular
 windows with a shift, key counts that are not multiples of 64 (ragged last tile, zero-filled DMA rows), 1 .. 17 key tiles (prologue /
 odd and even pipelined iterations / drain), ragged query tiles, waves without queries, the last group's remainder, and on inputs that
-force the online-softmax rescale."""
+force the online-softmax rescale.
+
+mmd_gn_group is held to rel-L2 and max-scaled tolerances here; its outputs, affine and mr_out meet float64 element by element in
+tests/test_elementwise_fwd_norm_gpu.py."""
 import pytest
 import torch
 

@@ -7,6 +7,7 @@ summation order) against a float64 reduction of the stored values, to fp32 round
 import pytest
 import torch
 
+import errbound_fwd as EF
 from helpers import rel_l2
 
 from mm_diffusion import ops as _ops
@@ -86,6 +87,7 @@ def test_strip_k3_convs_at_128_channels(ops, N, F, HW, Cout, res, form):
         yf = y2.double().view(M // 64, 64, Cout // 4, 4)
         ref = torch.stack([yf.sum((1, 3)), (yf * yf).sum((1, 3))], dim=-1)
         assert float((rec.double() - ref).abs().max() / ref.abs().max()) < 2e-6
+        EF.check_records(rec, EF.record_values(y2), "strip k = 3 records")               # ... and record by record, each with its own bound
 
 
 def test_strip_strided_views(ops):
@@ -171,6 +173,7 @@ def test_strip_output_statistics(ops, M, Cin, Cout, res, gn):
     yf = y1.double().view(M // 64, 64, Q, 4)
     ref = torch.stack([yf.sum((1, 3)), (yf * yf).sum((1, 3))], dim=-1)
     assert float((view.double() - ref).abs().max() / ref.abs().max()) < 2e-6
+    EF.check_records(view, EF.record_values(y1), "strip records")                        # ... and record by record, each with its own bound
     assert float((wide[:, :6] - 7).abs().max()) == 0 and float((wide[:, 6 + Q:] - 7).abs().max()) == 0
     # the next norm's affine from these records == the statistics pass over the stored output
     geom2 = ops.Geom.per_sample(2, M // 2) if (M // 2) % 64 == 0 and Cout % 128 == 0 else None

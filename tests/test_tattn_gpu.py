@@ -8,6 +8,7 @@ against the stored output, (4) bitwise repeatability and batch invariance."""
 import pytest
 import torch
 
+import errbound_fwd as EF
 from helpers import rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -121,6 +122,8 @@ def test_tattn_statistics_records(ops, C):
     want = torch.stack([v.sum(dim=(1, 3, 5)), (v * v).sum(dim=(1, 3, 5))], dim=-1).view(M // 64, C // 4, 2)
     assert torch.isfinite(rec).all()
     assert (rec.double() - want).abs().max().item() <= 1e-5 * want.abs().max().item()
+    # ... and record by record: every (record, quad) pair against float64 sums of its own 256 stored values, with its own bound
+    EF.check_records(rec, y.view(N, F, HW // 4, 4, C // 4, 4).permute(0, 2, 4, 1, 3, 5).reshape(M // 64, C // 4, 256), "tattn records")
     # a per-sample GroupNorm finalised from them = the norm of y
     g2, b2 = torch.ones(C, device="cuda"), torch.zeros(C, device="cuda")
     geom = ops.Geom.per_sample(N, F * HW)

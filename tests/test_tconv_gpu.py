@@ -7,6 +7,7 @@ torch.nn.functional.conv1d in float64; its statistics records (own row order) ag
 import pytest
 import torch
 
+import errbound_fwd as EF
 from helpers import rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -53,6 +54,11 @@ def test_tconv_is_bitwise_conv_gemm_and_matches_torch(ops, N, HW, Cin, Cout):
         assert rel_l2(y1.double().cpu(), ref.cpu().numpy()) < 5e-3
 
 
+def _record_values(y, N, HW, C):
+    """The 256 stored values of every record in the kernel's row order (record n * HW / 4 + (pixel >> 2): 16 frames of 4 pixels)."""
+    return y.view(N, F, HW // 4, 4, C // 4, 4).permute(0, 2, 4, 1, 3, 5).reshape(N * HW // 4, C // 4, 256)
+
+
 def test_tconv_statistics_records(ops):
     N, HW, Cin, Cout = 2, 64, 256, 256
     x, w, b = _case(N, HW, Cin, Cout, 5)
@@ -65,6 +71,8 @@ def test_tconv_statistics_records(ops):
     want = torch.stack([v.sum(dim=(1, 3, 5)), (v * v).sum(dim=(1, 3, 5))], dim=-1).view(M // 64, Cout // 4, 2)
     assert torch.isfinite(rec).all()
     assert (rec.double() - want).abs().max().item() <= 1e-5 * want.abs().max().item()
+    # ... and record by record: every (record, quad) pair against float64 sums of its own 256 stored values, with its own bound
+    EF.check_records(rec, _record_values(y, N, HW, Cout), "tconv records")
     for Cin2, Cout2 in ((384, 384), (512, 512)):                          # 32-channel chunks: one sub-tile per chunk
         x2, w2, b2 = _case(1, 32, Cin2, Cout2, Cin2)
         rec2 = torch.full((F * 32 // 64, Cout2 // 4, 2), float("nan"), device="cuda")
@@ -72,6 +80,7 @@ def test_tconv_statistics_records(ops):
         v2 = y2.double().view(1, F, 8, 4, Cout2 // 4, 4)
         want2 = torch.stack([v2.sum(dim=(1, 3, 5)), (v2 * v2).sum(dim=(1, 3, 5))], dim=-1).view(-1, Cout2 // 4, 2)
         assert (rec2.double() - want2).abs().max().item() <= 1e-5 * want2.abs().max().item()
+        EF.check_records(rec2, _record_values(y2, 1, 32, Cout2), f"tconv records, {Cout2} channels")
 
 
 def test_tconv_batch_invariant_and_strided_views(ops):

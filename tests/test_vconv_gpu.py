@@ -10,6 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F_
 
+import errbound_fwd as EF
 from helpers import rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -99,6 +100,9 @@ def test_vconv_statistics_records(ops):
     r = rec.double().reshape(N, -1, 32, 2)
     assert rel_l2(r[..., 0].sum(1).cpu(), yq.sum(dim=(1, 3)).cpu()) < 1e-5
     assert rel_l2(r[..., 1].sum(1).cpu(), (yq ** 2).sum(dim=(1, 3)).cpu()) < 1e-5
+    # ... and record by record: record (n * H * W / 16 + patch) * 4 + frame group holds 4 frames of a 4 x 4 pixel patch (patches row-major)
+    vals = y.view(N, 4, 4, H // 4, 4, W // 4, 4, 32, 4).permute(0, 3, 5, 1, 7, 2, 4, 6, 8).reshape(M // 64, 32, 256)
+    EF.check_records(rec, vals, "vconv records")
     # and mmd_gn_finalize_stats turns them into the same affine as the statistics pass over y
     gamma, beta = torch.rand(128, device="cuda") + 0.5, torch.randn(128, device="cuda")
     geom = ops.Geom.per_sample(N, 16 * H * W)
