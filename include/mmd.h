@@ -363,6 +363,31 @@ int mmd_attn_bwd_mfma(const void* Q, int64_t ldq, int q_off, const void* KV, int
  * tab3 [3,T] fp32 = alphas_cumprod, alphas_cumprod_prev, alphas_cumprod_next; flags 1 clip, 2 model predicts x0, 4 learned sigma. */
 int mmd_ddim_update(const float* x, const float* model_out, const float* noise, float* out, float* x0_out, const float* tables,
                     const float* tab3, const int64_t* t, int T, int N, int F, int C, int HW, int flags, float eta, void* stream);
+/* Counter-based noise: N(0,1) values that are a pure function of (seed, sample id, draw, stream tag, element), so a sample does not
+ * depend on its batch position, the batch size, the lane or the rank.  Philox4x32-10 (Salmon et al., SC'11; multipliers 0xD2511F53 /
+ * 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85), key = the 64-bit seed, low word first (key: device, 2 words), counter
+ *   c0 = r >> 2   r = the element's index inside its sample in API layout ([F,C,H,W] video, [C,L] audio, [C,H,W] SR image)
+ *   c1 = draw     the loop index t[n] the update kernels read (SpacedDiffusion: the respaced index); 0xFFFFFFFF = x_T
+ *   c2 = sample id  ids[n] (device int64 [N]); the low 32 bits are used and the HOST refuses ids outside [0, 2^32) (mm_diffusion/seeded.py:
+ *                 the library cannot look into device memory without a sync)
+ *   c3 = tag      0 video, 1 audio, 2 SR image, 3 window shifts (host only)
+ * The four output words belong to elements 4 c0 ... 4 c0 + 3 (one Philox evaluation per four outputs); words past the end of a sample
+ * are dropped.  Word w -> u = ((w >> 9) + 0.5) 2^-23 (exact in fp32, inside (0, 1)); words 0, 1 -> z0 = rho cos(2 pi u1), z1 = rho
+ * sin(2 pi u1), rho = sqrt(-2 ln u0), words 2, 3 likewise -> z2, z3: precise logf / sqrtf and sincospif(2 u), no fast intrinsics.
+ * The largest |z| is sqrt(2 * 24 ln 2) = 5.77.  Seed and ids live in device memory so that a captured graph does not bake them in.
+ * mmd_ctr_fill: out [N, per_sample], kind 0 = the fp32 normals, kind 1 = the raw uint32 words (tests, diagnosis); it serves x_T, the
+ * fixed conditioning noise of the replacement loop and the eager noise_source(like) call.  No LDS, no library state. */
+int mmd_ctr_fill(void* out, int kind, const uint32_t* key, const int64_t* ids, int N, int64_t per_sample, uint32_t draw, int tag,
+                 void* stream);
+/* mmd_ddpm_update / mmd_ddim_update with the noise drawn in the kernel from the counter above (draw = t[n]) instead of read from
+ * memory: bitwise the memory form fed with mmd_ctr_fill(kind 0) of the same key, ids, tag and draw.  A thread owns one quad of
+ * consecutive elements of a sample. */
+int mmd_ddpm_update_ctr(const float* x, const float* model_out, const uint32_t* key, const int64_t* ids, int tag, float* out, float* x0_out,
+                        float* mean_out, float* logvar_out, const float* tables, const int64_t* t, int T, int N, int F, int C, int HW,
+                        int flags, void* stream);
+int mmd_ddim_update_ctr(const float* x, const float* model_out, const uint32_t* key, const int64_t* ids, int tag, float* out, float* x0_out,
+                        const float* tables, const float* tab3, const int64_t* t, int T, int N, int F, int C, int HW, int flags, float eta,
+                        void* stream);
 /* out[n,:] = (ca[t_n] a + cb[t_n] b) cs[t_n]: the _predict_* / q_posterior helpers (gd:170-229,345-366); NULL table = 1, b nullable. */
 int mmd_lincomb_t(const float* a, const float* b, float* out, const float* ca, const float* cb, const float* cs, const int64_t* t,
                   int N, int64_t per_sample, void* stream);

@@ -56,28 +56,131 @@ __device__ __forceinline__ R pred_x0_clamped(const DiffusionParams& p, const X0C
 template <typename R>
 __device__ __forceinline__ R post_mean(const PostCoef<R>& q, R x0, R xv) { return q.c1 * x0 + q.c2 * xv; }
 
+// ----------------------------------------------------------------------------- counter-based noise
+// N(0,1) values that are a pure function of (seed, sample id, draw, stream tag, element): Philox4x32-10 (Salmon et al., SC'11) keyed
+// with the 64-bit seed (low word first) on the counter
+//   c0 = r >> 2   r = the element's index inside its sample in API layout     c1 = draw (the loop index t[n]; 0xFFFFFFFF = x_T)
+//   c2 = sample id (low 32 bits of ids[n]; the host refuses ids outside [0, 2^32))   c3 = tag (0 video, 1 audio, 2 SR image, 3 shifts)
+// The four output words belong to elements 4 c0 ... 4 c0 + 3; words past the end of a sample are dropped.  Nothing in the counter
+// depends on the batch position, the batch size, the lane or the rank.  Word w -> u = ((w >> 9) + 0.5) 2^-23, exact in fp32 and inside
+// (0, 1); words (0, 1) and (2, 3) each feed one Box-Muller pair z = sqrt(-2 ln u_a) (cos, sin)(2 pi u_b) through the precise logf /
+// sqrtf and sincospif(2 u_b), whose argument reduction is exact.  u >= 2^-24, so |z| <= sqrt(2 * 24 ln 2) = 5.77.
+// One evaluation costs 20 32-bit multiply pairs (low + high half) for four outputs, next to 16 bytes per element of memory traffic.
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t* w) {
+#pragma unroll
+  for (int round = 0; round < 10; ++round) {
+    const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+    const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    c0 = h1 ^ c1 ^ k0;
+    c1 = l1;
+    c2 = h0 ^ c3 ^ k1;
+    c3 = l0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
+}
+struct CtrKey { const uint32_t* key; const int64_t* ids; int tag; };
+// the words of the quad that starts at element r0 (a multiple of 4) of sample n
+__device__ __forceinline__ void ctr_words(const CtrKey& k, int64_t n, int64_t r0, uint32_t draw, uint32_t* w) {
+  philox4x32_10((uint32_t)(r0 >> 2), draw, (uint32_t)k.ids[n], (uint32_t)k.tag, k.key[0], k.key[1], w);
+}
+__device__ __forceinline__ float ctr_uniform(uint32_t w) { return ((float)(w >> 9) + 0.5f) * 1.1920928955078125e-07f; }
+__device__ __forceinline__ void ctr_box_muller(uint32_t wa, uint32_t wb, float* z) {
+  const float rho = sqrtf(-2.f * logf(ctr_uniform(wa)));
+  float s, c;
+  sincospif(2.f * ctr_uniform(wb), &s, &c);
+  z[0] = rho * c;
+  z[1] = rho * s;
+}
+__device__ __forceinline__ void ctr_normals(const CtrKey& k, int64_t n, int64_t r0, uint32_t draw, float* z) {
+  uint32_t w[4];
+  ctr_words(k, n, r0, draw, w);
+  ctr_box_muller(w[0], w[1], z);
+  ctr_box_muller(w[2], w[3], z + 2);
+}
+
+// Where an update kernel's noise comes from.  A thread owns W consecutive elements of one sample: one element with the noise in memory,
+// one Philox quad with the counter source.  draw() fills z[0 .. W) for the elements r0 ... of sample n (i0 = n per + r0).
+struct NoiseFromMemory {
+  static constexpr int W = 1;
+  const float* noise;
+  __device__ __forceinline__ bool present() const { return noise != nullptr; }
+  __device__ __forceinline__ void draw(int64_t, int64_t, int64_t i0, int, float* z) const { z[0] = noise[i0]; }
+};
+struct NoiseFromCounter {
+  static constexpr int W = 4;
+  CtrKey k;
+  __device__ __forceinline__ bool present() const { return true; }
+  __device__ __forceinline__ void draw(int64_t n, int64_t r0, int64_t, int ti, float* z) const { ctr_normals(k, n, r0, (uint32_t)ti, z); }
+};
+
+// kind 0: fp32 normals, kind 1: the raw words; out [N, per]
+template <int KIND>
+__global__ __launch_bounds__(256) void ctr_fill_kernel(const CtrKey k, uint32_t draw, int64_t per, int N, void* out) {
+  const int64_t ups = (per + 3) / 4, total = ups * N;
+  for (int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x; u < total; u += (int64_t)gridDim.x * 256) {
+    const int64_t n = u / ups, r0 = (u % ups) * 4;
+    const int64_t left = per - r0;
+    uint32_t w[4];
+    if (KIND == 0) {
+      float z[4];
+      ctr_normals(k, n, r0, draw, z);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) w[j] = __float_as_uint(z[j]);
+    } else {
+      ctr_words(k, n, r0, draw, w);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (j < left) ((uint32_t*)out)[n * per + r0 + j] = w[j];
+  }
+}
+static bool ctr_args_ok(const uint32_t* key, const int64_t* ids, int tag) { return key && ids && tag >= 0 && tag <= 3; }
+// a sample's quads are counted in 32 bits
+#define MMD_CTR_MAX_PER ((int64_t)1 << 34)
+
+extern "C" int mmd_ctr_fill(void* out, int kind, const uint32_t* key, const int64_t* ids, int N, int64_t per_sample, uint32_t draw, int tag,
+                            void* stream) {
+  MMD_REQUIRE(out && ctr_args_ok(key, ids, tag) && N > 0 && per_sample > 0 && per_sample <= MMD_CTR_MAX_PER, "ctr_fill: bad argument");
+  MMD_REQUIRE(kind == 0 || kind == 1, "ctr_fill: kind is 0 (fp32 normals) or 1 (uint32 words); got %d", kind);
+  const CtrKey k{key, ids, tag};
+  const dim3 grid(ew_grid((per_sample + 3) / 4 * N));
+  if (kind == 0) return mmd_launch<ctr_fill_kernel<0>>("ctr_fill", grid, dim3(256), 0, (hipStream_t)stream, k, draw, per_sample, N, out);
+  return mmd_launch<ctr_fill_kernel<1>>("ctr_fill", grid, dim3(256), 0, (hipStream_t)stream, k, draw, per_sample, N, out);
+}
+
 // ----------------------------------------------------------------------------- fused DDPM ancestral update
 // out = mean + [t != 0] exp(logvar / 2) noise; x0_out / mean_out / logvar_out optional (p_mean_variance's results)
-__global__ __launch_bounds__(256) void ddpm_update_kernel(const DiffusionParams p, const float* noise, float* out, float* x0_out, float* mean_out,
+template <class Src>
+__global__ __launch_bounds__(256) void ddpm_update_kernel(const DiffusionParams p, const Src src, float* out, float* x0_out, float* mean_out,
                                                           float* logvar_out) {
+  constexpr int W = Src::W;
   const int64_t per = (int64_t)p.F * p.C * p.HW;
-  const int64_t total = per * p.N;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int64_t n = i / per;
-    const ElemAddr a = elem_addr(p, n, i % per);
+  const int64_t ups = (per + W - 1) / W, total = ups * p.N;
+  for (int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x; u < total; u += (int64_t)gridDim.x * 256) {
+    const int64_t n = u / ups, r0 = (u % ups) * W;
     const int ti = (int)p.t[n];
     const X0Coef<float> k = x0_coef<float>(p, ti);
     const PostCoef<float> q = post_coef<float>(p, ti);
-    const float o = p.mo[a.mean];
-    const float logvar = (p.flags & 4) ? range_logvar(p, a, range_logs<float>(p, ti)) : table_row<float>(p, 4, ti);
-    const float xv = p.x[i];
-    const float x0 = pred_x0_clamped(p, k, o, xv);
-    const float mean = post_mean(q, x0, xv);
     const float nz = ti != 0 ? 1.f : 0.f;
-    if (out) out[i] = mean + nz * expf(0.5f * logvar) * noise[i];
-    if (x0_out) x0_out[i] = x0;
-    if (mean_out) mean_out[i] = mean;
-    if (logvar_out) logvar_out[i] = logvar;
+    float z[W] = {};
+    if (out) src.draw(n, r0, n * per + r0, ti, z);
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+      const int64_t r = r0 + j, i = n * per + r;
+      if (r >= per) break;
+      const ElemAddr a = elem_addr(p, n, r);
+      const float o = p.mo[a.mean];
+      const float logvar = (p.flags & 4) ? range_logvar(p, a, range_logs<float>(p, ti)) : table_row<float>(p, 4, ti);
+      const float xv = p.x[i];
+      const float x0 = pred_x0_clamped(p, k, o, xv);
+      const float mean = post_mean(q, x0, xv);
+      if (out) out[i] = mean + nz * expf(0.5f * logvar) * z[j];
+      if (x0_out) x0_out[i] = x0;
+      if (mean_out) mean_out[i] = mean;
+      if (logvar_out) logvar_out[i] = logvar;
+    }
   }
 }
 
@@ -87,8 +190,19 @@ extern "C" int mmd_ddpm_update(const float* x, const float* model_out, const flo
   MMD_REQUIRE(x && model_out && tables && t && T > 0 && N > 0 && F > 0 && C > 0 && HW > 0, "ddpm_update: bad argument");
   MMD_REQUIRE(!out || noise, "ddpm_update: sampling (out != NULL) needs noise");
   const DiffusionParams p{x, model_out, tables, t, T, N, F, C, HW, flags};
-  return mmd_launch<ddpm_update_kernel>("ddpm_update", dim3(ew_grid((int64_t)N * F * C * HW)), dim3(256), 0, (hipStream_t)stream, p, noise, out, x0_out,
-                                        mean_out, logvar_out);
+  return mmd_launch<ddpm_update_kernel<NoiseFromMemory>>("ddpm_update", dim3(ew_grid((int64_t)N * F * C * HW)), dim3(256), 0, (hipStream_t)stream, p,
+                                                         NoiseFromMemory{noise}, out, x0_out, mean_out, logvar_out);
+}
+extern "C" int mmd_ddpm_update_ctr(const float* x, const float* model_out, const uint32_t* key, const int64_t* ids, int tag, float* out,
+                                   float* x0_out, float* mean_out, float* logvar_out, const float* tables, const int64_t* t, int T, int N,
+                                   int F, int C, int HW, int flags, void* stream) {
+  MMD_REQUIRE(x && model_out && tables && t && T > 0 && N > 0 && F > 0 && C > 0 && HW > 0, "ddpm_update_ctr: bad argument");
+  MMD_REQUIRE(ctr_args_ok(key, ids, tag), "ddpm_update_ctr: needs the key, the sample ids and a stream tag in [0, 3]");
+  const int64_t per = (int64_t)F * C * HW;
+  MMD_REQUIRE(per <= MMD_CTR_MAX_PER, "ddpm_update_ctr: sample too large");
+  const DiffusionParams p{x, model_out, tables, t, T, N, F, C, HW, flags};
+  return mmd_launch<ddpm_update_kernel<NoiseFromCounter>>("ddpm_update_ctr", dim3(ew_grid((per + 3) / 4 * N)), dim3(256), 0, (hipStream_t)stream, p,
+                                                          NoiseFromCounter{{key, ids, tag}}, out, x0_out, mean_out, logvar_out);
 }
 
 // Backward of the sampling update through the posterior mean (gradient-guided conditional sampling, gd:722-817):
@@ -125,32 +239,42 @@ extern "C" int mmd_ddpm_update_bwd(const float* x, const float* model_out, const
 //   sigma = eta sqrt((1-ac_prev)/(1-ac)) sqrt(1 - ac/ac_prev),
 //   out = x0 sqrt(ac_prev) + sqrt(1 - ac_prev - sigma^2) eps + [t != 0] sigma noise          (flag 8: reverse ODE with ac_next, no noise)
 // tab3 = [3][T] fp32: alphas_cumprod, alphas_cumprod_prev, alphas_cumprod_next.
-__global__ __launch_bounds__(256) void ddim_update_kernel(const DiffusionParams p, const float* noise, float* out, float* x0_out, const float* tab3,
+// The noise of the forward step is read (or drawn) wherever a source is present; sigma == 0 (eta == 0) multiplies it away.
+template <class Src>
+__global__ __launch_bounds__(256) void ddim_update_kernel(const DiffusionParams p, const Src src, float* out, float* x0_out, const float* tab3,
                                                           float eta) {
+  constexpr int W = Src::W;
   const int64_t per = (int64_t)p.F * p.C * p.HW;
-  const int64_t total = per * p.N;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int64_t n = i / per;
-    const ElemAddr a = elem_addr(p, n, i % per);
+  const int64_t ups = (per + W - 1) / W, total = ups * p.N;
+  for (int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x; u < total; u += (int64_t)gridDim.x * 256) {
+    const int64_t n = u / ups, r0 = (u % ups) * W;
     const int ti = (int)p.t[n];
     const X0Coef<float> k = x0_coef<float>(p, ti);
-    const float o = p.mo[a.mean];
-    const float xv = p.x[i];
-    const float x0 = pred_x0_clamped(p, k, o, xv);
-    const float eps = (k.cr * xv - x0) / k.crm1;
-    float res;
-    if (p.flags & 8) {
-      const float an = tab3[2 * p.T + ti];
-      res = x0 * sqrtf(an) + sqrtf(1.f - an) * eps;
-    } else {
-      const float ab = tab3[ti], ap = tab3[p.T + ti];
-      const float sigma = eta * sqrtf((1.f - ap) / (1.f - ab)) * sqrtf(1.f - ab / ap);
-      const float mean = x0 * sqrtf(ap) + sqrtf(1.f - ap - sigma * sigma) * eps;
-      const float nz = ti != 0 ? 1.f : 0.f;
-      res = mean + nz * sigma * (noise ? noise[i] : 0.f);
+    float z[W] = {};
+    if (!(p.flags & 8) && src.present()) src.draw(n, r0, n * per + r0, ti, z);
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+      const int64_t r = r0 + j, i = n * per + r;
+      if (r >= per) break;
+      const ElemAddr a = elem_addr(p, n, r);
+      const float o = p.mo[a.mean];
+      const float xv = p.x[i];
+      const float x0 = pred_x0_clamped(p, k, o, xv);
+      const float eps = (k.cr * xv - x0) / k.crm1;
+      float res;
+      if (p.flags & 8) {
+        const float an = tab3[2 * p.T + ti];
+        res = x0 * sqrtf(an) + sqrtf(1.f - an) * eps;
+      } else {
+        const float ab = tab3[ti], ap = tab3[p.T + ti];
+        const float sigma = eta * sqrtf((1.f - ap) / (1.f - ab)) * sqrtf(1.f - ab / ap);
+        const float mean = x0 * sqrtf(ap) + sqrtf(1.f - ap - sigma * sigma) * eps;
+        const float nz = ti != 0 ? 1.f : 0.f;
+        res = mean + nz * sigma * z[j];
+      }
+      if (out) out[i] = res;
+      if (x0_out) x0_out[i] = x0;
     }
-    if (out) out[i] = res;
-    if (x0_out) x0_out[i] = x0;
   }
 }
 extern "C" int mmd_ddim_update(const float* x, const float* model_out, const float* noise, float* out, float* x0_out,
@@ -159,8 +283,19 @@ extern "C" int mmd_ddim_update(const float* x, const float* model_out, const flo
   MMD_REQUIRE(x && model_out && tables && tab3 && t && T > 0 && N > 0 && F > 0 && C > 0 && HW > 0, "ddim_update: bad argument");
   MMD_REQUIRE((flags & 8) || eta == 0.f || noise, "ddim_update: eta > 0 needs noise");
   const DiffusionParams p{x, model_out, tables, t, T, N, F, C, HW, flags};
-  return mmd_launch<ddim_update_kernel>("ddim_update", dim3(ew_grid((int64_t)N * F * C * HW)), dim3(256), 0, (hipStream_t)stream, p, noise, out, x0_out, tab3,
-                                        eta);
+  return mmd_launch<ddim_update_kernel<NoiseFromMemory>>("ddim_update", dim3(ew_grid((int64_t)N * F * C * HW)), dim3(256), 0, (hipStream_t)stream, p,
+                                                         NoiseFromMemory{noise}, out, x0_out, tab3, eta);
+}
+extern "C" int mmd_ddim_update_ctr(const float* x, const float* model_out, const uint32_t* key, const int64_t* ids, int tag, float* out,
+                                   float* x0_out, const float* tables, const float* tab3, const int64_t* t, int T, int N, int F, int C,
+                                   int HW, int flags, float eta, void* stream) {
+  MMD_REQUIRE(x && model_out && tables && tab3 && t && T > 0 && N > 0 && F > 0 && C > 0 && HW > 0, "ddim_update_ctr: bad argument");
+  MMD_REQUIRE(ctr_args_ok(key, ids, tag), "ddim_update_ctr: needs the key, the sample ids and a stream tag in [0, 3]");
+  const int64_t per = (int64_t)F * C * HW;
+  MMD_REQUIRE(per <= MMD_CTR_MAX_PER, "ddim_update_ctr: sample too large");
+  const DiffusionParams p{x, model_out, tables, t, T, N, F, C, HW, flags};
+  return mmd_launch<ddim_update_kernel<NoiseFromCounter>>("ddim_update_ctr", dim3(ew_grid((per + 3) / 4 * N)), dim3(256), 0, (hipStream_t)stream, p,
+                                                          NoiseFromCounter{{key, ids, tag}}, out, x0_out, tab3, eta);
 }
 
 // x_t = sqrt_ac[t] x0 + sqrt_1mac[t] eps   (q_sample, multimodal_gaussian_diffusion.py:187-205); tab2 = [2][T]

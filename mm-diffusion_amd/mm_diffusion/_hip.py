@@ -108,6 +108,9 @@ _PROTOS = {
     "mmd_vlb_workspace_bytes": (i64, [i32]),
     "mmd_vlb_terms": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp]),
     "mmd_vlb_terms_bwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
+    "mmd_ctr_fill": (i32, [vp, i32, vp, vp, i32, i64, C.c_uint32, i32, vp]),
+    "mmd_ddpm_update_ctr": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "mmd_ddim_update_ctr": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp]),
 }
 EXPORTS = tuple(_PROTOS)
 

@@ -21,6 +21,7 @@ from . import _hip as H
 from . import ops
 from .multimodal_gaussian_diffusion import (GaussianDiffusion as _Base, LossType, ModelMeanType, ModelVarType,  # noqa: F401
                                             get_named_beta_schedule, betas_for_alpha_bar, mean_flat)
+from .seeded import CounterNoise, TAG_IMAGE
 
 
 def _geom4(x):
@@ -41,8 +42,13 @@ class GaussianDiffusion(_Base):
         F, C, HW = _geom4(x)
         xs = x.float().contiguous()
         res = {k: th.empty_like(xs) for k in want}
-        ops.ddpm_update(xs, model_output, noise, res.get("sample"), tab, t.to(th.int64).contiguous(), F, C, HW, self._flags(clip_denoised),
-                        x0_out=res.get("pred_xstart"), mean_out=res.get("mean"), logvar_out=res.get("log_variance"))
+        outs = dict(x0_out=res.get("pred_xstart"), mean_out=res.get("mean"), logvar_out=res.get("log_variance"))
+        if isinstance(noise, CounterNoise):      # drawn in the kernel: counter (element, t, sample id, TAG_IMAGE)
+            ops.ddpm_update_ctr(xs, model_output, noise.key(xs.device), noise.ids(xs.shape[0], xs.device), TAG_IMAGE, res.get("sample"), tab,
+                                t.to(th.int64).contiguous(), F, C, HW, self._flags(clip_denoised), **outs)
+        else:
+            ops.ddpm_update(xs, model_output, noise, res.get("sample"), tab, t.to(th.int64).contiguous(), F, C, HW, self._flags(clip_denoised),
+                            **outs)
         return res
 
     def p_mean_variance(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None):
@@ -63,8 +69,11 @@ class GaussianDiffusion(_Base):
         H.require_cuda(x)
         mo = self._model_out(model, x, t, model_kwargs)
         if noise is None:
-            noise = self._randn_like(x)
-        r = self._upd(mo, x, t, clip_denoised, noise.float().contiguous(), ("sample", "pred_xstart"))
+            ctr = self._counter()
+            noise = self._randn_like(x) if ctr is None else ctr
+            if ctr is not None:
+                ctr.set_draw(t)
+        r = self._upd(mo, x, t, clip_denoised, noise if isinstance(noise, CounterNoise) else noise.float().contiguous(), ("sample", "pred_xstart"))
         return {"sample": r["sample"], "pred_xstart": r["pred_xstart"]}
 
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, device=None,
@@ -82,7 +91,7 @@ class GaussianDiffusion(_Base):
             raise NotImplementedError("cond_fn is not built for the SR stage")
         device = self._sampling_device(device)
         assert isinstance(shape, (tuple, list))
-        img = noise if noise is not None else th.randn(*shape, device="cpu").to(device)
+        img = noise if noise is not None else self._start_noise(shape, TAG_IMAGE, device)
         for i in self._indices(progress):
             t = th.tensor([i] * shape[0], device=device)
             with th.no_grad():
@@ -99,8 +108,14 @@ class GaussianDiffusion(_Base):
         tab, _ = self.device_tables(x.device)
         F, C, HW = _geom4(x)
         xs = x.float().contiguous()
-        noise = self._randn_like(xs).float().contiguous()
         out, x0 = th.empty_like(xs), th.empty_like(xs)
+        ctr = self._counter()
+        if ctr is not None:
+            ctr.set_draw(t)
+            ops.ddim_update_ctr(xs, mo, ctr.key(xs.device), ctr.ids(xs.shape[0], xs.device), TAG_IMAGE, out, tab, self.ddim_tables(xs.device),
+                                t.to(th.int64).contiguous(), F, C, HW, self._flags(clip_denoised), eta, x0_out=x0)
+            return {"sample": out, "pred_xstart": x0}
+        noise = self._randn_like(xs).float().contiguous()
         ops.ddim_update(xs, mo, noise, out, tab, self.ddim_tables(xs.device), t.to(th.int64).contiguous(), F, C, HW, self._flags(clip_denoised),
                         eta, x0_out=x0)
         return {"sample": out, "pred_xstart": x0}
@@ -117,7 +132,7 @@ class GaussianDiffusion(_Base):
                                      device=None, progress=False, eta=0.5):
         device = self._sampling_device(device if device is not None else next(model.parameters()).device)
         assert isinstance(shape, (tuple, list))
-        img = noise if noise is not None else th.randn(*shape, device=device)
+        img = noise if noise is not None else (th.randn(*shape, device=device) if self._counter() is None else self._start_noise(shape, TAG_IMAGE, device))
         for i in self._indices(progress):
             t = th.tensor([i] * shape[0], device=device)
             with th.no_grad():
@@ -202,6 +217,8 @@ class GaussianDiffusion(_Base):
         geom = _geom4(x_start)
         for i in self._indices(False):
             t = th.tensor([i] * N, device=device)
+            if self._counter() is not None:          # the callable form at this index
+                self._counter().set_draw(i)
             noise = self._randn_like(x_start)
             x_t = self.q_sample(x_start, t, noise=noise)
             with th.no_grad():

@@ -116,7 +116,8 @@ class GaussianDiffusion:
         self.posterior_log_variance_clipped = np.log(np.append(self.posterior_variance[1], self.posterior_variance[1:]))
         self.posterior_mean_coef1 = betas * np.sqrt(self.alphas_cumprod_prev) / (1.0 - self.alphas_cumprod)
         self.posterior_mean_coef2 = (1.0 - self.alphas_cumprod_prev) * np.sqrt(alphas) / (1.0 - self.alphas_cumprod)
-        # noise source for sampling: callable(like_tensor) -> N(0,1) tensor; default th.randn_like (gd:453-454)
+        # noise source for sampling: callable(like_tensor) -> N(0,1) tensor; default th.randn_like (gd:453-454).  A seeded.CounterNoise makes
+        # every sample a function of (seed, sample id): x_T, the per-step noise (drawn in the update kernels) and the window shifts
         self.noise_source = None
         self._dev_tables = {}
 
@@ -213,6 +214,19 @@ class GaussianDiffusion:
     def _randn_like(self, x):
         return self.noise_source(x) if self.noise_source is not None else th.randn_like(x)
 
+    def _counter(self):
+        """The noise source if it is a seeded.CounterNoise (x_T, per-step noise and window shifts then come from its counter), else None."""
+        from .seeded import counter_source
+        return counter_source(self)
+
+    def _start_noise(self, shape, tag, device):
+        """x_T of one stream: the counter's X_T draw, else drawn on the CPU and moved like the reference."""
+        ctr = self._counter()
+        if ctr is not None:
+            from .seeded import X_T
+            return ctr.randn(shape, tag, X_T, device)
+        return th.randn(*shape, device="cpu").to(device)
+
     # ------------------------------------------------------------------ q(x_t | x_0)
     def q_sample(self, x_start, t, noise=None):
         """x_t = sqrt(ac_t) x_0 + sqrt(1-ac_t) eps (gd:187-205) as one kernel."""
@@ -242,9 +256,14 @@ class GaussianDiffusion:
         xs = x.float().contiguous()
         mo = model_out.float().contiguous()
         res = {k: th.empty_like(xs) for k in want}
-        ops.ddpm_update(xs, mo, noise, res.get("sample"), tab, t.to(th.int64).contiguous(), F, C, HW,
-                        self._flags(clip_denoised) | (2 if start_x else 0), x0_out=res.get("pred_xstart"), mean_out=res.get("mean"),
-                        logvar_out=res.get("log_variance"))
+        flags = self._flags(clip_denoised) | (2 if start_x else 0)
+        outs = dict(x0_out=res.get("pred_xstart"), mean_out=res.get("mean"), logvar_out=res.get("log_variance"))
+        from .seeded import CounterNoise
+        if isinstance(noise, CounterNoise):      # drawn in the kernel: counter (element, t, sample id, stream)
+            ops.ddpm_update_ctr(xs, mo, noise.key(xs.device), noise.ids(xs.shape[0], xs.device), 0 if key == "video" else 1, res.get("sample"), tab,
+                                t.to(th.int64).contiguous(), F, C, HW, flags, **outs)
+        else:
+            ops.ddpm_update(xs, mo, noise, res.get("sample"), tab, t.to(th.int64).contiguous(), F, C, HW, flags, **outs)
         return res
 
     def p_mean_variance(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None):
@@ -268,10 +287,19 @@ class GaussianDiffusion:
         if cond_fn is not None:
             raise NotImplementedError("cond_fn: the reference's condition_mean raises for the multimodal dict (gd:385 calls dict.float()); not built")
         model_kwargs = model_kwargs or {}
-        video_output, audio_output = model(x["video"], x["audio"], self._scale_timesteps(t), **model_kwargs)
-        noise = {"video": self._randn_like(x["video"]), "audio": self._randn_like(x["audio"])}
-        res = {"sample": {}, "pred_start": {}, "pred_noise": {"video": video_output, "audio": audio_output}}
+        ctr = self._counter()
+        if ctr is not None:                  # the draw of this step; the eager forward takes its window shifts from the counter too
+            ctr.set_draw(t)
+            with ctr.shifting(model):
+                video_output, audio_output = model(x["video"], x["audio"], self._scale_timesteps(t), **model_kwargs)
+        else:
+            video_output, audio_output = model(x["video"], x["audio"], self._scale_timesteps(t), **model_kwargs)
         differentiable = th.is_grad_enabled() and any(v.requires_grad for v in (video_output, audio_output, x["video"], x["audio"]))
+        if ctr is not None and not differentiable:
+            noise = {"video": ctr, "audio": ctr}
+        else:                                # (the differentiable guided step takes the counter's values through the callable form)
+            noise = {"video": self._randn_like(x["video"]), "audio": self._randn_like(x["audio"])}
+        res = {"sample": {}, "pred_start": {}, "pred_noise": {"video": video_output, "audio": audio_output}}
         for key, mo in (("video", video_output), ("audio", audio_output)):
             if differentiable:          # gradient-guided conditional sampling differentiates the step (gd:795-817)
                 from .train_ops import DdpmUpdateFn
@@ -280,22 +308,33 @@ class GaussianDiffusion:
                                              t.to(th.int64).contiguous(), self._flags(clip_denoised), _geom(x[key]))
                 res["sample"][key], res["pred_start"][key] = s_, x0_
                 continue
-            r = self._update(key, mo, x[key], t, clip_denoised, noise=noise[key].float().contiguous(),
+            r = self._update(key, mo, x[key], t, clip_denoised, noise=noise[key] if noise[key] is ctr else noise[key].float().contiguous(),
                              want=("sample", "pred_xstart"), denoised_fn=denoised_fn)
             res["sample"][key], res["pred_start"][key] = r["sample"], r["pred_xstart"]
         return res
 
     # ------------------------------------------------------------------ DDIM
     def _ddim(self, model, x, t, clip_denoised, model_kwargs, eta, reverse):
-        video_output, audio_output = model(x["video"], x["audio"], self._scale_timesteps(t), **(model_kwargs or {}))
+        ctr = None if reverse else self._counter()
+        if ctr is not None:
+            ctr.set_draw(t)
+            with ctr.shifting(model):
+                video_output, audio_output = model(x["video"], x["audio"], self._scale_timesteps(t), **(model_kwargs or {}))
+        else:
+            video_output, audio_output = model(x["video"], x["audio"], self._scale_timesteps(t), **(model_kwargs or {}))
         res = {"sample": {}, "pred_xstart": {}}
         flags = self._flags(clip_denoised) | (8 if reverse else 0)
         for key, mo in (("video", video_output), ("audio", audio_output)):
             tab, _ = self.device_tables(x[key].device)
             F, C, HW = _geom(x[key])
             xs = x[key].float().contiguous()
-            noise = None if reverse else self._randn_like(xs).float().contiguous()      # drawn even when eta == 0 (gd:876-877)
             out, x0 = th.empty_like(xs), th.empty_like(xs)
+            if ctr is not None:
+                ops.ddim_update_ctr(xs, mo.float().contiguous(), ctr.key(xs.device), ctr.ids(xs.shape[0], xs.device), 0 if key == "video" else 1,
+                                    out, tab, self.ddim_tables(xs.device), t.to(th.int64).contiguous(), F, C, HW, flags, eta, x0_out=x0)
+                res["sample"][key], res["pred_xstart"][key] = out, x0
+                continue
+            noise = None if reverse else self._randn_like(xs).float().contiguous()      # drawn even when eta == 0 (gd:876-877)
             ops.ddim_update(xs, mo.float().contiguous(), noise, out, tab, self.ddim_tables(xs.device), t.to(th.int64).contiguous(),
                             F, C, HW, flags, eta, x0_out=x0)
             res["sample"][key], res["pred_xstart"][key] = out, x0
@@ -330,7 +369,7 @@ class GaussianDiffusion:
         if cond_fn is not None or denoised_fn is not None:
             raise NotImplementedError("cond_fn / denoised_fn: see ddim_sample")
         device = self._sampling_device(device)
-        x = {"video": th.randn(*shape["video"], device="cpu").to(device), "audio": th.randn(*shape["audio"], device="cpu").to(device)}
+        x = {"video": self._start_noise(shape["video"], 0, device), "audio": self._start_noise(shape["audio"], 1, device)}
         indices = self._indices(progress)
         from .sampler import GraphStepper, unwrap_unet
         unet = unwrap_unet(model)
@@ -380,7 +419,7 @@ class GaussianDiffusion:
     def _cond_setup(self, shape, noise, model_kwargs, device):
         device = self._sampling_device(device)
         if noise is None:
-            noise = {"video": th.randn(*shape["video"], device="cpu").to(device), "audio": th.randn(*shape["audio"], device="cpu").to(device)}
+            noise = {"video": self._start_noise(shape["video"], 0, device), "audio": self._start_noise(shape["audio"], 1, device)}
         model_kwargs = model_kwargs if model_kwargs is not None else {}
         cond = {k: model_kwargs.pop(k) for k in ("video", "audio") if k in model_kwargs}     # popped like gd:687-691
         return device, noise, model_kwargs, cond
@@ -478,9 +517,7 @@ class GaussianDiffusion:
         if cond_fn is not None:
             raise NotImplementedError("cond_fn: see p_sample")
         device = self._sampling_device(device)
-        video = th.randn(*shape["video"], device="cpu").to(device)
-        audio = th.randn(*shape["audio"], device="cpu").to(device)
-        x = {"video": video, "audio": audio}
+        x = {"video": self._start_noise(shape["video"], 0, device), "audio": self._start_noise(shape["audio"], 1, device)}
         indices = list(range(self.num_timesteps))[::-1]
         if progress:
             from tqdm.auto import tqdm
@@ -589,6 +626,8 @@ class GaussianDiffusion:
             tabs = {k: tuple(th.zeros(B, T, dtype=th.float32, device=device) for _ in range(3)) for k in ("video", "audio")}
             for i in self._indices(False):
                 t = th.tensor([i] * B, device=device)
+                if self._counter() is not None:          # the callable form at this index, as the graph step does
+                    self._counter().set_draw(i)
                 noise = {"video": self._randn_like(x_start["video"]), "audio": self._randn_like(x_start["audio"])}
                 x_t = {k: self.q_sample(x_start[k], t, noise=noise[k]) for k in ("video", "audio")}
                 with th.no_grad():

@@ -977,6 +977,34 @@ def ddim_update(x, model_out, noise, out, tables, tab3, t, F, C, HW, flags, eta,
     return out
 
 
+def ctr_fill(out, kind, key, ids, draw, tag):
+    """out [N, ...] (fp32 for kind 0, int32 / uint32 storage for kind 1) = the counter-based noise of samples `ids` (include/mmd.h:
+    mmd_ctr_fill); key: device uint32[2] (as int32 storage), ids: device int64 [N]."""
+    H.require_cuda(out, key, ids)
+    if ids.dtype != torch.int64 or ids.numel() != out.shape[0] or not out.is_contiguous() or out.element_size() != 4:
+        raise H.MMDError("ctr_fill: needs one int64 id per sample and a contiguous 4-byte output")
+    _dispatch("mmd_ctr_fill", out.data_ptr(), int(kind), key.data_ptr(), ids.data_ptr(), out.shape[0], out[0].numel(), int(draw) & 0xFFFFFFFF,
+              int(tag), meta=("ctr_fill", 0, 4 * out.numel()))
+    return out
+
+
+def ddpm_update_ctr(x, model_out, key, ids, tag, out, tables, t, F, C, HW, flags, x0_out=None, mean_out=None, logvar_out=None):
+    """ddpm_update with the noise drawn in the kernel (counter = (element, t[n], ids[n], tag))."""
+    H.require_cuda(x, model_out, key, ids, out, tables, t)
+    _dispatch("mmd_ddpm_update_ctr", x.data_ptr(), model_out.data_ptr(), key.data_ptr(), ids.data_ptr(), int(tag), H.ptr(out), H.ptr(x0_out),
+              H.ptr(mean_out), H.ptr(logvar_out), tables.data_ptr(), t.data_ptr(), tables.shape[1], x.shape[0], F, C, HW, flags,
+              meta=("ddpm_update_ctr", 0, 12 * x.numel()))
+    return out
+
+
+def ddim_update_ctr(x, model_out, key, ids, tag, out, tables, tab3, t, F, C, HW, flags, eta, x0_out=None):
+    H.require_cuda(x, model_out, key, ids, tables, tab3, t)
+    _dispatch("mmd_ddim_update_ctr", x.data_ptr(), model_out.data_ptr(), key.data_ptr(), ids.data_ptr(), int(tag), H.ptr(out), H.ptr(x0_out),
+              tables.data_ptr(), tab3.data_ptr(), t.data_ptr(), tables.shape[1], x.shape[0], F, C, HW, flags, float(eta),
+              meta=("ddim_update_ctr", 0, 12 * x.numel()))
+    return out
+
+
 def lincomb_t(a, b, out, ca, cb, cs, t):
     """out[n] = (ca[t_n] a[n] + cb[t_n] b[n]) cs[t_n] (None table = 1, b may be None); fp32 contiguous tensors."""
     H.require_cuda(a, out, t)

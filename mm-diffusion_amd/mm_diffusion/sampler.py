@@ -46,7 +46,11 @@ class GraphStepper:
     streams; packed weights are shared) and its own captured graph; the lane graphs are launched on the lanes' private streams,
     forked from and joined to the caller's stream with events.  Every sample's trajectory is independent (GroupNorm / attention
     never mix batch elements, tests: batch sharding is bitwise exact), so the result is identical.  Noise and timestep buffers stay
-    full-batch (lanes read slices), so the RNG stream does not depend on `lanes`.  Default: see default_lanes."""
+    full-batch (lanes read slices), so the RNG stream does not depend on `lanes`.  Default: see default_lanes.
+
+    With a seeded.CounterNoise as the diffusion's noise_source (update "ddpm" / "ddim") the step owns no noise buffers: the graph records
+    mmd_ddpm_update_ctr / mmd_ddim_update_ctr, which draw the noise of (seed, sample id, loop index, stream, element) in the kernel - a
+    lane reads its slice of the sample ids as it reads its slice of the timesteps - and set_step takes the window shifts from the counter."""
 
     def __init__(self, diffusion, unet, batch, device, clip_denoised=True, use_graph=True, update="ddpm", eta=0.0, lanes=None):
         if update not in ("ddpm", "ddim", "vlb"):
@@ -62,8 +66,14 @@ class GraphStepper:
         self.tab, _ = diffusion.device_tables(self.device)
         self.flags = diffusion._flags(clip_denoised)
         self.t_idx = th.zeros(self.N, dtype=th.int64, device=self.device)      # loop index (table row)
-        self.noise_v = th.zeros((self.N,) + tuple(e.x_video.shape[1:]), dtype=th.float32, device=self.device)
-        self.noise_a = th.zeros((self.N,) + tuple(e.x_audio.shape[1:]), dtype=th.float32, device=self.device)
+        from .seeded import counter_source
+        self.ctr = ctr = counter_source(diffusion) if update != "vlb" else None
+        if ctr is not None:
+            self.noise_v = self.noise_a = None
+            self.key, self.ids = ctr.key(self.device), ctr.ids(self.N, self.device)
+        else:
+            self.noise_v = th.zeros((self.N,) + tuple(e.x_video.shape[1:]), dtype=th.float32, device=self.device)
+            self.noise_a = th.zeros((self.N,) + tuple(e.x_audio.shape[1:]), dtype=th.float32, device=self.device)
         # model timestep: SpacedDiffusion maps the loop index to the original step (resp:134-139)
         tmap = getattr(diffusion, "timestep_map", None)
         self.tmap = list(tmap) if tmap is not None else list(range(diffusion.num_timesteps))
@@ -81,7 +91,8 @@ class GraphStepper:
             self._ws = [(ops.vlb_workspace(n, self.device), ops.vlb_workspace(n, self.device)) for _ in self.engs]
         for r, e in enumerate(self.engs):
             sl = slice(r * n, (r + 1) * n)
-            t_idx, nv, na = self.t_idx[sl], self.noise_v[sl], self.noise_a[sl]
+            t_idx = self.t_idx[sl]
+            nv, na = (None, None) if ctr is not None else (self.noise_v[sl], self.noise_a[sl])
             plan = []
             if update == "vlb":
                 pre = []
@@ -102,9 +113,23 @@ class GraphStepper:
                 elif update == "ddim":       # ddim_sample (gd:821-901): same graph, different fused update
                     tab3 = diffusion.ddim_tables(self.device)
                     with ops.on_stream(0):
-                        ops.ddim_update(e.x_video, e.out_video, nv, e.x_video, self.tab, tab3, t_idx, F, C, HW, self.flags, eta)
+                        if ctr is not None:
+                            ops.ddim_update_ctr(e.x_video, e.out_video, self.key, self.ids[sl], 0, e.x_video, self.tab, tab3, t_idx, F, C, HW,
+                                                self.flags, eta)
+                        else:
+                            ops.ddim_update(e.x_video, e.out_video, nv, e.x_video, self.tab, tab3, t_idx, F, C, HW, self.flags, eta)
                     with ops.on_stream(1):
-                        ops.ddim_update(e.x_audio, e.out_audio, na, e.x_audio, self.tab, tab3, t_idx, 1, e.Ca_in, e.L0, self.flags, eta)
+                        if ctr is not None:
+                            ops.ddim_update_ctr(e.x_audio, e.out_audio, self.key, self.ids[sl], 1, e.x_audio, self.tab, tab3, t_idx, 1, e.Ca_in,
+                                                e.L0, self.flags, eta)
+                        else:
+                            ops.ddim_update(e.x_audio, e.out_audio, na, e.x_audio, self.tab, tab3, t_idx, 1, e.Ca_in, e.L0, self.flags, eta)
+                elif ctr is not None:
+                    with ops.on_stream(0):
+                        ops.ddpm_update_ctr(e.x_video, e.out_video, self.key, self.ids[sl], 0, e.x_video, self.tab, t_idx, F, C, HW, self.flags)
+                    with ops.on_stream(1):
+                        ops.ddpm_update_ctr(e.x_audio, e.out_audio, self.key, self.ids[sl], 1, e.x_audio, self.tab, t_idx, 1, e.Ca_in, e.L0,
+                                            self.flags)
                 else:
                     with ops.on_stream(0):
                         ops.ddpm_update(e.x_video, e.out_video, nv, e.x_video, self.tab, t_idx, F, C, HW, self.flags)
@@ -205,13 +230,20 @@ class GraphStepper:
         for up in self._up_tm:
             up.host().fill_(float(tm) * (1000.0 / self.orig_T) if self.use_f32 else int(tm))
             up.push()
-        shifts = self.unet.draw_shifts() if shifts is None else shifts      # one draw per block for the whole batch (unet:619-620)
+        if shifts is None:      # one draw per block for the whole batch (unet:619-620)
+            own = self.ctr is not None and self.unet.shift_source is None      # (a model with a shift_source of its own keeps it)
+            shifts = self.ctr.shifts(i, self.unet) if own else self.unet.draw_shifts()
         for e in self.engs:
             e.set_shifts(shifts)
-        if noise is not None:
+        if self.ctr is not None:
+            if noise is not None:
+                raise H.MMDError("this step draws its noise in the update kernels (CounterNoise): it takes no noise tensors")
+        elif noise is not None:
             self.noise_v.copy_(noise["video"])
             self.noise_a.copy_(noise["audio"])
         elif self.diff.noise_source is not None:
+            if hasattr(self.diff.noise_source, "set_draw"):      # update="vlb" keeps its noise in memory: the callable form at this index
+                self.diff.noise_source.set_draw(int(i))
             self.noise_v.copy_(self.diff.noise_source(self.noise_v))
             self.noise_a.copy_(self.diff.noise_source(self.noise_a))
         else:
