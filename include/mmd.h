@@ -151,6 +151,23 @@ int mmd_gn_conv1x1_stats(int dtype, const void* A, int64_t lda, const float* gn_
                          int64_t rows_per_slice, const void* W, const float* bias, const void* R, int64_t ldr, void* Y, int64_t ldy,
                          int M, int Cout, int Cin, int tile, float* stats, int64_t stats_ld, void* stream);
 
+/* The ResBlock tail of a channel-changing block in ONE launch: out conv of the normalised h plus the 1x1 skip conv of x
+ * (unet:373-388,401,457-483), on the row-strip kernel with two register-stationary operands:
+ *   Y[m, :] = bf16( (W_out . g(h[m, :]) + bias_out) + float( bf16( W_skip . x[m, :] + bias_skip ) ) )
+ *   g(h) = act(h * gn_a[s(m)] + gn_b[s(m)]) on the K1 channels of h only (gn_a / gn_b [S, K1]; act: 0 none, 1 SiLU); x is not normalised.
+ * Bitwise equal to mmd_conv_gemm(x, W_skip, bias_skip) -> sk followed by mmd_gn_conv1x1[_stats](h, ..., R = sk, tile 131): the skip
+ * product has its own accumulator (ascending k), gets its bias and is rounded to bf16 where sk would have been stored, and is added
+ * where the residual is added; the two biases are never pre-added.  The tensor sk, its write, its read and one launch disappear.
+ * stats (nullable) / stats_ld as mmd_gn_conv1x1_stats; the records are folded in the order of the one-fragment K = 128 strip
+ * instance, which is what the two-launch path runs for slices of >= 16384 rows (with shorter slices that path's records differ
+ * in the last bit, Y does not).  bf16; K1 == 128, K2 in {256, 384} (K1 + K2 <= 512: an argument error beyond), Cout % 32 == 0,
+ * Cout <= 2048, rows_per_slice >= 128, S * rows_per_slice == M; pointers and row strides 16-byte multiples, M * ldy * 2 < 4 GB.
+ * Any other shape returns MMD_ERR_UNSUPPORTED: no fallback inside the library. */
+int mmd_gn_conv1x1_skip(int dtype, const void* h, int64_t ldh, const float* gn_a, const float* gn_b, int act, int S,
+                        int64_t rows_per_slice, const void* W_out, const float* bias_out, const void* x, int64_t ldx, int K2,
+                        const void* W_skip, const float* bias_skip, void* Y, int64_t ldy, int M, int Cout, int K1, float* stats,
+                        int64_t stats_ld, void* stream);
+
 /* Spatial 3x3 conv whose input GroupNorm32(+FiLM)(+SiLU) is applied to the staged halo tile in LDS (tile 130, bf16, the nine
  * (0, dh, dw) taps, slices of whole frames): Y = conv3x3(act(A * gn_a[s(m)] + gn_b[s(m)])) + bias (+ R), zero padding of the
  * NORMALISED activation.  Replaces GroupNorm32 -> SiLU -> video_conv_spatial of the ResBlock in_layers (unet:339-340,83-99,

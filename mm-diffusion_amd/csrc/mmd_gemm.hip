@@ -35,6 +35,15 @@ struct ConvGemmParams {
   int taps[27 * 3];
 };
 
+// Second, un-normalised operand of the row-strip kernel's two-operand instances (KS2 > 0: the ResBlock out conv with its 1x1 skip conv
+// in the same launch, mmd_gn_conv1x1_skip).  Its own kernel argument: ConvGemmParams - and with it every other kernel's argument
+// layout - stays as it is.
+struct StripSkipParams {
+  const char* A2; int64_t lda2;              // x [M, 64 * KS2], row stride lda2
+  const char* W2;                            // [Cout][64 * KS2]
+  const float* bias2;                        // [Cout] or null
+};
+
 // ---- producer-side GroupNorm statistics.  The epilogue threads (column group cg = tid % (BN/8), row phase rr = tid / (BN/8)) hold
 // per-record sums over their rows; lanes of a wave that share cg are folded with xor-shuffles, the four waves through `sP`
 // (4 x BM/64 x BN float2; aliases the fp32 staging tile, the caller has a barrier in front), and BM/64 x BN threads write one
@@ -1402,21 +1411,27 @@ __global__ __launch_bounds__(512, 2) void conv_gemm_halo16_kernel(const ConvGemm
   } while (0)
 // s_waitcnt immediate of gfx9: vmcnt(n) lgkmcnt(0), expcnt untouched
 __host__ __device__ constexpr int wait_imm(int vm) { return (vm & 15) | ((vm >> 4) << 14) | 0x0070; }
-template <int KS, int RF, int CC, int GNM, int STM, bool HR>   // HR: residual operand (compile time: behind a runtime branch hipcc waits vmcnt(0) in
+template <int KS, int RF, int CC, int GNM, int STM, bool HR, int KS2 = 0>   // HR: residual operand (compile time: behind a runtime branch hipcc waits vmcnt(0) in
                                              // front of EVERY use of the residual registers, i.e. for the acknowledgement of the store issued just before). STM: output statistics 0 none / 1 quad records (compile
                                              // time: the runtime branches cost the K = 128 instance 30 spilled registers).  GNM: 0 no GroupNorm, 1 fused affine, 2 fused affine + SiLU (compile time: two copies of the
                                              // normalisation in one kernel spill ~100 registers around the branch)
-__device__ __forceinline__ void conv1x1_strip_body(const ConvGemmParams& p, const int nsplit) {
+                                             // KS2: 64-channel planes of a SECOND operand x with its own weights and bias (0: none).  y = bf16((W . g(h) + b) + float(bf16(W2 . x + b2))): the
+                                             // second product runs in its own accumulator in ascending k order, gets its bias and its bf16 rounding where a separate launch would have
+                                             // stored it, and is added where the residual is added: bitwise the two launches (conv_gemm, then this kernel with R = its output)
+__device__ __forceinline__ void conv1x1_strip_body(const ConvGemmParams& p, const int nsplit, const StripSkipParams& q) {
   constexpr int K = 64 * KS;                 // input channels
+  constexpr int K2 = 64 * KS2, NCG2 = 4 * KS2;      // second operand: channels, k-steps
   constexpr int NCG = 4 * KS;                // 16-channel k-steps (one MFMA each)
   constexpr int BR = 128 * RF;               // rows per block: 4 waves x RF fragments of 32 rows
   constexpr int NA = CC / 32;                // 32-channel output sub-tiles per chunk
   constexpr int GP = CC / 32;                // weight DMA instructions per wave per 64-channel plane (CC / 8 row groups over 4 waves)
-  constexpr int PLANE_B = CC * 128, STAGE_B = KS * PLANE_B;
+  constexpr int PLANE_B = CC * 128, STAGE_B = (KS + KS2) * PLANE_B;      // a stage holds the KS planes of W, then the KS2 planes of W2
   // software-pipelined sub-tile loop (below): the instances whose launches run one workgroup per CU (K >= 256: the ds2 / ds4 / ds8 levels; the K = 128
   // launches of the ds1 level put 3 - 4 workgroups on a CU and the hardware overlaps their waves).  K = 256 with a residual does not fit the
   // register file (two accumulator sets + the rows' 128 operand registers + the residual pieces: ~45 spilled registers)
   constexpr bool PIPE = KS >= 4 && !(KS == 4 && HR);
+  // two operands: the plain chunk loop only (the pipelined loop's vmcnt values are counted for one operand and one residual)
+  static_assert(KS2 == 0 || (!PIPE && !HR && RF == 1 && GNM != 0 && (KS + KS2) * 16 <= 128), "two-operand instances: K1 = 128, one fragment, no residual");
   constexpr bool DEFER = KS > 2 || RF == 1;  // K = 128 / 256 with two fragments: 1-4 chunks per block, the 16 registers buy a third wave per SIMD
   static_assert(RF == 2 || CC == 32, "one row fragment per wave: one sub-tile per chunk, deferred epilogue");
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1438,18 +1453,21 @@ __device__ __forceinline__ void conv1x1_strip_body(const ConvGemmParams& p, cons
   const int Cs = p.Cout / nsplit, cbase = sp * Cs, nchunk = Cs / CC;
   const int m0 = mt * BR;
   float* sBias = (float*)(smem + 2 * STAGE_B);          // [Cs] bias of this block's column range
-  float* sGN = sBias + ((Cs + 3) & ~3);                 // [2 slices][a | b][K] fused GroupNorm affine
+  float* sBias2 = sBias + ((Cs + 3) & ~3);              // KS2 > 0: [Cs] bias of the second product (its own row: the two are rounded apart)
+  float* sGN = sBias2 + (KS2 > 0 ? (Cs + 3) & ~3 : 0);  // [2 slices][a | b][K] fused GroupNorm affine (the K channels of A only)
   float* sRec = sGN + (GNM != 0 ? 4 * K : 0);           // RF = 1: [2 chunk parities][4 waves][NA * 2][32] half-record statistics
 
   typedef const __attribute__((address_space(1))) void* gptr_t;
   typedef __attribute__((address_space(3))) void* lptr_t;
   const int lrow = lane >> 3, pc = lane & 7;
   const char* w_ptr[GP];
+  const char* w2_ptr[KS2 > 0 ? GP : 1];
 #pragma unroll
   for (int ih = 0; ih < GP; ++ih) {
     const int row = 8 * (ih * 4 + wave) + lrow;          // row of the chunk this lane fetches 16 bytes of
     const int logical = pc ^ ((row >> 1) & 7);
     w_ptr[ih] = p.W + ((int64_t)(cbase + row) * K + logical * 8) * 2;
+    if constexpr (KS2 > 0) w2_ptr[ih] = q.W2 + ((int64_t)(cbase + row) * K2 + logical * 8) * 2;
   }
   const unsigned lds0 = (unsigned)(uintptr_t)(lptr_t)sW;
   auto issue = [&](int stage, int ci) {
@@ -1464,6 +1482,15 @@ __device__ __forceinline__ void conv1x1_strip_body(const ConvGemmParams& p, cons
         // issue (= the prefetch).  Untracked VMEM instructions only make the compiler's own counted waits conservative (in-order return).
         asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off"
                      :: "v"(w_ptr[ih] + off + pl * 128), "s"(lds0 + stage * STAGE_B + pl * PLANE_B + (ih * 4 + wave) * 1024) : "memory", "m0");
+    if constexpr (KS2 > 0) {
+      const int64_t off2 = (int64_t)ci * CC * K2 * 2;
+#pragma unroll
+      for (int pl = 0; pl < KS2; ++pl)
+#pragma unroll
+        for (int ih = 0; ih < GP; ++ih)
+          asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off"
+                       :: "v"(w2_ptr[ih] + off2 + pl * 128), "s"(lds0 + stage * STAGE_B + (KS + pl) * PLANE_B + (ih * 4 + wave) * 1024) : "memory", "m0");
+    }
   };
 
   issue(0, 0);
@@ -1503,6 +1530,13 @@ __device__ __forceinline__ void conv1x1_strip_body(const ConvGemmParams& p, cons
       }
     }
   }
+  // the second operand's rows, loaded like the first's (RF = 1): plain loads, all in flight before the first barrier; never normalised
+  u32x4 xb[KS2 > 0 ? NCG2 : 1];
+  if constexpr (KS2 > 0) {
+    const char* ap = q.A2 + ((int64_t)rowc[0] * q.lda2 + half * 8) * 2;
+#pragma unroll
+    for (int cg = 0; cg < NCG2; ++cg) xb[cg] = *(const u32x4*)(ap + cg * 32);
+  }
   // bias of the column range and the GroupNorm affine rows of the (at most two) slices of the strip -> LDS.  All global loads
   // first (branch-free: clamped indices, the zero page when there is no bias), then the LDS writes: one round trip for everything
   constexpr bool gn = GNM != 0;
@@ -1512,6 +1546,13 @@ __device__ __forceinline__ void conv1x1_strip_body(const ConvGemmParams& p, cons
     const int bmul = p.bias ? 1 : 0;
 #pragma unroll
     for (int i = 0; i < 8; ++i) bias_v[i] = bsrc[min(tid + 256 * i, Cs - 1) * bmul];
+  }
+  float bias2_v[KS2 > 0 ? 8 : 1];
+  if constexpr (KS2 > 0) {
+    const float* bsrc = q.bias2 ? q.bias2 + cbase : (const float*)g_zero_page;
+    const int bmul = q.bias2 ? 1 : 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) bias2_v[i] = bsrc[min(tid + 256 * i, Cs - 1) * bmul];
   }
   int gsel[RF];
 #pragma unroll
@@ -1533,6 +1574,11 @@ __device__ __forceinline__ void conv1x1_strip_body(const ConvGemmParams& p, cons
 #pragma unroll
   for (int i = 0; i < 8; ++i)
     if (tid + 256 * i < Cs) sBias[tid + 256 * i] = bias_v[i];
+  if constexpr (KS2 > 0) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+      if (tid + 256 * i < Cs) sBias2[tid + 256 * i] = bias2_v[i];
+  }
   if (gn) {
 #pragma unroll
     for (int e = 0; e < KS; ++e) sGN[tid + 256 * e] = tv[e];
@@ -1800,6 +1846,18 @@ __device__ __forceinline__ void conv1x1_strip_body(const ConvGemmParams& p, cons
 #pragma unroll
           for (int f = 0; f < RF; ++f) Mma<__bf16>::run(fw, xa[f][4 * pl + c], acc[f]);
         }
+      f32x16 acc2;                                       // the second product: its own accumulator, ascending k
+      if constexpr (KS2 > 0) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc2[r] = 0.f;
+#pragma unroll
+        for (int pl = 0; pl < KS2; ++pl)
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            const u32x4 fw = *(const u32x4*)(bW + (KS + pl) * PLANE_B + (((2 * c + half) ^ xsw) * 16));
+            Mma<__bf16>::run(fw, xb[4 * pl + c], acc2);
+          }
+      }
       // acc[f][4 q + j] = channel 8 q + 4 half + j of row l31.  Pair q = 2 j2 (vdst) with q = 2 j2 + 1 (src): afterwards this lane
       // holds the 8 consecutive channels 16 j2 + 8 half .. + 8 of its row
 #pragma unroll
@@ -1824,6 +1882,19 @@ __device__ __forceinline__ void conv1x1_strip_body(const ConvGemmParams& p, cons
           if constexpr (HR) {
             float rf[8];
             Elt<__bf16>::unpack(rres[f][j2], rf);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] += rf[j];
+          }
+          if constexpr (KS2 > 0) {                       // + float(bf16(W2 . x + b2)): the tensor the separate launch stores, then the residual add
+            const f32x4 c0 = *(const f32x4*)(sBias2 + cb + 16 * j2 + 8 * half), c1 = *(const f32x4*)(sBias2 + cb + 16 * j2 + 8 * half + 4);
+            float s[8], rf[8];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc2[8 * j2 + j]), __float_as_uint(acc2[8 * j2 + 4 + j]), false, false);
+              s[j] = __uint_as_float(sw[0]) + c0[j];
+              s[4 + j] = __uint_as_float(sw[1]) + c1[j];
+            }
+            Elt<__bf16>::unpack(Elt<__bf16>::pack(s), rf);
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] += rf[j];
           }
@@ -1889,18 +1960,21 @@ __device__ __forceinline__ void conv1x1_strip_body(const ConvGemmParams& p, cons
 #define STRIP_LAUNCH_BOUNDS __launch_bounds__(256, (KS <= 2 ? (RF == 1 ? 4 : 3) : 2))
 template <int KS, int RF, int CC, int GNM, int STM>
 __global__ STRIP_LAUNCH_BOUNDS void conv1x1_strip_kernel(const ConvGemmParams p, const int nsplit) {
-  conv1x1_strip_body<KS, RF, CC, GNM, STM, false>(p, nsplit);
+  conv1x1_strip_body<KS, RF, CC, GNM, STM, false>(p, nsplit, StripSkipParams{});
 }
 // with a residual operand: v[248:255] are not the compiler's (STRIP_RES_LOAD / STRIP_RES_WAIT above)
 template <int KS, int RF, int CC, int GNM, int STM>
 __global__ STRIP_LAUNCH_BOUNDS __attribute__((amdgpu_num_vgpr(248))) void conv1x1_strip_res_kernel(const ConvGemmParams p, const int nsplit) {
-  conv1x1_strip_body<KS, RF, CC, GNM, STM, true>(p, nsplit);
+  conv1x1_strip_body<KS, RF, CC, GNM, STM, true>(p, nsplit, StripSkipParams{});
+}
+// two operands (mmd_gn_conv1x1_skip): K1 = 128 normalised + 64 * KS2 plain channels, one row fragment per wave, 32-channel chunks.  The rows'
+// (2 + KS2) * 16 operand registers and the (2 + KS2)-plane weight ring are at most what <8, 1, 32> holds: two workgroups per CU
+template <int KS2, int GNM, int STM>
+__global__ __launch_bounds__(256, 2) void conv1x1_strip_skip_kernel(const ConvGemmParams p, const int nsplit, const StripSkipParams q) {
+  conv1x1_strip_body<2, 1, 32, GNM, STM, false, KS2>(p, nsplit, q);
 }
 
-template <int KS, int RF, int CC, int GNM, int STM, bool HR>
-static int launch_conv1x1_strip_res(const ConvGemmParams& p, hipStream_t st) {
-  constexpr int BR = 128 * RF, STAGE_B = KS * CC * 128;
-  const int rowblocks = cdiv(p.M, BR), nch = p.Cout / CC;
+static int strip_nsplit(int rowblocks, int nch) {
   // column split: the smallest divisor of the chunk count that gives the chip ONE block per CU (the strip's rows are then loaded nsplit
   // times, from L2 after the first); results do not depend on it.  256 since round 5 (448 = ~1.75 blocks per CU before): a launch of the
   // small levels that fills BOTH block slots of every CU leaves no room for the other launch chain's blocks, and the two chains' small,
@@ -1914,6 +1988,13 @@ static int launch_conv1x1_strip_res(const ConvGemmParams& p, hipStream_t st) {
       nsplit = d;
       if ((int64_t)rowblocks * d >= want_blocks) break;
     }
+  return nsplit;
+}
+
+template <int KS, int RF, int CC, int GNM, int STM, bool HR>
+static int launch_conv1x1_strip_res(const ConvGemmParams& p, hipStream_t st) {
+  constexpr int BR = 128 * RF, STAGE_B = KS * CC * 128;
+  const int rowblocks = cdiv(p.M, BR), nsplit = strip_nsplit(rowblocks, p.Cout / CC);
   const int Cs = p.Cout / nsplit;
   constexpr size_t REC_B = RF == 1 ? 2 * 4 * (CC / 32) * 2 * 32 * sizeof(float) : 0;
   const size_t lds = 2 * (size_t)STAGE_B + (size_t)((Cs + 3) & ~3) * 4 + (p.gn_a ? 4 * (size_t)(64 * KS) * 4 : 0) + REC_B;
@@ -1962,6 +2043,25 @@ static int dispatch_conv1x1_strip(const ConvGemmParams& p, hipStream_t st) {
   if (K == 256) return launch_conv1x1_strip<4, 2, 64>(p, st);
   if (K == 384) return launch_conv1x1_strip<6, 1, 32>(p, st);
   return launch_conv1x1_strip<8, 1, 32>(p, st);
+}
+
+template <int KS2, int GNM, int STM>
+static int launch_conv1x1_strip_skip(const ConvGemmParams& p, const StripSkipParams& q, hipStream_t st) {
+  constexpr int STAGE_B = (2 + KS2) * 32 * 128;
+  const int rowblocks = cdiv(p.M, 128), nsplit = strip_nsplit(rowblocks, p.Cout / 32);
+  const int Cs = p.Cout / nsplit;
+  constexpr size_t REC_B = 2 * 4 * 2 * 32 * sizeof(float);
+  const size_t lds = 2 * (size_t)STAGE_B + 2 * (size_t)((Cs + 3) & ~3) * 4 + 4 * 128 * 4 + REC_B;      // ring | two bias rows | affine tables | records
+  const size_t lds_max = 2 * (size_t)STAGE_B + 2 * 2048 * 4 + 4 * 128 * 4 + REC_B;
+  if (lds > lds_max) return mmd_set_error(MMD_ERR_UNSUPPORTED, "gn_conv1x1_skip: %d output channels per block", Cs);
+  return mmd_launch_cap<conv1x1_strip_skip_kernel<KS2, GNM, STM>>("conv1x1_strip_skip", dim3(rowblocks * nsplit), dim3(256), lds, lds_max, st, p, nsplit, q);
+}
+
+template <int KS2>
+static int dispatch_conv1x1_strip_skip(const ConvGemmParams& p, const StripSkipParams& q, hipStream_t st) {
+  if (p.stats)
+    return p.gn_act ? launch_conv1x1_strip_skip<KS2, 2, 1>(p, q, st) : launch_conv1x1_strip_skip<KS2, 1, 1>(p, q, st);
+  return p.gn_act ? launch_conv1x1_strip_skip<KS2, 2, 0>(p, q, st) : launch_conv1x1_strip_skip<KS2, 1, 0>(p, q, st);
 }
 
 template <typename T, bool GN>
@@ -2150,3 +2250,40 @@ extern "C" int mmd_gn_conv_gemm(int dtype, const void* A, int64_t lda, const flo
                         rows_per_slice, nullptr, 0, stream);
 }
 
+
+// ResBlock out conv and its 1x1 skip conv in one launch (row-strip kernel, two operands):
+//   Y[m, :] = bf16((W_out . g(h[m, :]) + bias_out) + float(bf16(W_skip . x[m, :] + bias_skip)))
+// g = the fused GroupNorm affine (+SiLU) on the K1 channels of h only; x is not normalised.  Bitwise what mmd_conv_gemm(x, W_skip, bias_skip) -> sk
+// followed by mmd_gn_conv1x1[_stats](h, ..., R = sk, tile 131) produce, Y and statistics records alike, on the layers whose out conv runs the
+// one-fragment K = 128 strip instance (slices of >= 16384 rows; with shorter slices Y is still bitwise equal, the records are folded in the
+// one-fragment order).  stats may be null (no records).  No fallback: shapes outside K1 = 128, K2 in {256, 384}, Cout % 32 == 0 are refused.
+extern "C" int mmd_gn_conv1x1_skip(int dtype, const void* h, int64_t ldh, const float* gn_a, const float* gn_b, int act, int S,
+                                   int64_t rows_per_slice, const void* W_out, const float* bias_out, const void* x, int64_t ldx, int K2,
+                                   const void* W_skip, const float* bias_skip, void* Y, int64_t ldy, int M, int Cout, int K1, float* stats,
+                                   int64_t stats_ld, void* stream) {
+  MMD_REQUIRE(dtype == MMD_BF16 || dtype == MMD_F32, "gn_conv1x1_skip: bad dtype %d", dtype);
+  MMD_REQUIRE(h && x && W_out && W_skip && Y && gn_a && gn_b && M > 0 && Cout > 0 && K1 > 0 && K2 > 0, "gn_conv1x1_skip: null/empty argument");
+  MMD_REQUIRE(K1 % 8 == 0 && K2 % 8 == 0 && Cout % 8 == 0, "gn_conv1x1_skip: K1 %d, K2 %d, Cout %d must be multiples of 8", K1, K2, Cout);
+  MMD_REQUIRE(K1 + K2 <= 512, "gn_conv1x1_skip: K1 + K2 = %d exceeds the 512 register-stationary channels of a row strip", K1 + K2);
+  MMD_REQUIRE(ldh % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0 && ldh >= K1 && ldx >= K2 && ldy >= Cout, "gn_conv1x1_skip: row strides must be 16-byte multiples that cover the row");
+  MMD_REQUIRE(((uintptr_t)h | (uintptr_t)x | (uintptr_t)W_out | (uintptr_t)W_skip | (uintptr_t)Y) % 16 == 0, "gn_conv1x1_skip: pointers must be 16-byte aligned");
+  MMD_REQUIRE((int64_t)M * ldy * 2 < 0xffffffffLL, "gn_conv1x1_skip: output offsets must stay below 4 GB");
+  MMD_REQUIRE(S > 0 && rows_per_slice > 0 && (int64_t)S * rows_per_slice == M, "gn_conv1x1_skip: needs contiguous slices covering M (got S=%d rows=%ld M=%d)", S,
+              (long)rows_per_slice, M);
+  MMD_REQUIRE(!stats || (M % 64 == 0 && Cout % 4 == 0 && stats_ld >= Cout / 4 && (uintptr_t)stats % 8 == 0),
+              "gn_conv1x1_skip: output statistics need M %% 64 == 0 and stats_ld >= Cout / 4 (quads)");
+  if (dtype != MMD_BF16 || K1 != 128 || (K2 != 256 && K2 != 384) || Cout % 32 != 0 || Cout > 2048 || rows_per_slice < 128)
+    return mmd_set_error(MMD_ERR_UNSUPPORTED, "gn_conv1x1_skip: needs bf16, K1 == 128, K2 in {256, 384}, Cout %% 32 == 0, Cout <= 2048, slices of >= 128 rows "
+                         "(got dtype=%d K1=%d K2=%d Cout=%d rows=%ld)", dtype, K1, K2, Cout, (long)rows_per_slice);
+  ConvGemmParams p;
+  p.A = (const char*)h; p.lda = ldh; p.W = (const char*)W_out; p.bias = bias_out;
+  p.R = nullptr; p.ldr = 0; p.Y = (char*)Y; p.ldy = ldy;
+  p.M = M; p.Cout = Cout; p.Cin = K1; p.ntaps = 1; p.D0 = p.D1 = p.D2 = 1;
+  p.gn_a = gn_a; p.gn_b = gn_b; p.gn_act = act; p.gn_S = S; p.gn_rows = rows_per_slice;
+  p.stats = stats; p.stats_ld = stats_ld;
+  p.taps[0] = p.taps[1] = p.taps[2] = 0;
+  StripSkipParams q;
+  q.A2 = (const char*)x; q.lda2 = ldx; q.W2 = (const char*)W_skip; q.bias2 = bias_skip;
+  hipStream_t st = (hipStream_t)stream;
+  return K2 == 256 ? dispatch_conv1x1_strip_skip<4>(p, q, st) : dispatch_conv1x1_strip_skip<6>(p, q, st);
+}

@@ -45,6 +45,7 @@ _PROTOS = {
     "mmd_gn_conv1x1": (i32, [i32, vp, i64, vp, vp, i32, i32, i64, vp, vp, vp, i64, vp, i64, i32, i32, i32, i32, vp]),
     "mmd_conv_gemm_stats": (i32, [i32, vp, i64, vp, vp, vp, i64, vp, i64, i32, i32, i32, i32, C.POINTER(i32), i32, i32, i32, i32, vp, i64, vp]),
     "mmd_gn_conv1x1_stats": (i32, [i32, vp, i64, vp, vp, i32, i32, i64, vp, vp, vp, i64, vp, i64, i32, i32, i32, i32, vp, i64, vp]),
+    "mmd_gn_conv1x1_skip": (i32, [i32, vp, i64, vp, vp, i32, i32, i64, vp, vp, vp, i64, i32, vp, vp, vp, i64, i32, i32, i32, vp, i64, vp]),
     "mmd_gn_conv_gemm": (i32, [i32, vp, i64, vp, vp, i32, i32, i64, vp, vp, vp, i64, vp, i64, i32, i32, i32, i32, C.POINTER(i32), i32, i32, i32, i32, vp]),
     "mmd_tconv_weight_bytes": (i64, [i32, i32]),
     "mmd_tconv_pack": (i32, [vp, vp, i32, i32, vp]),

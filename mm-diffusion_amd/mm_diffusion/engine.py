@@ -28,6 +28,7 @@ _POOL_NOREUSE = os.environ.get("MMD_POOL_NOREUSE") == "1"      # diagnostics (to
 _UP_LOWRES = ops._flag("MMD_UP_LOWRES")                   # _res_side
 _CROSS_SERIAL = ops._flag("MMD_CROSS_SERIAL")             # _cross
 _RESAMPLE_STATS = ops._flag("MMD_RESAMPLE_STATS")         # _resample_stats
+_SKIP_FUSE = ops._flag("MMD_SKIP_FUSE")                   # _res_tail
 
 
 class _Pool:
@@ -265,6 +266,30 @@ class UNetEngine:
         self._release(a, b)
         return y
 
+    def _res_tail(self, s, h, xs, geom, film, make_out):
+        """The tail of a ResBlock half: out = out_conv(SiLU(norm(h))) + skip(xs).  make_out() allocates (or returns) the output buffer.
+        A channel-changing block whose shapes the two-operand strip launch takes (ops.skip_fusable: the ds1 level) runs the 1x1 skip conv
+        INSIDE the out conv's launch - the skip tensor is never allocated, written or read back; bitwise the two launches, which every other
+        block (and MMD_SKIP_FUSE=0) still runs."""
+        if s.cin != s.cout and _SKIP_FUSE and ops.skip_fusable(h, xs, s.cout, geom):
+            dest = make_out()
+            will_emit = True if self._rec_slice(dest)[0] is not None else None      # (as _gn_pw: the launch emits dest's statistics)
+            if ops.skip_fusable(h, xs, s.cout, geom, will_emit, dest):
+                a, b = self._gn_affine(h, s.out_norm, geom, film)
+                (wo, bo), (wk, bk) = self._wb(s.out_conv), self._wb(s.skip)
+                ops.gn_conv1x1_skip(h, a, b, geom, True, self._gemm_w(wo), self._f32(bo), xs, self._gemm_w(wk), self._f32(bk), out=dest,
+                                    stats=self._stats_for(dest))
+                self._release(a, b)
+                return dest
+            sk = self._pw(xs, *self._wb(s.skip))      # (the output buffer's stride or alignment rules the fused launch out)
+        else:
+            sk = self._pw(xs, *self._wb(s.skip)) if s.cin != s.cout else xs
+            dest = make_out()
+        self._gn_pw(h, s.out_norm, geom, True, *self._wb(s.out_conv), film=film, residual=sk, out=dest)
+        if sk is not xs:
+            self._release(sk)
+        return dest
+
     def _pw(self, x, wkey, bkey, residual=None, out=None):
         y = self._alloc(x.shape[0], self.params[wkey].shape[0]) if out is None else out
         return ops.conv_gemm(x, self._gemm_w(wkey), self._f32(bkey), residual=residual, out=y, **self._stats_kw(y))
@@ -415,12 +440,8 @@ class UNetEngine:
 
     def _res_out_low(self, s, x, h, out):
         """Up blocks: skip connection + out_layers at the INPUT resolution, then one upsample writes the result (see _res_side)."""
-        sk = x if s.cin == s.cout else self._pw(x, *self._wb(s.skip))
-        ylow = self._alloc(s.rows_in, s.cout)
-        self._gn_pw(h, s.out_norm, s.gin, True, *self._wb(s.out_conv), film=s.film, residual=sk, out=ylow)
+        ylow = self._res_tail(s, h, x, s.gin, s.film, lambda: self._alloc(s.rows_in, s.cout))
         self._release(h)
-        if sk is not x:
-            self._release(sk)
         dest = self._alloc(s.rows_out, s.cout, stats=True, unit=s.rows_out // self.N) if out is None else out
         ops.resample(ylow, dest, *s.rs, stats=self._resample_stats(dest))
         self._release(ylow)
@@ -440,15 +461,11 @@ class UNetEngine:
             h, xs = hp, xp
         if not s.ss:
             ops.add_rowbias(h, s.film, per)
-        sk = self._pw(xs, *self._wb(s.skip)) if s.cin != s.cout else xs
         # consumer of dest: the spatial-attention norm (per-frame slices), the audio-attention norm or the next block's norm (per sample)
-        dest = self._alloc(s.rows_out, s.cout, stats=True, unit=s.Ho * s.Ho if (s.attn and s.vid) else per) \
-            if (s.attn or out is None) else out
-        self._gn_pw(h, s.out_norm, Geom.per_sample(self.N, per), True, *self._wb(s.out_conv), film=s.film if s.ss else None,
-                    residual=sk, out=dest)
+        dest = self._res_tail(s, h, xs, Geom.per_sample(self.N, per), s.film if s.ss else None,
+                              lambda: self._alloc(s.rows_out, s.cout, stats=True, unit=s.Ho * s.Ho if (s.attn and s.vid) else per)
+                              if (s.attn or out is None) else out)
         self._release(h)
-        if sk is not xs:
-            self._release(sk)
         if xs is not x:
             self._release(xs)
         return self._res_attn(s, dest, out) if s.attn else dest

@@ -573,6 +573,56 @@ def gn_conv1x1(x, a, b, geom: Geom, act, w, bias, residual=None, out=None, tile=
     return out
 
 
+# the library's own A/B switch of the one-fragment K = 128 strip instance (mmd_gemm.hip): with it off the two-launch path folds its
+# records in the two-fragment order and the fused launch below would not be bitwise its equal
+_STRIP_K128_RF1 = os.environ.get("MMD_STRIP_K128_RF1", "1") != "0"
+
+
+def skip_fusable(h, x, cout, geom: Geom, stats=None, out=None):
+    """Whether the ResBlock out conv of h (GroupNorm + SiLU fused) and the 1x1 skip conv of x can run as ONE launch
+    (mmd_gn_conv1x1_skip) that is bitwise equal - Y and statistics records - to conv_gemm(x) followed by gn_conv1x1(h, residual=sk).
+    Layer geometry and alignment only: the layers whose out conv runs the one-fragment K = 128 strip instance today (128 channels into
+    the out conv, per-sample slices of >= 16384 rows, Cout % 32 == 0) with 256 or 384 channels into the skip conv - K1 + K2 <= 512, the
+    operand registers of a row strip.  In the base model: the ds1 level, video and audio."""
+    if h.dtype != torch.bfloat16 or x.dtype != torch.bfloat16 or h.dim() != 2 or x.dim() != 2 or h.shape[0] != x.shape[0]:
+        return False
+    M, K1 = h.shape
+    if K1 != 128 or x.shape[1] not in (256, 384) or cout % 32 or cout > 2048 or not _STRIP_K128_RF1:
+        return False
+    if not (geom.covers(M) and geom.Tn >= 16384) or (stats is not None and M % 64):
+        return False
+    # the two-launch path must be the fused-norm strip launch this one reproduces (MMD_GEMM_STRIP, the fuse / unfuse rule)
+    if not strip_tile_pinned(h, cout, stats=stats, geom=geom) or not gn_fusable(geom, K1, cout, h, stats, act=True):
+        return False
+    ts = (h, x) + (() if out is None else (out,))
+    if any(t.stride(1) != 1 or t.stride(0) % 8 or t.data_ptr() % 16 for t in ts):
+        return False
+    return M * (cout if out is None else out.stride(0)) * 2 < 0xffffffff
+
+
+def gn_conv1x1_skip(h, a, b, geom: Geom, act, w, bias, x, w_skip, bias_skip, out=None, stats=None):
+    """out = (w . act(h * a + b) + bias) + bf16(w_skip . x + bias_skip): the ResBlock out conv with its 1x1 skip conv in the same
+    launch (include/mmd.h: mmd_gn_conv1x1_skip); bitwise conv_gemm(x, w_skip, bias_skip) -> sk, gn_conv1x1(h, ..., residual=sk)."""
+    _chk2d(h)
+    _chk2d(x)
+    M, K1 = h.shape
+    K2 = x.shape[1]
+    Cout = w.shape[0]
+    _chk_conv_w("gn_conv1x1_skip", h, w, 1)
+    _chk_conv_w("gn_conv1x1_skip", x, w_skip, 1)
+    if x.shape[0] != M or w_skip.shape[0] != Cout:
+        raise H.MMDError(f"gn_conv1x1_skip: h {tuple(h.shape)} / x {tuple(x.shape)} / skip weight {tuple(w_skip.shape)} do not match")
+    out = alloc(M, Cout, dtype=h.dtype, device=h.device) if out is None else out
+    _chk2d(out)
+    es = h.element_size()
+    meta = (f"gn_conv1x1_skip<{'bf16' if es == 2 else 'f32'},strip>[M={M},K={K1}+{K2},N={Cout}]", 2 * M * (K1 + K2) * Cout,
+            es * (M * (K1 + K2) + M * Cout + Cout * (K1 + K2)) + 8 * Cout)
+    _dispatch("mmd_gn_conv1x1_skip", H.dt_of(h), h.data_ptr(), h.stride(0), a.data_ptr(), b.data_ptr(), 1 if act else 0, geom.S, geom.Tn,
+              w.data_ptr(), H.ptr(bias), x.data_ptr(), x.stride(0), K2, w_skip.data_ptr(), H.ptr(bias_skip), out.data_ptr(), out.stride(0),
+              M, Cout, K1, *_stats_args(stats, M, Cout), meta=meta)
+    return out
+
+
 # GroupNorm(+FiLM)(+SiLU) of the INPUT of a 3x3 conv applied to the staged halo tile in LDS (mmd_gn_conv_gemm): the gn_apply pass in
 # front of the ResBlock in-convs disappears wherever the conv runs on tile 130.  Bitwise equal to gn_apply + conv_gemm(tile 130), so
 # the switch (MMD_HALO_GN=0: separate pass) is a pure speed choice.
