@@ -405,6 +405,20 @@ int mmd_ddpm_update_ctr(const float* x, const float* model_out, const uint32_t* 
 int mmd_ddim_update_ctr(const float* x, const float* model_out, const uint32_t* key, const int64_t* ids, int tag, float* out, float* x0_out,
                         const float* tables, const float* tab3, const int64_t* t, int T, int N, int F, int C, int HW, int flags, float eta,
                         void* stream);
+/* Masked conditioning of the replacement method (gd:642-720 overwrites a whole stream with q_sample(condition, t, noise = that stream's
+ * x_T) before every step; here any part of it): in place, x = A known + B eps where the mask cell is set; elsewhere x is NOT written.
+ * x / known / noise fp32 [N, F, C, HW] (audio: F = 1, HW = L).  mask uint8, one cell per (frame, position) shared by the channels: element
+ * (n, f, c, p) reads mask[n * mask_stride + f * HW + p]; mask_stride = 0 (one mask for the batch) or F * HW (one per sample); non-zero =
+ * known; mask == NULL = the whole stream.  A, B = tab2[t[n]], tab2[T + t[n]] (mmd_q_sample's table; a t[n] outside [0, T) replaces
+ * nothing), or the host scalars ca, cb with t == NULL.  On known cells the result is bitwise what mmd_q_sample writes.  eps = noise[i], or
+ * (_ctr) the counter normal of (element, draw 0xFFFFFFFF, ids[n], tag): the value mmd_ctr_fill gives the element at the x_T draw, so no
+ * buffer holds the fixed conditioning noise.  noise may be NULL with t == NULL and cb == 0 only: x = ca known (ca = 1: the final paste,
+ * bitwise `known`). */
+int mmd_cond_replace(float* x, const float* known, const float* noise, const uint8_t* mask, int64_t mask_stride, const float* tab2,
+                     const int64_t* t, float ca, float cb, int T, int N, int F, int C, int HW, void* stream);
+int mmd_cond_replace_ctr(float* x, const float* known, const uint32_t* key, const int64_t* ids, int tag, const uint8_t* mask,
+                         int64_t mask_stride, const float* tab2, const int64_t* t, float ca, float cb, int T, int N, int F, int C, int HW,
+                         void* stream);
 /* out[n,:] = (ca[t_n] a + cb[t_n] b) cs[t_n]: the _predict_* / q_posterior helpers (gd:170-229,345-366); NULL table = 1, b nullable. */
 int mmd_lincomb_t(const float* a, const float* b, float* out, const float* ca, const float* cb, const float* cs, const int64_t* t,
                   int N, int64_t per_sample, void* stream);

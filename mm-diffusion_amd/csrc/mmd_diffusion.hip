@@ -299,12 +299,16 @@ extern "C" int mmd_ddim_update_ctr(const float* x, const float* model_out, const
 }
 
 // x_t = sqrt_ac[t] x0 + sqrt_1mac[t] eps   (q_sample, multimodal_gaussian_diffusion.py:187-205); tab2 = [2][T]
+// One element of it, shared with cond_replace_kernel so that both write the same bits.  Under -ffp-contract=fast the compiler fuses ONE
+// of the two products of a x0 + b eps into the sum, and which one depends on the code around the expression; q_sample_kernel has
+// always compiled to a rounded b eps and a fused a x0, and that form is spelled out here (its device code is unchanged by it).
+__device__ __forceinline__ float q_sample_elem(float a, float x0, float b, float eps) { return fmaf(a, x0, b * eps); }
 __global__ __launch_bounds__(256) void q_sample_kernel(const float* __restrict__ x0, const float* __restrict__ eps, float* __restrict__ out,
                                                        const float* __restrict__ tab2, const int64_t* __restrict__ t, int T, int64_t per,
                                                        int64_t total) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     const int ti = (int)t[i / per];
-    out[i] = tab2[ti] * x0[i] + tab2[T + ti] * eps[i];
+    out[i] = q_sample_elem(tab2[ti], x0[i], tab2[T + ti], eps[i]);
   }
 }
 
@@ -313,6 +317,82 @@ extern "C" int mmd_q_sample(const float* x0, const float* eps, float* out, const
   MMD_REQUIRE(x0 && eps && out && tab2 && t && T > 0 && N > 0 && per_sample > 0, "q_sample: bad argument");
   const int64_t total = per_sample * N;
   return mmd_launch<q_sample_kernel>("q_sample", dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, x0, eps, out, tab2, t, T, per_sample, total);
+}
+
+// Replacement-method conditioning with partial masks (the reference overwrites a whole stream before every step, gd:642-720): where a
+// cell of the mask is set, x = A known + B eps in place, q_sample's element; elsewhere x is not written.  x / known (/ noise): fp32
+// [N, F, C, HW]; mask: uint8, one cell per (frame, position) shared by the channels - element (n, f, c, p) reads
+// mask[n * mask_stride + f * HW + p], mask_stride = 0 (one mask for the batch) or F * HW; mask == NULL = the whole stream.
+// A, B = tab2[t[n]], tab2[T + t[n]], or the host scalars ca, cb with t == NULL (a timestep outside [0, T) replaces nothing).
+// eps = noise[i], or the counter's x_T draw of the element: the value mmd_ctr_fill(draw = 0xFFFFFFFF) gives it.  Without a noise tensor
+// (t == NULL, cb == 0) x = ca known, which is `known` bit for bit with ca == 1: the final paste.
+// A thread owns W consecutive elements of a sample like the update kernels; a quad may straddle a mask row, a channel, a frame and the
+// end of the sample, so the cell is tested per element, and a quad with no known element draws nothing.
+#define MMD_CTR_DRAW_X_T (-1)      // NoiseFromCounter::draw casts its int to the 32-bit draw: 0xFFFFFFFF
+struct CondReplaceParams {
+  float* x; const float* known; const uint8_t* mask; int64_t mask_stride; const float* tab2; const int64_t* t;
+  float ca, cb;
+  int T, N, F, C, HW;
+};
+template <class Src>
+__global__ __launch_bounds__(256) void cond_replace_kernel(const CondReplaceParams p, const Src src) {
+  constexpr int W = Src::W;
+  const int64_t chw = (int64_t)p.C * p.HW, per = chw * p.F;
+  const int64_t ups = (per + W - 1) / W, total = ups * p.N;
+  for (int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x; u < total; u += (int64_t)gridDim.x * 256) {
+    const int64_t n = u / ups, r0 = (u % ups) * W;
+    float a = p.ca, b = p.cb;
+    if (p.t) {
+      const int64_t ti = p.t[n];
+      if (ti < 0 || ti >= p.T) continue;
+      a = p.tab2[ti];
+      b = p.tab2[p.T + ti];
+    }
+    bool on[W];
+    bool any = false;
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+      const int64_t r = r0 + j;
+      on[j] = r < per && (!p.mask || p.mask[n * p.mask_stride + (r / chw) * p.HW + r % p.HW] != 0);
+      any = any || on[j];
+    }
+    if (!any) continue;
+    float z[W] = {};
+    if (src.present()) src.draw(n, r0, n * per + r0, MMD_CTR_DRAW_X_T, z);
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+      if (!on[j]) continue;
+      const int64_t i = n * per + r0 + j;
+      p.x[i] = src.present() ? q_sample_elem(a, p.known[i], b, z[j]) : a * p.known[i];
+    }
+  }
+}
+static int cond_replace_args(const char* what, const float* x, const float* known, int64_t mask_stride, const float* tab2, const int64_t* t,
+                             int T, int N, int F, int C, int HW) {
+  MMD_REQUIRE(x && known && (!t || tab2), "%s: needs x and known, and tab2 when t is given", what);
+  MMD_REQUIRE(T > 0 && N > 0 && F > 0 && C > 0 && HW > 0, "%s: T, N, F, C, HW must be positive", what);
+  MMD_REQUIRE(mask_stride == 0 || mask_stride == (int64_t)F * HW, "%s: mask_stride is 0 (one mask for the batch) or F * HW = %ld; got %ld", what,
+              (long)((int64_t)F * HW), (long)mask_stride);
+  return MMD_OK;
+}
+extern "C" int mmd_cond_replace(float* x, const float* known, const float* noise, const uint8_t* mask, int64_t mask_stride, const float* tab2,
+                                const int64_t* t, float ca, float cb, int T, int N, int F, int C, int HW, void* stream) {
+  if (int rc = cond_replace_args("cond_replace", x, known, mask_stride, tab2, t, T, N, F, C, HW)) return rc;
+  MMD_REQUIRE(noise || (!t && cb == 0.f), "cond_replace: noise may be NULL only with t == NULL and cb == 0 (the paste)");
+  const CondReplaceParams p{x, known, mask, mask_stride, tab2, t, ca, cb, T, N, F, C, HW};
+  return mmd_launch<cond_replace_kernel<NoiseFromMemory>>("cond_replace", dim3(ew_grid((int64_t)N * F * C * HW)), dim3(256), 0, (hipStream_t)stream, p,
+                                                          NoiseFromMemory{noise});
+}
+extern "C" int mmd_cond_replace_ctr(float* x, const float* known, const uint32_t* key, const int64_t* ids, int tag, const uint8_t* mask,
+                                    int64_t mask_stride, const float* tab2, const int64_t* t, float ca, float cb, int T, int N, int F, int C,
+                                    int HW, void* stream) {
+  if (int rc = cond_replace_args("cond_replace_ctr", x, known, mask_stride, tab2, t, T, N, F, C, HW)) return rc;
+  MMD_REQUIRE(ctr_args_ok(key, ids, tag), "cond_replace_ctr: needs the key, the sample ids and a stream tag in [0, 3]");
+  const int64_t per = (int64_t)F * C * HW;
+  MMD_REQUIRE(per <= MMD_CTR_MAX_PER, "cond_replace_ctr: sample too large");
+  const CondReplaceParams p{x, known, mask, mask_stride, tab2, t, ca, cb, T, N, F, C, HW};
+  return mmd_launch<cond_replace_kernel<NoiseFromCounter>>("cond_replace_ctr", dim3(ew_grid((per + 3) / 4 * N)), dim3(256), 0, (hipStream_t)stream, p,
+                                                           NoiseFromCounter{{key, ids, tag}});
 }
 
 // out[n, i] = (ca[t_n] a + cb[t_n] b) * cs[t_n]    per-sample coefficients looked up from fp32 tables of length T

@@ -112,6 +112,8 @@ _PROTOS = {
     "mmd_ctr_fill": (i32, [vp, i32, vp, vp, i32, i64, C.c_uint32, i32, vp]),
     "mmd_ddpm_update_ctr": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "mmd_ddim_update_ctr": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp]),
+    "mmd_cond_replace": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, f32, i32, i32, i32, i32, i32, vp]),
+    "mmd_cond_replace_ctr": (i32, [vp, vp, vp, vp, i32, vp, i64, vp, vp, f32, f32, i32, i32, i32, i32, i32, vp]),
 }
 EXPORTS = tuple(_PROTOS)
 

@@ -14,7 +14,9 @@ MI355X-first differences:
     refreshing only the timestep, the window shifts and the noise
   * DDIM (`ddim_sample(_loop)`) rides the same graph with mmd_ddim_update; zero-shot conditional sampling
     (`conditional_p_sample_loop`, gd:584-819) is built for both the replacement and the gradient-guided method
-    (the latter differentiates the HIP training path w.r.t. the target stream's input)
+    (the latter differentiates the HIP training path w.r.t. the target stream's input); `masked_sample_loop` is the replacement
+    method with partial masks (clip continuation, inpainting) on the DDPM or the DDIM stepper, the replacement itself one
+    mmd_cond_replace launch per stream inside the step graph
   * the variational bound in bits / dim (`_vb_terms_bpd`, `_prior_bpd`, `calc_bpd_loop`, gd:1048-1092, 1213-1286) is one
     reduction kernel per stream and step (mmd_vlb_terms) that writes into device result tables; `calc_bpd_loop` replays
     [q_sample + U-Net plan + both reductions] as one hipGraph per step and reads the tables back once.  The reference's
@@ -498,6 +500,77 @@ class GaussianDiffusion:
                 grad = th.autograd.grad(loss.mean() * loss_scale, x[target])[0]
                 x = {condition: x[condition], target: (pred[target] - none_zero_mask * grad * class_scale *
                                                        float(self.sqrt_alphas_cumprod[i])).detach()}
+            yield x
+
+    # ------------------------------------------------------------------ masked conditional sampling
+    def masked_sample_loop(self, model, shape, known, mask=None, *, sampler="ddpm", eta=0.0, noise=None, clip_denoised=True,
+                           model_kwargs=None, device=None, progress=False, paste_known=True, use_graph=True, lanes=None):
+        """The last state of masked_sample_loop_progressive."""
+        final = None
+        for sample in self.masked_sample_loop_progressive(model, shape, known, mask, sampler=sampler, eta=eta, noise=noise,
+                                                          clip_denoised=clip_denoised, model_kwargs=model_kwargs, device=device,
+                                                          progress=progress, paste_known=paste_known, use_graph=use_graph, lanes=lanes):
+            final = sample
+        return final
+
+    def masked_sample_loop_progressive(self, model, shape, known, mask=None, *, sampler="ddpm", eta=0.0, noise=None, clip_denoised=True,
+                                       model_kwargs=None, device=None, progress=False, paste_known=True, use_graph=True, lanes=None):
+        """The replacement method (gd:642-720) with partial masks, for the DDPM and the DDIM stepper.  known: {"video": [B,F,C,H,W],
+        "audio": [B,C,L]}, either or both; mask: the known cells of these streams (masking.normalize has the shapes; a stream without a
+        mask is known as a whole).  Before every step the known cells are set to q_sample(known, t, noise = that stream's x_T) by one
+        mmd_cond_replace per stream - in front of the U-Net plan inside the step graph - then one ordinary p_sample (sampler="ddpm") or
+        ddim_sample ("ddim", eta) follows, the reference's order.  With paste_known the LAST yielded state carries `known` itself on
+        its known cells; the states before it are the raw step outputs.  noise: an optional x_T dict that doubles as the fixed
+        conditioning noise; with a seeded.CounterNoise source x_T, the conditioning noise (regenerated in the kernel, no buffer) and the
+        per-step noise all come from the counter and `noise` must be None."""
+        from . import masking
+        from .sampler import GraphStepper, unwrap_unet
+        if sampler not in ("ddpm", "ddim"):
+            raise H.MMDError(f"masked_sample_loop: unknown sampler {sampler!r} (ddpm or ddim)")
+        device = self._sampling_device(device)
+        cond = masking.normalize(known, mask, shape)
+        for k, c in cond.items():
+            H.require_cuda(c.known)
+            cond[k] = c._replace(known=c.known.to(device), mask=None if c.mask is None else c.mask.to(device))
+        ctr = self._counter()
+        if ctr is not None and noise is not None:
+            raise H.MMDError("masked_sample_loop: a CounterNoise source draws x_T and the conditioning noise itself: noise must be None")
+        if noise is None:
+            noise = {"video": self._start_noise(shape["video"], 0, device), "audio": self._start_noise(shape["audio"], 1, device)}
+        noise = {k: noise[k].to(device).float().contiguous() for k in ("video", "audio")}
+        B = shape["video"][0]
+        unet = unwrap_unet(model)
+        model_kwargs = model_kwargs or {}
+        if use_graph and unet is not None and not model_kwargs:
+            stepper = GraphStepper(self, unet, B, device, clip_denoised, update=sampler, eta=eta, lanes=lanes, cond=cond)
+            stepper.load(noise["video"], noise["audio"])
+            stepper.load_cond(cond, noise)
+            try:
+                for i in self._indices(progress):
+                    stepper.step(i)
+                    if paste_known and i == 0:
+                        stepper.paste_known()
+                    yield stepper.current()
+            finally:
+                stepper.close()
+            return
+        _, qtab = self.device_tables(device)
+        x = dict(noise)
+        for i in self._indices(progress):
+            t = th.tensor([i] * B, device=device)
+            x = dict(x)                      # the state yielded last, and at first x_T itself, stay as they are: a new dict, and copies below
+            for k, c in cond.items():
+                x[k] = x[k].clone()
+                src = dict(ctr=(ctr.key(device), ctr.ids(B, device), 0 if k == "video" else 1)) if ctr is not None else dict(noise=noise[k])
+                ops.cond_replace(x[k], c.known, qtab, t, mask=c.mask, **src)
+            with th.no_grad():
+                if sampler == "ddim":
+                    x = self.ddim_sample(model, x, t, clip_denoised=clip_denoised, model_kwargs=model_kwargs, eta=eta)["sample"]
+                else:
+                    x = self.p_sample(model, x, t, clip_denoised=clip_denoised, model_kwargs=model_kwargs)["sample"]
+            if paste_known and i == 0:
+                for k, c in cond.items():
+                    ops.cond_replace(x[k], c.known, None, None, mask=c.mask, coef=(1.0, 0.0))
             yield x
 
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,

@@ -1128,6 +1128,54 @@ def q_sample(x0, eps, out, tab2, t):
     return out
 
 
+def cond_replace(x, known, tab2, t, *, noise=None, ctr=None, mask=None, coef=None):
+    """In place: x = A known + B eps on the known cells of `mask`, the other elements are not written (include/mmd.h: mmd_cond_replace).
+    x / known / noise: fp32 contiguous video [N,F,C,H,W] (or [N,F,C,HW]) or audio [N,C,L].  A, B = tab2[:, t[n]] (tab2: q_sample's [2, T]
+    table, t int64 [N]), or the host pair coef = (ca, cb) with tab2 = t = None.  eps = noise, or with ctr = (key, ids, tag) the counter's
+    x_T draw.  mask: uint8, one cell per (frame, position): [F*HW] cells for the whole batch or [N, F*HW] cells (any shape with that many
+    elements); None = the whole stream.  noise = ctr = None needs coef = (ca, 0): x = ca known."""
+    H.require_cuda(x, known, tab2, t, noise, mask, *(ctr[:2] if ctr is not None else ()))
+    if x.dim() == 5:
+        F, C, HW = x.shape[1], x.shape[2], x.shape[3] * x.shape[4]
+    elif x.dim() == 4:
+        F, C, HW = x.shape[1:]
+    elif x.dim() == 3:
+        F, C, HW = 1, x.shape[1], x.shape[2]
+    else:
+        raise H.MMDError(f"cond_replace: x must be video [N,F,C,H,W] / [N,F,C,HW] or audio [N,C,L], got {tuple(x.shape)}")
+    N = x.shape[0]
+    for name, v in (("x", x), ("known", known), ("noise", noise)):
+        if v is not None and (v.dtype != torch.float32 or not v.is_contiguous() or v.numel() != x.numel()):
+            raise H.MMDError(f"cond_replace: {name} must be contiguous fp32 with the {x.numel()} elements of x")
+    if (t is None) != (tab2 is None) or (t is None) == (coef is None):
+        raise H.MMDError("cond_replace: give either (tab2, t) or coef = (ca, cb)")
+    if t is not None and (t.dtype != torch.int64 or t.numel() != N or not t.is_contiguous() or tab2.dtype != torch.float32 or tab2.dim() != 2 or
+                          tab2.shape[0] != 2 or not tab2.is_contiguous()):
+        raise H.MMDError("cond_replace: needs one contiguous int64 timestep per sample and a contiguous fp32 [2, T] table")
+    ca, cb = (0.0, 0.0) if coef is None else (float(coef[0]), float(coef[1]))
+    if noise is not None and ctr is not None:
+        raise H.MMDError("cond_replace: noise and ctr are two sources for the same eps")
+    if noise is None and ctr is None and (t is not None or cb != 0.0):
+        raise H.MMDError("cond_replace: without a noise source only coef = (ca, 0) is defined")
+    stride = 0
+    if mask is not None:
+        if mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.numel() not in (F * HW, N * F * HW):
+            raise H.MMDError(f"cond_replace: mask must be contiguous uint8 with {F * HW} or {N * F * HW} cells, got {mask.dtype} {tuple(mask.shape)}")
+        stride = F * HW if mask.numel() == N * F * HW else 0
+    T = 1 if tab2 is None else tab2.shape[1]
+    nbytes = (12 if noise is not None else 8) * x.numel()
+    if ctr is not None:
+        key, ids, tag = ctr
+        if ids.dtype != torch.int64 or ids.numel() != N or not ids.is_contiguous():
+            raise H.MMDError("cond_replace: ctr needs one contiguous int64 id per sample")
+        _dispatch("mmd_cond_replace_ctr", x.data_ptr(), known.data_ptr(), key.data_ptr(), ids.data_ptr(), int(tag), H.ptr(mask), stride, H.ptr(tab2),
+                  H.ptr(t), ca, cb, T, N, F, C, HW, meta=("cond_replace_ctr", 0, nbytes))
+    else:
+        _dispatch("mmd_cond_replace", x.data_ptr(), known.data_ptr(), H.ptr(noise), H.ptr(mask), stride, H.ptr(tab2), H.ptr(t), ca, cb, T, N, F, C,
+                  HW, meta=("cond_replace", 0, nbytes))
+    return x
+
+
 def loss_terms(model_out, target, tables, t, F, C, HW, flags, x0=None, xt=None, vb_scale=1.0):
     """Per-sample (mse, vb) of one stream on API-layout fp32 tensors; vb is None without the learned-range flag (4)."""
     H.require_cuda(model_out, target, tables, t)

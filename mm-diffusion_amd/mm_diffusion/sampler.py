@@ -50,11 +50,17 @@ class GraphStepper:
 
     With a seeded.CounterNoise as the diffusion's noise_source (update "ddpm" / "ddim") the step owns no noise buffers: the graph records
     mmd_ddpm_update_ctr / mmd_ddim_update_ctr, which draw the noise of (seed, sample id, loop index, stream, element) in the kernel - a
-    lane reads its slice of the sample ids as it reads its slice of the timesteps - and set_step takes the window shifts from the counter."""
+    lane reads its slice of the sample ids as it reads its slice of the timesteps - and set_step takes the window shifts from the counter.
 
-    def __init__(self, diffusion, unet, batch, device, clip_denoised=True, use_graph=True, update="ddpm", eta=0.0, lanes=None):
+    cond (masking.normalize's result; update "ddpm" / "ddim") conditions the step on known cells: every lane's graph starts with one
+    mmd_cond_replace per conditioned stream, which sets the known cells of the state to q_sample(known, t, noise = that stream's x_T)
+    and leaves the others alone (masked_sample_loop).  cond=None records nothing."""
+
+    def __init__(self, diffusion, unet, batch, device, clip_denoised=True, use_graph=True, update="ddpm", eta=0.0, lanes=None, cond=None):
         if update not in ("ddpm", "ddim", "vlb"):
             raise H.MMDError(f"unknown update {update!r} (ddpm, ddim or vlb)")
+        if cond and update == "vlb":
+            raise H.MMDError("masked conditioning rides the sampling steps (ddpm, ddim), not the variational bound")
         self.diff, self.unet, self.N = diffusion, unet, int(batch)
         self.device = th.device(device)
         self.lanes = default_lanes(self.N) if lanes is None else int(lanes)
@@ -89,10 +95,28 @@ class GraphStepper:
             self.x0_v, self.x0_a = th.zeros_like(self.noise_v), th.zeros_like(self.noise_a)
             self.res = {k: tuple(th.zeros(self.N, T, dtype=th.float32, device=self.device) for _ in range(3)) for k in ("video", "audio")}
             self._ws = [(ops.vlb_workspace(n, self.device), ops.vlb_workspace(n, self.device)) for _ in self.engs]
+        # masked conditioning (masking.normalize): per conditioned stream the static known values, one uint8 mask row per sample (none:
+        # the whole stream) and, without a counter source, the fixed conditioning noise (= that stream's x_T); load_cond fills them
+        self.cond = {}
+        for k, c in (cond or {}).items():
+            xk = e.x_video if k == "video" else e.x_audio
+            buf = {"known": th.zeros((self.N,) + tuple(xk.shape[1:]), dtype=th.float32, device=self.device),
+                   "mask": None if c.mask is None else th.zeros(self.N, F * HW if k == "video" else e.L0, dtype=th.uint8, device=self.device),
+                   "noise": None if ctr is not None else th.zeros((self.N,) + tuple(xk.shape[1:]), dtype=th.float32, device=self.device)}
+            self.cond[k] = buf
+        if self.cond:
+            _, self._qtab = diffusion.device_tables(self.device)
         for r, e in enumerate(self.engs):
             sl = slice(r * n, (r + 1) * n)
             t_idx = self.t_idx[sl]
             nv, na = (None, None) if ctr is not None else (self.noise_v[sl], self.noise_a[sl])
+            if self.cond:
+                pre = []
+                with ops.recording(pre):       # on the origin stream like the vlb pre-plan: the known cells at this step's noise level
+                    for k, tag in (("video", 0), ("audio", 1)):
+                        if k in self.cond:
+                            self._cond_replace(r, k, tag, self._qtab, t_idx, None)
+                self.pre_plans.append(pre)
             plan = []
             if update == "vlb":
                 pre = []
@@ -161,6 +185,38 @@ class GraphStepper:
         """update="vlb": the clean clips every step noises afresh."""
         self.x0_v.copy_(video)
         self.x0_a.copy_(audio)
+
+    def _cond_replace(self, r, k, tag, tab2, t, coef):
+        """ops.cond_replace of stream k on lane r's state and its slices of the conditioning buffers; coef = (ca, cb) draws no noise."""
+        e, sl = self.engs[r], slice(r * self.n, (r + 1) * self.n)
+        b = self.cond[k]
+        src = {}
+        if coef is None:
+            src = dict(ctr=(self.key, self.ids[sl], tag)) if self.ctr is not None else dict(noise=b["noise"][sl])
+        ops.cond_replace(e.x_video if k == "video" else e.x_audio, b["known"][sl], tab2, t, mask=None if b["mask"] is None else b["mask"][sl],
+                         coef=coef, **src)
+
+    def load_cond(self, cond, noise=None):
+        """Fill the conditioning buffers from masking.normalize's result (the streams and the presence of masks as at construction);
+        noise: {stream: x_T}, the fixed conditioning noise - needed unless the kernels draw it from the counter."""
+        if set(cond) != set(self.cond) or any((cond[k].mask is None) != (self.cond[k]["mask"] is None) for k in cond):
+            raise H.MMDError("load_cond: the conditioned streams and their masks' presence are fixed when the stepper is built")
+        for k, c in cond.items():
+            b = self.cond[k]
+            b["known"].copy_(c.known)
+            if c.mask is not None:      # one row per sample: a lane reads its slice whether the caller's mask was shared or not
+                b["mask"].copy_(c.mask.reshape(-1, b["mask"].shape[1]).expand_as(b["mask"]))
+            if b["noise"] is not None:
+                if noise is None or k not in noise:
+                    raise H.MMDError(f"load_cond: the fixed conditioning noise of {k!r} is missing")
+                b["noise"].copy_(noise[k])
+
+    def paste_known(self):
+        """The current state's known cells = the known values, bit for bit (after the last step)."""
+        for r in range(self.lanes):
+            for k, tag in (("video", 0), ("audio", 1)):
+                if k in self.cond:
+                    self._cond_replace(r, k, tag, None, None, (1.0, 0.0))
 
     def results(self):
         """update="vlb": {"video" / "audio": (vb, xstart_mse, eps_mse)} [N, T] tables, column = loop index t."""
