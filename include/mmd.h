@@ -434,6 +434,27 @@ int mmd_ddpm_update_bwd(const float* x, const float* model_out, const float* dsa
  * linear interpolation), exact radix select; then x[n,:] = clamp(x, -s, s) / (s / max_val) with s = max(s_n, 1), in place. */
 int mmd_abs_quantile(const float* x, int N, int64_t per_sample, float q, float* out, void* stream);
 int mmd_clamp_scale(float* x, const float* s, float max_val, int N, int64_t per_sample, void* stream);
+/* One evaluation of the fixed-grid multistep DPM-Solver / DPM-Solver++ loop (multimodal_dpm_solver_plus.py:1252-1283) with every
+ * coefficient in a device table, so that a captured step bakes in no scalar.  tab: fp32 [6][rows] = cx, ce, c0, c1, c2, kind; k: device
+ * int64 [N], the step number (a sample whose k is outside [0, rows) is not written).  x / x0raw / M1: fp32 [N,F,C,HW]; the model output
+ * fp32 [N,F,Cm,HW] with Cm = C or 2C, eps = its first C channels.
+ *   mmd_dpmpp_x0      x0raw = cx[k] x + ce[k] eps: data_prediction_fn before its thresholding (dpm:419-428), mmd_lincomb's bits.  hist:
+ *                     NULL, or the workspace below - the same pass then adds level 0 (top 11 magnitude bits) of |x0raw| to it.
+ *   mmd_dpmpp_select  out[n] = q-quantile of |x[n,:]|, torch.quantile 'linear' (dpm:432,436): exact three-level (11 + 10 + 10 bits)
+ *                     multi-workgroup selection of the two neighbouring ranks, bitwise what mmd_abs_quantile returns.  level0_done != 0:
+ *                     mmd_dpmpp_x0 has filled level 0.  The workspace (mmd_dpmpp_workspace_bytes(N), per call in flight) must be zero
+ *                     on entry and is zero again afterwards.  x must hold no NaN.
+ *   mmd_dpmpp_update  m0 = clamp(m0, -s, s) / (s / max_val), s = max(s[n], 1) (dpm:433-434,437-438; s == NULL: m0 as it is), then by the
+ *                     row's kind, in place: 0  x = c0 x + c1 m0 (dpm_solver_first_update, dpm:532-590; M1 is not read)
+ *                     1  x = c0 x + c1 m0 + c2 M1 (multistep_dpm_solver_second_update, dpm:889-947)   2  x = m0 (denoise_fn, dpm:526-530);
+ *                     and M1 = m0, the history of the next step.  m0: x0raw (Cm = C) or, for the noise-prediction solver, the model output.
+ */
+int64_t mmd_dpmpp_workspace_bytes(int N);
+int mmd_dpmpp_x0(const float* x, const float* model_out, float* x0raw, const float* tab, const int64_t* k, int rows, void* hist, int N, int F,
+                 int C, int Cm, int HW, void* stream);
+int mmd_dpmpp_select(const float* x, void* workspace, int level0_done, int N, int64_t per_sample, float q, float* out, void* stream);
+int mmd_dpmpp_update(float* x, const float* m0, float* M1, const float* s, float max_val, const float* tab, const int64_t* k, int rows, int N,
+                     int F, int C, int Cm, int HW, void* stream);
 /* adaptive-step error term (dpm:1088-1149): out[n] += sum(((hi - lo) / max(atol, rtol max(|lo|, |prev|)))^2), fp64, caller zeroes. */
 int mmd_dpm_err(const float* hi, const float* lo, const float* prev, float atol, float rtol, int N, int64_t per_sample, double* out,
                 void* stream);

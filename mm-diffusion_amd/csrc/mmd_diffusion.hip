@@ -416,12 +416,17 @@ extern "C" int mmd_lincomb_t(const float* a, const float* b, float* out, const f
 }
 
 // out = ca a + cb b + cc c with host scalars (b, c nullable): the DPM-Solver update combinations (dpm:520-1100).
+// The terms of such a combination, shared with the graph step's kernels (dpmpp_x0_kernel, dpmpp_update_kernel) so that both write the
+// same bits: lincomb_kernel has always compiled to a rounded ca a and one fused multiply-add per further term, and that form is spelled
+// out here (its device code is unchanged by it).  A term that is absent is not added: -0 + 0 * c is +0.
+__device__ __forceinline__ float lincomb_first(float ca, float a) { return ca * a; }
+__device__ __forceinline__ float lincomb_add(float v, float c, float t) { return fmaf(c, t, v); }
 __global__ __launch_bounds__(256) void lincomb_kernel(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ c,
                                                       float* __restrict__ out, float ca, float cb, float cc, int64_t total) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    float v = ca * a[i];
-    if (b) v += cb * b[i];
-    if (c) v += cc * c[i];
+    float v = lincomb_first(ca, a[i]);
+    if (b) v = lincomb_add(v, cb, b[i]);
+    if (c) v = lincomb_add(v, cc, c[i]);
     out[i] = v;
   }
 }
@@ -761,17 +766,26 @@ __device__ uint32_t radix_select_block(const float* __restrict__ x, int64_t n, i
   return prefix;
 }
 
+// The two neighbouring ranks of torch.quantile(..., 'linear') among `per` values and the weight between them, and the interpolation:
+// shared with the multi-workgroup selection (dpmpp_select_final_kernel), which therefore returns the same bits.
+struct QuantileRanks { int64_t lo, hi; float frac; };
+__device__ __forceinline__ QuantileRanks quantile_ranks(int64_t per, float q) {
+  const double pos = (double)q * (double)(per - 1);
+  const int64_t lo = (int64_t)floor(pos);
+  const int64_t hi = lo + 1 < per ? lo + 1 : lo;
+  return {lo, hi, (float)(pos - (double)lo)};
+}
+// vlo + (vhi - vlo) frac; torch.lerp(lo, hi, frac) for frac < 0.5 and its mirror agree to 1 ulp
+__device__ __forceinline__ float quantile_lerp(float vlo, float vhi, float frac) { return fmaf(vhi - vlo, frac, vlo); }
+
 __global__ __launch_bounds__(1024) void abs_quantile_kernel(const float* __restrict__ x, int64_t per, float q, float* __restrict__ out) {
   __shared__ uint32_t hist[256];
   const int n = blockIdx.x, tid = threadIdx.x;
   const float* xs = x + (int64_t)n * per;
-  const double pos = (double)q * (double)(per - 1);
-  const int64_t lo = (int64_t)floor(pos);
-  const int64_t hi = lo + 1 < per ? lo + 1 : lo;
-  const float frac = (float)(pos - (double)lo);
-  const float vlo = __uint_as_float(radix_select_block(xs, per, lo, hist, tid, blockDim.x));
-  const float vhi = hi == lo ? vlo : __uint_as_float(radix_select_block(xs, per, hi, hist, tid, blockDim.x));
-  if (tid == 0) out[n] = vlo + (vhi - vlo) * frac;          // torch.lerp(lo, hi, frac) for frac < 0.5 and its mirror agree to 1 ulp
+  const QuantileRanks r = quantile_ranks(per, q);
+  const float vlo = __uint_as_float(radix_select_block(xs, per, r.lo, hist, tid, blockDim.x));
+  const float vhi = r.hi == r.lo ? vlo : __uint_as_float(radix_select_block(xs, per, r.hi, hist, tid, blockDim.x));
+  if (tid == 0) out[n] = quantile_lerp(vlo, vhi, r.frac);
 }
 extern "C" int mmd_abs_quantile(const float* x, int N, int64_t per_sample, float q, float* out, void* stream) {
   MMD_REQUIRE(x && out && N > 0 && per_sample > 0 && q >= 0.f && q <= 1.f, "abs_quantile: bad argument");
@@ -779,11 +793,16 @@ extern "C" int mmd_abs_quantile(const float* x, int N, int64_t per_sample, float
 }
 
 // x[n, :] = clamp(x, -s_n, s_n) / (s_n / max_val),  s_n = max(s[n], 1)        (in place)
+// one element of it, shared with dpmpp_update_kernel
+__device__ __forceinline__ float clamp_scale_elem(float v, float s, float max_val) {
+  const float sn = fmaxf(s, 1.f);
+  return fminf(fmaxf(v, -sn), sn) / (sn / max_val);
+}
 __global__ __launch_bounds__(256) void clamp_scale_kernel(float* __restrict__ x, const float* __restrict__ s, float max_val, int64_t per,
                                                           int64_t total) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const float sn = fmaxf(s[i / per], 1.f);
-    x[i] = fminf(fmaxf(x[i], -sn), sn) / (sn / max_val);
+    const float sv = s[i / per];
+    x[i] = clamp_scale_elem(x[i], sv, max_val);
   }
 }
 extern "C" int mmd_clamp_scale(float* x, const float* s, float max_val, int N, int64_t per_sample, void* stream) {
@@ -816,4 +835,236 @@ extern "C" int mmd_dpm_err(const float* hi, const float* lo, const float* prev, 
   const int chunks = (int)((per_sample + 256 * 16 - 1) / (256 * 16));
   return mmd_launch<dpm_err_kernel>("dpm_err", dim3(chunks < 1 ? 1 : (chunks > 256 ? 256 : chunks), N), dim3(256), 0, (hipStream_t)stream, hi, lo, prev, atol,
                                     rtol, per_sample, out);
+}
+
+// ----------------------------------------------------------------------------- DPM-Solver / DPM-Solver++ multistep step, graph form
+// One evaluation of the fixed-grid multistep loop (DPM_Solver.sample(method="multistep"), dpm:1252-1283, with data_prediction_fn
+// dpm:419-440, dpm_solver_first_update dpm:532-590 and multistep_dpm_solver_second_update dpm:889-947) without a host scalar: every
+// coefficient comes from a device table indexed by the step number k[n] (int64 [N], like t of the other steppers), so a captured step
+// bakes none in.  tab: fp32 [6][rows], rows = cx, ce (x0raw = cx x + ce eps), c0, c1, c2 (x = c0 x + c1 m0 + c2 m1) and the row's kind:
+//   0 first order (m1 is not read)   1 second order   2 denoise (x = m0)
+// One table per stream (the noise-prediction first-order step moves the audio stream with other coefficients, dpm:576-584).  A sample
+// whose k is outside [0, rows) is not written.  Tensors are API layout as in the update kernels above: x / x0raw / M1 fp32 [N, F, C, HW],
+// the model output fp32 [N, F, Cm, HW] with Cm = C or 2C (the first C channels are eps: learned-sigma outputs need no slicing copy).
+#define DPMPP_TAB_ROWS 6
+#define DPMPP_CHUNK 4096            // elements of one sample per workgroup in the histogram passes
+#define DPMPP_L0_BINS 2048          // level 0: the top 11 of the 31 magnitude bits
+#define DPMPP_L_BINS 1024           // levels 1 and 2: 10 bits each, one table per wanted rank
+#define DPMPP_WS_WORDS (DPMPP_L0_BINS + 4 * DPMPP_L_BINS)      // per sample: level 0, level 1 [2], level 2 [2]
+struct DpmppTab { const float* tab; const int64_t* k; int rows; };
+
+// Level 0 of the selection, per workgroup: h = one 2048-bin table PER WAVE in LDS (activations sit in a handful of exponents, so one
+// table for 256 threads would serialize on a few addresses), then the non-empty bins go to the sample's global table with integer
+// atomicAdd - order-independent, so the table is deterministic.
+__device__ __forceinline__ void l0_hist_zero(uint32_t* h, int tid) {
+  for (int b = tid; b < 4 * DPMPP_L0_BINS; b += 256) h[b] = 0;
+  __syncthreads();
+}
+__device__ __forceinline__ void l0_hist_add(uint32_t* h, int tid, float v) { atomicAdd(&h[(tid >> 6) * DPMPP_L0_BINS + (absbits(v) >> 20)], 1u); }
+__device__ __forceinline__ void l0_hist_flush(const uint32_t* h, int tid, uint32_t* g) {
+  __syncthreads();
+  for (int b = tid; b < DPMPP_L0_BINS; b += 256) {
+    const uint32_t c = h[b] + h[DPMPP_L0_BINS + b] + h[2 * DPMPP_L0_BINS + b] + h[3 * DPMPP_L0_BINS + b];
+    if (c) atomicAdd(g + b, c);
+  }
+}
+
+// x0raw = cx[k] x + ce[k] eps (data_prediction_fn before its thresholding); HIST: the same pass builds level 0 of |x0raw|
+template <bool HIST>
+__global__ __launch_bounds__(256) void dpmpp_x0_kernel(const DiffusionParams p, const DpmppTab t, float* __restrict__ x0raw, uint32_t* ws) {
+  __shared__ uint32_t h[HIST ? 4 * DPMPP_L0_BINS : 1];
+  const int n = blockIdx.y, tid = threadIdx.x;
+  const int64_t per = (int64_t)p.F * p.C * p.HW;
+  const int64_t ki = t.k[n];
+  if (ki < 0 || ki >= t.rows) return;          // uniform over the workgroup
+  const float cx = t.tab[ki], ce = t.tab[t.rows + ki];
+  if (HIST) l0_hist_zero(h, tid);
+  const int64_t lo = (int64_t)blockIdx.x * DPMPP_CHUNK, hi = lo + DPMPP_CHUNK < per ? lo + DPMPP_CHUNK : per;
+  for (int64_t r = lo + tid; r < hi; r += 256) {
+    const ElemAddr a = elem_addr(p, n, r);
+    const int64_t i = n * per + r;
+    const float v = lincomb_add(lincomb_first(cx, p.x[i]), ce, p.mo[a.mean]);
+    x0raw[i] = v;
+    if (HIST) l0_hist_add(h, tid, v);
+  }
+  if (HIST) l0_hist_flush(h, tid, ws + (int64_t)n * DPMPP_WS_WORDS);
+}
+
+// The bin of hist[NB] that holds rank `rank` (0-based, in ascending bin order) and the rank inside that bin; every thread of the 256
+// returns the same pair.  sm: 8 words of LDS.  A rank past the table's total (a workspace that was not zero) leaves (0, 0).
+template <int NB>
+__device__ __forceinline__ void find_bin(const uint32_t* hist, uint32_t rank, uint32_t* sm, int tid, uint32_t& bin, uint32_t& rem) {
+  constexpr int PT = NB / 256;
+  uint32_t c[PT], sum = 0;
+#pragma unroll
+  for (int j = 0; j < PT; ++j) {
+    c[j] = hist[tid * PT + j];
+    sum += c[j];
+  }
+  uint32_t inc = sum;                       // inclusive scan over the wave, then over the four waves
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t v = __shfl_up(inc, o, 64);
+    if ((tid & 63) >= o) inc += v;
+  }
+  __syncthreads();                          // the previous call's readers are done with sm
+  if ((tid & 63) == 63) sm[tid >> 6] = inc;
+  if (tid == 0) sm[4] = sm[5] = 0;
+  __syncthreads();
+  uint32_t exc = inc - sum;
+  for (int w = 0; w < (tid >> 6); ++w) exc += sm[w];
+  __syncthreads();
+  if (rank >= exc && rank - exc < sum) {    // exactly one thread
+    uint32_t r = rank - exc, b = 0;
+    bool done = false;
+#pragma unroll
+    for (int j = 0; j < PT; ++j) {
+      if (!done) {
+        if (r < c[j]) { b = j; done = true; }
+        else r -= c[j];
+      }
+    }
+    sm[4] = tid * PT + b;
+    sm[5] = r;
+  }
+  __syncthreads();
+  bin = sm[4];
+  rem = sm[5];
+}
+// The magnitude-bit prefix of rank `rank` of sample table w after LEVELS levels (1: 11 bits, 2: 21, 3: all 31) and the rank left
+// inside it; e = 0 / 1: the lower / upper of the two wanted ranks (levels 1 and 2 keep one table each).
+template <int LEVELS>
+__device__ __forceinline__ uint32_t select_prefix(const uint32_t* w, int e, uint32_t rank, uint32_t* sm, int tid) {
+  uint32_t b, r;
+  find_bin<DPMPP_L0_BINS>(w, rank, sm, tid, b, r);
+  uint32_t pre = b;
+  if (LEVELS >= 2) {
+    find_bin<DPMPP_L_BINS>(w + DPMPP_L0_BINS + e * DPMPP_L_BINS, r, sm, tid, b, r);
+    pre = (pre << 10) | b;
+  }
+  if (LEVELS >= 3) {
+    find_bin<DPMPP_L_BINS>(w + DPMPP_L0_BINS + (2 + e) * DPMPP_L_BINS, r, sm, tid, b, r);
+    pre = (pre << 10) | b;
+  }
+  return pre;
+}
+
+// One grid-wide histogram pass over x [N, per].  LEVEL 0: the top 11 magnitude bits of every element (what dpmpp_x0_kernel<true> fuses).
+// LEVEL 1 / 2: every workgroup re-derives the 11- / 21-bit prefixes of the two wanted ranks from the tables of the levels before - no
+// data-dependent buffer, no host read - and counts the next 10 bits of the elements under each prefix.
+template <int LEVEL>
+__global__ __launch_bounds__(256) void dpmpp_hist_kernel(const float* __restrict__ x, int64_t per, float q, uint32_t* ws) {
+  __shared__ uint32_t h[LEVEL == 0 ? 4 * DPMPP_L0_BINS : 2 * DPMPP_L_BINS];
+  __shared__ uint32_t sm[8];
+  const int n = blockIdx.y, tid = threadIdx.x;
+  uint32_t* w = ws + (int64_t)n * DPMPP_WS_WORDS;
+  const float* xs = x + (int64_t)n * per;
+  const int64_t lo = (int64_t)blockIdx.x * DPMPP_CHUNK, hi = lo + DPMPP_CHUNK < per ? lo + DPMPP_CHUNK : per;
+  if (LEVEL == 0) {
+    l0_hist_zero(h, tid);
+    for (int64_t r = lo + tid; r < hi; r += 256) l0_hist_add(h, tid, xs[r]);
+    l0_hist_flush(h, tid, w);
+  } else {
+    const QuantileRanks qr = quantile_ranks(per, q);
+    const uint32_t pre0 = select_prefix<LEVEL>(w, 0, (uint32_t)qr.lo, sm, tid), pre1 = select_prefix<LEVEL>(w, 1, (uint32_t)qr.hi, sm, tid);
+    constexpr int SHIFT = LEVEL == 1 ? 20 : 10;
+    for (int b = tid; b < 2 * DPMPP_L_BINS; b += 256) h[b] = 0;
+    __syncthreads();
+    for (int64_t r = lo + tid; r < hi; r += 256) {
+      const uint32_t b = absbits(xs[r]);
+      const uint32_t d = (b >> (SHIFT - 10)) & (DPMPP_L_BINS - 1);
+      if ((b >> SHIFT) == pre0) atomicAdd(&h[d], 1u);
+      if ((b >> SHIFT) == pre1) atomicAdd(&h[DPMPP_L_BINS + d], 1u);
+    }
+    __syncthreads();
+    uint32_t* g = w + DPMPP_L0_BINS + (LEVEL - 1) * 2 * DPMPP_L_BINS;
+    for (int b = tid; b < 2 * DPMPP_L_BINS; b += 256)
+      if (h[b]) atomicAdd(g + b, h[b]);
+  }
+}
+// The last consumer: one workgroup per sample walks the three levels for both ranks, interpolates as abs_quantile_kernel does, and
+// leaves the sample's tables zero for the next step.
+__global__ __launch_bounds__(256) void dpmpp_select_final_kernel(int64_t per, float q, uint32_t* ws, float* __restrict__ out) {
+  __shared__ uint32_t sm[8];
+  const int n = blockIdx.x, tid = threadIdx.x;
+  uint32_t* w = ws + (int64_t)n * DPMPP_WS_WORDS;
+  const QuantileRanks qr = quantile_ranks(per, q);
+  const float vlo = __uint_as_float(select_prefix<3>(w, 0, (uint32_t)qr.lo, sm, tid));
+  const float vhi = __uint_as_float(select_prefix<3>(w, 1, (uint32_t)qr.hi, sm, tid));
+  if (tid == 0) out[n] = quantile_lerp(vlo, vhi, qr.frac);
+  __syncthreads();
+  for (int b = tid; b < DPMPP_WS_WORDS; b += 256) w[b] = 0;
+}
+
+// x = c0[k] x + c1[k] m0 + c2[k] m1 in place, m0 = clamp_scale(m0src, s[n], max_val) (s == NULL: m0src itself), M1 = m0
+__global__ __launch_bounds__(256) void dpmpp_update_kernel(const DiffusionParams p, const DpmppTab t, float* x, float* M1, const float* __restrict__ s,
+                                                           float max_val) {
+  const int64_t per = (int64_t)p.F * p.C * p.HW;
+  const int64_t total = per * p.N;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int64_t n = i / per;
+    const int64_t ki = t.k[n];
+    if (ki < 0 || ki >= t.rows) continue;
+    const float c0 = t.tab[2 * t.rows + ki], c1 = t.tab[3 * t.rows + ki], c2 = t.tab[4 * t.rows + ki];
+    const int kind = (int)t.tab[5 * t.rows + ki];
+    const ElemAddr a = elem_addr(p, n, i % per);
+    float m0 = p.mo[a.mean];
+    if (s) m0 = clamp_scale_elem(m0, s[n], max_val);
+    float v;
+    if (kind == 2) {
+      v = m0;
+    } else {
+      v = lincomb_add(lincomb_first(c0, x[i]), c1, m0);
+      if (kind == 1) v = lincomb_add(v, c2, M1[i]);
+    }
+    x[i] = v;
+    M1[i] = m0;
+  }
+}
+
+// the element counts and ranks of a sample are 32-bit in the tables
+#define DPMPP_MAX_PER ((int64_t)1 << 31)
+static int dpmpp_geom_ok(const char* what, int rows, int N, int F, int C, int Cm, int HW) {
+  MMD_REQUIRE(rows > 0 && N > 0 && N <= 65535 && F > 0 && C > 0 && HW > 0, "%s: rows, N (<= 65535), F, C, HW must be positive", what);
+  MMD_REQUIRE(Cm == C || Cm == 2 * C, "%s: the model output has C = %d or 2C channels; got %d", what, C, Cm);
+  MMD_REQUIRE((int64_t)F * C * HW <= DPMPP_MAX_PER, "%s: sample too large", what);
+  return MMD_OK;
+}
+
+extern "C" int64_t mmd_dpmpp_workspace_bytes(int N) { return N > 0 ? (int64_t)N * DPMPP_WS_WORDS * sizeof(uint32_t) : 0; }
+
+extern "C" int mmd_dpmpp_x0(const float* x, const float* model_out, float* x0raw, const float* tab, const int64_t* k, int rows, void* hist, int N,
+                            int F, int C, int Cm, int HW, void* stream) {
+  MMD_REQUIRE(x && model_out && x0raw && tab && k, "dpmpp_x0: needs x, the model output, x0raw, the table and the step numbers");
+  if (int rc = dpmpp_geom_ok("dpmpp_x0", rows, N, F, C, Cm, HW)) return rc;
+  const DiffusionParams p{x, model_out, nullptr, nullptr, 0, N, F, C, HW, Cm == C ? 0 : 4};
+  const DpmppTab t{tab, k, rows};
+  const dim3 grid(cdiv((int64_t)F * C * HW, DPMPP_CHUNK), N);
+  if (hist) return mmd_launch<dpmpp_x0_kernel<true>>("dpmpp_x0", grid, dim3(256), 0, (hipStream_t)stream, p, t, x0raw, (uint32_t*)hist);
+  return mmd_launch<dpmpp_x0_kernel<false>>("dpmpp_x0", grid, dim3(256), 0, (hipStream_t)stream, p, t, x0raw, (uint32_t*)nullptr);
+}
+
+extern "C" int mmd_dpmpp_select(const float* x, void* workspace, int level0_done, int N, int64_t per_sample, float q, float* out, void* stream) {
+  MMD_REQUIRE(x && workspace && out, "dpmpp_select: needs x, the workspace and out");
+  MMD_REQUIRE(N > 0 && N <= 65535 && per_sample > 0 && per_sample <= DPMPP_MAX_PER, "dpmpp_select: N in [1, 65535], per_sample in [1, 2^31]");
+  MMD_REQUIRE(q >= 0.f && q <= 1.f, "dpmpp_select: q must be in [0, 1]; got %g", (double)q);
+  hipStream_t st = (hipStream_t)stream;
+  uint32_t* ws = (uint32_t*)workspace;
+  const dim3 grid(cdiv(per_sample, DPMPP_CHUNK), N);
+  int rc = MMD_OK;
+  if (!level0_done) rc = mmd_launch<dpmpp_hist_kernel<0>>("dpmpp_select level 0", grid, dim3(256), 0, st, x, per_sample, q, ws);
+  if (!rc) rc = mmd_launch<dpmpp_hist_kernel<1>>("dpmpp_select level 1", grid, dim3(256), 0, st, x, per_sample, q, ws);
+  if (!rc) rc = mmd_launch<dpmpp_hist_kernel<2>>("dpmpp_select level 2", grid, dim3(256), 0, st, x, per_sample, q, ws);
+  if (!rc) rc = mmd_launch<dpmpp_select_final_kernel>("dpmpp_select final", dim3(N), dim3(256), 0, st, per_sample, q, ws, out);
+  return rc;
+}
+
+extern "C" int mmd_dpmpp_update(float* x, const float* m0, float* M1, const float* s, float max_val, const float* tab, const int64_t* k, int rows,
+                                int N, int F, int C, int Cm, int HW, void* stream) {
+  MMD_REQUIRE(x && m0 && M1 && tab && k, "dpmpp_update: needs x, m0, M1, the table and the step numbers");
+  MMD_REQUIRE(!s || max_val > 0.f, "dpmpp_update: max_val must be positive with thresholding (s != NULL)");
+  if (int rc = dpmpp_geom_ok("dpmpp_update", rows, N, F, C, Cm, HW)) return rc;
+  const DiffusionParams p{nullptr, m0, nullptr, nullptr, 0, N, F, C, HW, Cm == C ? 0 : 4};
+  const DpmppTab t{tab, k, rows};
+  return mmd_launch<dpmpp_update_kernel>("dpmpp_update", dim3(ew_grid((int64_t)N * F * C * HW)), dim3(256), 0, (hipStream_t)stream, p, t, x, M1, s, max_val);
 }

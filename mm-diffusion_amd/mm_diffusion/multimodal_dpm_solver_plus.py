@@ -12,6 +12,11 @@ sigma, phi_k, ...) is a HOST fp32 scalar computed with the same formulas as the 
 `x_t = c0 x + c1 model_s + c2 model_s1` is ONE fused kernel per stream (mmd_lincomb); dynamic thresholding is an
 exact radix-select quantile + clamp (mmd_abs_quantile / mmd_clamp_scale); the adaptive error norm is mmd_dpm_err.
 
+`DPM_Solver.sample_graph` runs the fixed-grid multistep method (orders 1 and 2) without any of those host scalars in the launch path:
+the coefficients go into device tables indexed by the step number (`graph_tables`, built from the helpers the eager updates call) and
+one evaluation is one graph replay per lane (sampler.DpmppStepper: mmd_dpmpp_x0 / mmd_dpmpp_select / mmd_dpmpp_update), bitwise the
+eager loop, with batch lanes, seeded.CounterNoise and the partial masks of masked_sample_loop.
+
 Reference behaviours reproduced knowingly:
   * the noise-prediction first-order update moves the AUDIO stream with the x0-form coefficients
     (sigma_t/sigma_s, alpha_t * expm1(h)) while video uses (alpha_t/alpha_s, sigma_t * expm1(h))   (dpm:576-584)
@@ -198,6 +203,7 @@ def model_wrapper(model, noise_schedule, model_type="noise", model_kwargs={}, gu
             audio_output = audio_output[:, :1, ...]
         return {"video": video_output, "audio": audio_output}
 
+    model_fn.get_model_input_time = get_model_input_time      # DPM_Solver.sample_graph tabulates the model timesteps with it
     return model_fn
 
 
@@ -227,6 +233,7 @@ class DPM_Solver:
                  max_val=1., model_kwargs={}, rescale=False):
         noise_schedule = NoiseScheduleVP(schedule="discrete", betas=betas, alphas_cumprod=alphas_cumprod)
         self.model = model_wrapper(model, noise_schedule, model_type="noise", model_kwargs=model_kwargs, guidance_type=guidance_type)
+        self.raw_model, self.model_kwargs = model, model_kwargs
         self.noise_schedule = noise_schedule
         self.predict_x0 = predict_x0
         self.thresholding = thresholding
@@ -249,11 +256,10 @@ class DPM_Solver:
     def data_prediction_fn(self, x, t):
         """x0 = (x - sigma_t eps) / alpha_t, optionally with Imagen-style dynamic thresholding (dpm:419-440)."""
         noise = self.noise_prediction_fn(x, t)
-        tc = t.detach().float().cpu().reshape(-1)[:1]
-        alpha_t, sigma_t = _f(self.noise_schedule.marginal_alpha(tc)), _f(self.noise_schedule.marginal_std(tc))
+        cx, ce = self._x0_coefs(t)
         x0 = {}
         for k in self.KEYS:
-            v = ops.lincomb(x[k].float().contiguous(), 1.0 / alpha_t, noise[k], -sigma_t / alpha_t)
+            v = ops.lincomb(x[k].float().contiguous(), cx, noise[k], ce)
             if self.thresholding:
                 s = ops.abs_quantile(v, 0.995)          # p of the Imagen paper
                 ops.clamp_scale_(v, s, self.max_val)
@@ -305,14 +311,23 @@ class DPM_Solver:
             out.append((ns.marginal_lambda(tc), ns.marginal_log_mean_coeff(tc), ns.marginal_std(tc)))
         return out
 
-    # ------------------------------------------------------------------ first order (DDIM)
-    def dpm_solver_first_update(self, x, s, t, model_s=None, return_intermediate=False):
+    # ------------------------------------------------------------------ coefficients: host scalars, shared by the eager updates and
+    # the device tables of sample_graph (the kernels round them to fp32 on the way in, the tables when they are built)
+    def _alpha_sigma(self, t):
+        """(alpha_t, sigma_t) as host fp32 values."""
+        tc = t.detach().float().cpu().reshape(-1)[:1]
+        return _f(self.noise_schedule.marginal_alpha(tc)), _f(self.noise_schedule.marginal_std(tc))
+
+    def _x0_coefs(self, t):
+        """x0 = cx x + ce eps at time t (dpm:419-428)."""
+        alpha_t, sigma_t = self._alpha_sigma(t)
+        return 1.0 / alpha_t, -sigma_t / alpha_t
+
+    def _first_coefs(self, s, t):
+        """{stream: (c_x, c_model)} of the first-order update s -> t (dpm:532-590)."""
         (lam_s, la_s, sig_s), (lam_t, la_t, sig_t) = self._sc(s, t)
         h = lam_t - lam_s
         alpha_t = torch.exp(la_t)
-        x = self._prep(x)
-        if model_s is None:
-            model_s = self.model_fn(x, s)
         if self.predict_x0:
             phi_1 = torch.expm1(-h)
             c = {k: (_f(sig_t / sig_s), -_f(alpha_t * phi_1)) for k in self.KEYS}
@@ -322,6 +337,34 @@ class DPM_Solver:
             c = {k: (_f(torch.exp(la_t - la_s)), -_f(sig_t * phi_1)) for k in self.KEYS}
             if "audio" in c:
                 c["audio"] = (_f(sig_t / sig_s), -_f(alpha_t * phi_1))
+        return c
+
+    def _second_coefs(self, t_prev_1, t_prev_0, t, solver_type):
+        """(c_x, c_model_prev_0, c_model_prev_1) of the multistep second-order update (dpm:889-947), D1_0 = (m0 - m1) / r0 expanded."""
+        if solver_type not in ["dpm_solver", "taylor"]:
+            raise ValueError(f"'solver_type' must be either 'dpm_solver' or 'taylor', got {solver_type}")
+        if solver_type == "taylor" and not self.predict_x0:
+            raise NotImplementedError("noise-prediction multistep 'taylor': the reference expands the audio coefficient to the video "
+                                      "rank (dpm:961) - wrong shapes for B > 1")
+        (lam_p1, _, _), (lam_p0, la_p0, sig_p0), (lam_t, la_t, sig_t) = self._sc(t_prev_1, t_prev_0, t)
+        alpha_t = torch.exp(la_t)
+        h_0, h = lam_p0 - lam_p1, lam_t - lam_p0
+        r0 = h_0 / h
+        inv_r0 = _f(1. / r0)
+        if self.predict_x0:
+            c0, c1 = _f(sig_t / sig_p0), -_f(alpha_t * (torch.exp(-h) - 1.))
+            cd = (-0.5 * _f(alpha_t * (torch.exp(-h) - 1.))) if solver_type == "dpm_solver" else _f(alpha_t * ((torch.exp(-h) - 1.) / h + 1.))
+        else:
+            c0, c1 = _f(torch.exp(la_t - la_p0)), -_f(sig_t * (torch.exp(h) - 1.))
+            cd = -0.5 * _f(sig_t * (torch.exp(h) - 1.))
+        return c0, c1 + cd * inv_r0, -cd * inv_r0
+
+    # ------------------------------------------------------------------ first order (DDIM)
+    def dpm_solver_first_update(self, x, s, t, model_s=None, return_intermediate=False):
+        c = self._first_coefs(s, t)
+        x = self._prep(x)
+        if model_s is None:
+            model_s = self.model_fn(x, s)
         x_t = self._streams(lambda k: _comb([(c[k][0], x[k]), (c[k][1], model_s[k])]))
         return (x_t, {"model_s": model_s}) if return_intermediate else x_t
 
@@ -415,27 +458,11 @@ class DPM_Solver:
 
     # ------------------------------------------------------------------ multistep
     def multistep_dpm_solver_second_update(self, x, model_prev_list, t_prev_list, t, solver_type="dpm_solver"):
-        if solver_type not in ["dpm_solver", "taylor"]:
-            raise ValueError(f"'solver_type' must be either 'dpm_solver' or 'taylor', got {solver_type}")
-        if solver_type == "taylor" and not self.predict_x0:
-            raise NotImplementedError("noise-prediction multistep 'taylor': the reference expands the audio coefficient to the video "
-                                      "rank (dpm:961) - wrong shapes for B > 1")
         model_prev_1, model_prev_0 = model_prev_list
         t_prev_1, t_prev_0 = t_prev_list
-        (lam_p1, _, _), (lam_p0, la_p0, sig_p0), (lam_t, la_t, sig_t) = self._sc(t_prev_1, t_prev_0, t)
-        alpha_t = torch.exp(la_t)
-        h_0, h = lam_p0 - lam_p1, lam_t - lam_p0
-        r0 = h_0 / h
-        inv_r0 = _f(1. / r0)
+        c0, cm0, cm1 = self._second_coefs(t_prev_1, t_prev_0, t, solver_type)
         x = self._prep(x)
-        if self.predict_x0:
-            c0, c1 = _f(sig_t / sig_p0), -_f(alpha_t * (torch.exp(-h) - 1.))
-            cd = (-0.5 * _f(alpha_t * (torch.exp(-h) - 1.))) if solver_type == "dpm_solver" else _f(alpha_t * ((torch.exp(-h) - 1.) / h + 1.))
-        else:
-            c0, c1 = _f(torch.exp(la_t - la_p0)), -_f(sig_t * (torch.exp(h) - 1.))
-            cd = -0.5 * _f(sig_t * (torch.exp(h) - 1.))
-        # D1_0 = (m0 - m1) / r0
-        return self._streams(lambda k: _comb([(c0, x[k]), (c1 + cd * inv_r0, model_prev_0[k]), (-cd * inv_r0, model_prev_1[k])]))
+        return self._streams(lambda k: _comb([(c0, x[k]), (cm0, model_prev_0[k]), (cm1, model_prev_1[k])]))
 
     def multistep_dpm_solver_third_update(self, x, model_prev_list, t_prev_list, t, solver_type="dpm_solver"):
         raise NotImplementedError("multistep third-order update: the reference expands every audio coefficient to the video rank "
@@ -562,6 +589,139 @@ class DPM_Solver:
         if denoise:
             x = self.denoise_fn(x, torch.ones((B,)) * t_0)
         return x
+
+    # ------------------------------------------------------------------ graph-replayed multistep loop
+    def graph_tables(self, steps, order=2, skip_type="logSNR", solver_type="dpm_solver", denoise=False, device="cpu"):
+        """The per-evaluation tables of sample_graph, from the very helpers the eager updates call on the same host fp32 time grid.
+        Row i < steps: evaluation at timesteps[i] and the update to timesteps[i + 1] (first order at i == 0 or order == 1, else second
+        order); row `steps` (denoise): the final data prediction at t_0.  Returns {"rows", "timesteps" (fp32 [rows], host),
+        "tab": {stream: float32 [6, rows] = cx, ce, c0, c1, c2, kind}, "tab2": float32 [2, rows] = alpha, sigma (mmd_cond_replace's table),
+        "tm": the model's integer timesteps, get_model_input_time evaluated on `device` as the eager path evaluates it}."""
+        import numpy as np
+        steps = self._graph_check(steps, order, solver_type)
+        # kept per argument set: a sampling call otherwise spends the host time of every evaluation's scalars before its first launch
+        key = (steps, order, skip_type, solver_type, bool(denoise), str(device), bool(self.predict_x0))
+        cache = self.__dict__.setdefault("_graph_tables", {})
+        if key not in cache:
+            cache[key] = self._build_graph_tables(np, steps, order, skip_type, solver_type, denoise, device)
+        return cache[key]
+
+    def _build_graph_tables(self, np, steps, order, skip_type, solver_type, denoise, device):
+        t_0, t_T = 1. / self.noise_schedule.total_N, self.noise_schedule.T
+        grid = self.get_time_steps(skip_type=skip_type, t_T=t_T, t_0=t_0, N=steps, device="cpu")
+        times = [grid[i:i + 1] for i in range(steps + 1)]
+        evals = times[:steps] + ([torch.ones((1,)) * t_0] if denoise else [])
+        rows = len(evals)
+        tab = {k: np.zeros((ops.DPMPP_TAB_ROWS, rows), dtype=np.float32) for k in self.KEYS}
+        tab2 = np.zeros((2, rows), dtype=np.float32)
+        for i, t in enumerate(evals):
+            tab2[:, i] = self._alpha_sigma(t)
+            cx, ce = self._x0_coefs(t) if (self.predict_x0 or i == steps) else (0.0, 0.0)
+            if i == steps:
+                c = {k: (0.0, 0.0, 0.0, ops.DPMPP_KIND_DENOISE) for k in self.KEYS}
+            elif i == 0 or order == 1:
+                c = {k: v + (0.0, ops.DPMPP_KIND_FIRST) for k, v in self._first_coefs(times[i], times[i + 1]).items()}
+            else:
+                c = {k: self._second_coefs(times[i - 1], times[i], times[i + 1], solver_type) + (ops.DPMPP_KIND_SECOND,) for k in self.KEYS}
+            for k in self.KEYS:
+                tab[k][:, i] = (cx, ce) + tuple(c[k])
+        tm = self.model.get_model_input_time(torch.cat(evals).to(device))
+        return {"rows": rows, "timesteps": torch.cat(evals), "tab": tab, "tab2": tab2, "tm": [int(v) for v in tm.cpu()]}
+
+    def _graph_check(self, steps, order, solver_type):
+        if order not in (1, 2):
+            raise H.MMDError(f"sample_graph: order must be 1 or 2 (the reference's third-order multistep update cannot run, dpm:1006-1013); got {order}")
+        if solver_type not in ("dpm_solver", "taylor"):
+            raise H.MMDError(f"sample_graph: solver_type must be 'dpm_solver' or 'taylor', got {solver_type!r}")
+        if solver_type == "taylor" and not self.predict_x0 and order == 2:
+            raise H.MMDError("sample_graph: solver_type 'taylor' needs predict_x0 (the reference's noise-prediction 'taylor' update has wrong shapes, dpm:961)")
+        steps = int(steps)
+        if steps < order:
+            raise H.MMDError(f"sample_graph: steps ({steps}) must be at least the order ({order})")
+        return steps
+
+    def sample_graph(self, x_T=None, *, shape=None, steps, order=2, skip_type="logSNR", solver_type="dpm_solver", denoise=False, known=None,
+                     mask=None, noise_source=None, paste_known=True, use_graph=True, lanes=None, method="multistep"):
+        """sample(method="multistep") as one graph replay per lane and evaluation (sampler.DpmppStepper): the same x_T and window-shift
+        stream give the same bits.  x_T: {"video", "audio"} device tensors, or `shape` = {"video": (B,F,C,H,W), "audio": (B,C,L)} to draw
+        it.  noise_source: a seeded.CounterNoise - x_T is then its start draw (passing x_T as well raises), the window shifts and the
+        conditioning noise come from the counter, and sample k of a seed is the same at any batch and lane count.  known / mask: the
+        replacement method of masked_sample_loop (masking.normalize has the shapes): before every evaluation the known cells are set to
+        alpha(t) known + sigma(t) eps with eps = that stream's x_T; with paste_known the result carries `known` itself there.  Orders 1
+        and 2 of the fixed-grid multistep method only; batch 1 is accepted."""
+        from . import masking
+        from .sampler import DpmppStepper, unwrap_unet
+        from .seeded import CounterNoise, TAG_AUDIO, TAG_VIDEO, X_T
+        if method != "multistep":
+            raise H.MMDError(f"sample_graph: only method 'multistep' is recorded; the single-step and adaptive solvers ({method!r}) choose "
+                             "their evaluations on the host - use sample()")
+        if self.model_kwargs:
+            raise H.MMDError("sample_graph: model_kwargs cannot be recorded into the step graph - use sample()")
+        self._graph_check(steps, order, solver_type)
+        ctr = noise_source
+        if ctr is not None and not isinstance(ctr, CounterNoise):
+            raise H.MMDError("sample_graph: noise_source must be a seeded.CounterNoise or None")
+        if ctr is not None and x_T is not None:
+            raise H.MMDError("sample_graph: a CounterNoise source draws x_T itself: x_T must be None")
+        if x_T is None and shape is None:
+            raise H.MMDError("sample_graph: give x_T or shape")
+        if x_T is not None:
+            for k in self.KEYS:
+                H.require_cuda(x_T[k])
+            device = x_T[self.KEYS[0]].device
+            shape = {k: tuple(x_T[k].shape) for k in self.KEYS}
+        unet = unwrap_unet(self.raw_model)
+        if unet is None:
+            raise H.MMDError("sample_graph: the model is no MultimodalUNet (or a wrapper of one)")
+        if x_T is None:
+            device = next(unet.parameters()).device
+            if device.type != "cuda":
+                raise H.MMDError("sample_graph runs on the MI355X HIP path only (the model must be on a GPU); no CPU fallback")
+            shape = {k: tuple(int(v) for v in shape[k]) for k in self.KEYS}
+        tabs = self.graph_tables(steps, order, skip_type, solver_type, denoise, device=device)
+        cond = masking.normalize(known, mask, shape) if known is not None else {}
+        if mask is not None and known is None:
+            raise H.MMDError("sample_graph: mask without known")
+        for k, c in cond.items():
+            H.require_cuda(c.known)
+            cond[k] = c._replace(known=c.known.to(device), mask=None if c.mask is None else c.mask.to(device))
+        if x_T is None:
+            if ctr is not None:
+                x_T = {"video": ctr.randn(shape["video"], TAG_VIDEO, X_T, device), "audio": ctr.randn(shape["audio"], TAG_AUDIO, X_T, device)}
+            else:
+                x_T = {k: torch.randn(*shape[k]).to(device) for k in self.KEYS}
+        x_T = {k: x_T[k].float().contiguous() for k in self.KEYS}
+        # the stepper of the last call is kept: another call of the same shape and structure reloads its tables and replays its graphs
+        from . import sampler
+        B = shape["video"][0]
+        key = (B, sampler.default_lanes(B) if lanes is None else int(lanes), bool(use_graph), ctr is not None, sampler.DPMPP_SELECT,
+               tuple((k, c.mask is not None) for k, c in sorted(cond.items())), bool(self.predict_x0), bool(self.thresholding),
+               float(self.max_val), str(device), id(unet))
+        kept = getattr(self, "_stepper", None)
+        self._stepper = None
+        with torch.no_grad():
+            if kept is not None and kept[0] == key and kept[1].usable():
+                stepper = kept[1]
+                stepper.retable(tabs, ctr)
+            else:
+                if kept is not None:
+                    kept[1].close()
+                stepper = DpmppStepper(self, unet, B, device, tabs, use_graph=use_graph, lanes=lanes, cond=cond, ctr=ctr)
+            try:
+                stepper.load(x_T["video"], x_T["audio"])
+                if cond:
+                    stepper.load_cond(cond, x_T)
+                for i in range(tabs["rows"]):
+                    stepper.step(i)
+                    self.nfe += 1
+                if cond and paste_known:
+                    stepper.paste_known()
+                out = stepper.current()
+            except BaseException:
+                stepper.close()
+                raise
+            self._stepper = (key, stepper)
+            return out
 
 
 def expand_dims(v, dims):

@@ -1093,10 +1093,10 @@ def bilinear_concat_rows(x, low, out):
     return out
 
 
-def abs_quantile(x, q):
+def abs_quantile(x, q, out=None):
     """per-sample q-quantile of |x| (fp32 contiguous [N, ...]) -> fp32 [N]."""
-    H.require_cuda(x)
-    out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+    H.require_cuda(x, out)
+    out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device) if out is None else out
     _dispatch("mmd_abs_quantile", x.data_ptr(), x.shape[0], x[0].numel(), float(q), out.data_ptr(), meta=("abs_quantile", 0, 20 * x.numel()))
     return out
 
@@ -1104,6 +1104,75 @@ def abs_quantile(x, q):
 def clamp_scale_(x, s, max_val):
     H.require_cuda(x, s)
     _dispatch("mmd_clamp_scale", x.data_ptr(), s.data_ptr(), float(max_val), x.shape[0], x[0].numel(), meta=("clamp_scale", 0, 8 * x.numel()))
+    return x
+
+
+DPMPP_TAB_ROWS = 6      # cx, ce, c0, c1, c2, kind (include/mmd.h: mmd_dpmpp_*)
+DPMPP_CHUNK = 4096      # elements of a sample per workgroup in the selection's histogram passes
+DPMPP_KIND_FIRST, DPMPP_KIND_SECOND, DPMPP_KIND_DENOISE = 0, 1, 2
+
+
+def dpmpp_workspace(N, device):
+    """The zeroed selection workspace of N samples (one per stream and call in flight); mmd_dpmpp_select leaves it zero again."""
+    return torch.zeros(H.lib().mmd_dpmpp_workspace_bytes(int(N)) // 4, dtype=torch.int32, device=device)
+
+
+def _dpmpp_args(name, tab, k, N, fp32):
+    if tab.dtype != torch.float32 or tab.dim() != 2 or tab.shape[0] != DPMPP_TAB_ROWS or not tab.is_contiguous():
+        raise H.MMDError(f"{name}: the table must be contiguous fp32 [{DPMPP_TAB_ROWS}, rows]")
+    if k.dtype != torch.int64 or k.numel() != N or not k.is_contiguous():
+        raise H.MMDError(f"{name}: needs one contiguous int64 step number per sample")
+    for what, v in fp32:
+        if v is not None and (v.dtype != torch.float32 or not v.is_contiguous()):
+            raise H.MMDError(f"{name}: {what} must be contiguous fp32")
+
+
+def dpmpp_x0(x, model_out, x0raw, tab, k, F, C, Cm, HW, hist=None):
+    """x0raw = cx[k] x + ce[k] eps (eps = the first C of the model output's Cm channels); hist = a dpmpp_workspace: the same pass adds
+    level 0 of the selection to it."""
+    H.require_cuda(x, model_out, x0raw, tab, k, hist)
+    N = x.shape[0]
+    _dpmpp_args("dpmpp_x0", tab, k, N, (("x", x), ("model_out", model_out), ("x0raw", x0raw)))
+    if x.numel() != N * F * C * HW or x0raw.numel() != x.numel() or model_out.numel() != N * F * Cm * HW:
+        raise H.MMDError(f"dpmpp_x0: x / x0raw must hold N F C HW = {N * F * C * HW} and the model output N F Cm HW = {N * F * Cm * HW} elements")
+    if hist is not None and hist.numel() * hist.element_size() < H.lib().mmd_dpmpp_workspace_bytes(N):
+        raise H.MMDError("dpmpp_x0: the histogram workspace is smaller than mmd_dpmpp_workspace_bytes(N)")
+    _dispatch("mmd_dpmpp_x0", x.data_ptr(), model_out.data_ptr(), x0raw.data_ptr(), tab.data_ptr(), k.data_ptr(), tab.shape[1], H.ptr(hist), N, F, C,
+              Cm, HW, meta=("dpmpp_x0", 0, 12 * x.numel()))
+    return x0raw
+
+
+def dpmpp_select(x, q, out, ws, level0_done=False):
+    """out[n] = the q-quantile of |x[n]| by the multi-workgroup selection: bitwise abs_quantile(x, q).  ws: a dpmpp_workspace, zero on
+    entry (level0_done: but for level 0, which dpmpp_x0 has filled) and zero again afterwards.  x must hold no NaN."""
+    H.require_cuda(x, out, ws)
+    N = x.shape[0]
+    if x.dtype != torch.float32 or not x.is_contiguous() or out.dtype != torch.float32 or out.numel() != N or not out.is_contiguous():
+        raise H.MMDError("dpmpp_select: x must be contiguous fp32 [N, ...] and out contiguous fp32 [N]")
+    if ws.numel() * ws.element_size() < H.lib().mmd_dpmpp_workspace_bytes(N):
+        raise H.MMDError("dpmpp_select: the workspace is smaller than mmd_dpmpp_workspace_bytes(N)")
+    _dispatch("mmd_dpmpp_select", x.data_ptr(), ws.data_ptr(), 1 if level0_done else 0, N, x[0].numel(), float(q), out.data_ptr(),
+              meta=("dpmpp_select", 0, (8 if level0_done else 12) * x.numel()))
+    return out
+
+
+def dpmpp_abs_quantile(x, q, ws=None):
+    """abs_quantile by the multi-workgroup selection (all three levels from x)."""
+    H.require_cuda(x)
+    ws = dpmpp_workspace(x.shape[0], x.device) if ws is None else ws
+    return dpmpp_select(x, q, torch.empty(x.shape[0], dtype=torch.float32, device=x.device), ws)
+
+
+def dpmpp_update(x, m0, M1, tab, k, F, C, Cm, HW, s=None, max_val=1.0):
+    """In place x = c0[k] x + c1[k] m0 + c2[k] M1 by the row's kind (include/mmd.h), M1 = m0; m0 [N,F,Cm,HW] is clamp-scaled by s [N] first
+    when s is given."""
+    H.require_cuda(x, m0, M1, tab, k, s)
+    N = x.shape[0]
+    _dpmpp_args("dpmpp_update", tab, k, N, (("x", x), ("m0", m0), ("M1", M1), ("s", s)))
+    if x.numel() != N * F * C * HW or M1.numel() != x.numel() or m0.numel() != N * F * Cm * HW or (s is not None and s.numel() != N):
+        raise H.MMDError(f"dpmpp_update: x / M1 must hold N F C HW = {N * F * C * HW}, m0 N F Cm HW = {N * F * Cm * HW} elements and s one per sample")
+    _dispatch("mmd_dpmpp_update", x.data_ptr(), m0.data_ptr(), M1.data_ptr(), H.ptr(s), float(max_val), tab.data_ptr(), k.data_ptr(), tab.shape[1],
+              N, F, C, Cm, HW, meta=("dpmpp_update", 0, 20 * x.numel()))
     return x
 
 

@@ -339,3 +339,181 @@ class GraphStepper:
             pass
 
     __del__ = close
+
+
+# Which kernel a recorded DPM-Solver++ step takes its thresholding quantile from: "multi" = the three-level multi-workgroup selection
+# whose first level rides mmd_dpmpp_x0, "block" = mmd_abs_quantile (one workgroup per sample).  The two return the same bits; the choice
+# is a timing one (tools/dpm_graph_bench.py).
+DPMPP_SELECT = "multi"
+
+
+class DpmppStepper(GraphStepper):
+    """One evaluation of the fixed-grid multistep DPM-Solver / DPM-Solver++ loop (multimodal_dpm_solver_plus.DPM_Solver.sample_graph)
+    as one graph replay per lane: [mmd_cond_replace of each conditioned stream] + U-Net plan + per stream on its own stream
+    [mmd_dpmpp_x0 (+ the quantile selection) + mmd_dpmpp_update] + join.  Every coefficient sits in the device tables of
+    DPM_Solver.graph_tables, indexed by the step number in t_idx, so the graph of one step serves them all.  The noise-prediction solver
+    updates from the model output directly; its closing denoise evaluation is a data prediction and has a second plan ("final").
+    Lanes, conditioning buffers, capture and launch are GraphStepper's.
+
+    The tables have a fixed capacity (ROWS_CAP rows, the stride the recorded launches carry), so a stepper outlives one sampling call:
+    retable() loads another time grid, order or seed into the same buffers and the captured graphs are replayed as they are
+    (DPM_Solver.sample_graph keeps its last stepper; a capture costs about as much as five evaluations of a 50-evaluation call)."""
+    ROWS_CAP = 1024
+
+    def __init__(self, solver, unet, batch, device, tabs, use_graph=True, lanes=None, cond=None, ctr=None, select=None):
+        self.diff, self.unet, self.N = None, unet, int(batch)
+        self.device = th.device(device)
+        self.lanes = default_lanes(self.N) if lanes is None else int(lanes)
+        if self.lanes < 1 or self.N % self.lanes:
+            raise H.MMDError(f"batch {self.N} does not split into {self.lanes} lanes")
+        n = self.n = self.N // self.lanes
+        select = DPMPP_SELECT if select is None else select
+        if select not in ("multi", "block"):
+            raise H.MMDError(f"unknown selection {select!r} (multi or block)")
+        self.engs = [unet.engine(n, self.device, replica=r) for r in range(self.lanes)]
+        self.eng = e = self.engs[0]
+        self.tab = {k: th.zeros(ops.DPMPP_TAB_ROWS, self.ROWS_CAP, dtype=th.float32, device=self.device) for k in ("video", "audio")}
+        self._qtab = th.zeros(2, self.ROWS_CAP, dtype=th.float32, device=self.device)
+        self.t_idx = th.zeros(self.N, dtype=th.int64, device=self.device)      # step number (table row)
+        self.ctr = ctr
+        if ctr is not None:      # own copies: retable() refills them for another seed or other sample ids
+            self.key, self.ids = ctr.key(self.device).clone(), ctr.ids(self.N, self.device).clone()
+        self.predict_x0 = bool(solver.predict_x0)
+        self.retable(tabs, ctr)
+        self.use_f32 = False
+        F, HW = e.F, e.H0 * e.W0
+        geom = {"video": (F, e.Cv_in, unet.video_out_channels, HW), "audio": (1, e.Ca_in, unet.audio_out_channels, e.L0)}
+        self.cond = {}
+        for k, c in (cond or {}).items():
+            xk = e.x_video if k == "video" else e.x_audio
+            self.cond[k] = {"known": th.zeros((self.N,) + tuple(xk.shape[1:]), dtype=th.float32, device=self.device),
+                            "mask": None if c.mask is None else th.zeros(self.N, F * HW if k == "video" else e.L0, dtype=th.uint8, device=self.device),
+                            "noise": None if ctr is not None else th.zeros((self.N,) + tuple(xk.shape[1:]), dtype=th.float32, device=self.device)}
+        predict_x0, thresholding, max_val = bool(solver.predict_x0), bool(solver.thresholding), float(solver.max_val)
+        self.has_final = not predict_x0      # the noise-prediction solver's denoise row needs the data-prediction plan
+        self.update_plans, self.final_plans, self.pre_plans, self._bufs = [], [], [], []
+        for r, e in enumerate(self.engs):
+            sl = slice(r * n, (r + 1) * n)
+            t_idx = self.t_idx[sl]
+            if self.cond:
+                pre = []
+                with ops.recording(pre):
+                    for k, tag in (("video", 0), ("audio", 1)):
+                        if k in self.cond:
+                            self._cond_replace(r, k, tag, self._qtab, t_idx, None)
+                self.pre_plans.append(pre)
+            streams = []
+            for sid, k, xk, ok in ((0, "video", e.x_video, e.out_video), (1, "audio", e.x_audio, e.out_audio)):
+                buf = {"m1": th.zeros_like(xk), "x0": th.empty_like(xk), "s": th.zeros(n, dtype=th.float32, device=self.device),
+                       "ws": ops.dpmpp_workspace(n, self.device)}
+                self._bufs.append(buf)
+                streams.append((sid, k, xk, ok, buf))
+
+            def record(data_form):
+                plan = []
+                with ops.recording(plan):
+                    for sid, k, xk, ok, b in streams:
+                        Fk, C, Cm, HWk = geom[k]
+                        with ops.on_stream(sid):
+                            if data_form:
+                                multi = thresholding and select == "multi"
+                                ops.dpmpp_x0(xk, ok, b["x0"], self.tab[k], t_idx, Fk, C, Cm, HWk, hist=b["ws"] if multi else None)
+                                if multi:
+                                    ops.dpmpp_select(b["x0"], 0.995, b["s"], b["ws"], level0_done=True)      # p of the Imagen paper
+                                elif thresholding:
+                                    ops.abs_quantile(b["x0"], 0.995, out=b["s"])
+                                ops.dpmpp_update(xk, b["x0"], b["m1"], self.tab[k], t_idx, Fk, C, C, HWk, s=b["s"] if thresholding else None,
+                                                 max_val=max_val)
+                            else:
+                                ops.dpmpp_update(xk, ok, b["m1"], self.tab[k], t_idx, Fk, C, Cm, HWk)
+                    ops.record_sync(1, 0)
+                return plan
+            self.update_plans.append(record(predict_x0))
+            if self.has_final:
+                self.final_plans.append(record(True))
+        self.update_plan = self.update_plans[0]
+        self.graphs = self.final_graphs = None
+        self.use_graph = use_graph
+        self._final = False
+        self._up_t = H.Staged(self.t_idx)
+        self._up_tm = [H.Staged(e.t_i64) for e in self.engs]
+        import ctypes
+        self._lane_ev = []
+        for _ in range(self.lanes + 1 if self.lanes > 1 else 0):
+            ev = ctypes.c_void_p()
+            H.call("mmd_event_create", ctypes.byref(ev))
+            self._lane_ev.append(ev)
+
+    def retable(self, tabs, ctr=None):
+        """Load the tables of DPM_Solver.graph_tables (and the key and sample ids of `ctr`) into the buffers the recorded plans read."""
+        if tabs["rows"] > self.ROWS_CAP:
+            raise H.MMDError(f"sample_graph: {tabs['rows']} evaluations exceed the table capacity of {self.ROWS_CAP} rows")
+        if (ctr is None) != (self.ctr is None):
+            raise H.MMDError("the noise source's kind is fixed when the stepper is built")
+        self.rows, self.tm = tabs["rows"], tabs["tm"]
+        for k in ("video", "audio"):
+            self.tab[k][:, :self.rows].copy_(th.from_numpy(tabs["tab"][k]))
+        self._qtab[:, :self.rows].copy_(th.from_numpy(tabs["tab2"]))
+        self.kinds = [int(v) for v in tabs["tab"]["video"][5]]
+        self.ctr = ctr
+        if ctr is not None:
+            self.key.copy_(ctr.key(self.device))
+            self.ids.copy_(ctr.ids(self.N, self.device))
+
+    def usable(self):
+        """False once the model has rebuilt its engines (new weights, another dtype): the recorded plans then point at retired buffers."""
+        try:
+            return all(self.unet.engine(self.n, self.device, replica=r) is e for r, e in enumerate(self.engs))
+        except Exception:
+            return False
+
+    def set_step(self, i, shifts=None, noise=None):
+        """Refresh the per-evaluation device state: the step number, the model timestep and the window shifts (one draw per
+        evaluation, in the eager loop's order; from the counter with a CounterNoise)."""
+        i = int(i)
+        if not 0 <= i < self.rows:
+            raise H.MMDError(f"step {i} is outside the {self.rows} rows of the tables")
+        self._final = self.has_final and self.kinds[i] == ops.DPMPP_KIND_DENOISE
+        self._up_t.host().fill_(i)
+        self._up_t.push()
+        for up in self._up_tm:
+            up.host().fill_(int(self.tm[i]))
+            up.push()
+        if shifts is None:
+            own = self.ctr is not None and self.unet.shift_source is None
+            shifts = self.ctr.shifts(i, self.unet) if own else self.unet.draw_shifts()
+        for e in self.engs:
+            e.set_shifts(shifts)
+
+    def _lane_launch(self, r, stream):
+        e = self.engs[r]
+        aux = e.aux.cuda_stream
+        if self.pre_plans:
+            ops.run_plan(self.pre_plans[r], stream, aux)
+        ops.run_plan(e.plan, stream, aux)
+        ops.run_plan((self.final_plans if self._final else self.update_plans)[r], stream, aux)
+
+    def launch(self):
+        # the step plan and the final plan have a graph each; GraphStepper.launch captures and replays whichever self.graphs names
+        if self._final:
+            self.graphs, keep = self.final_graphs, self.graphs
+            try:
+                super().launch()
+            finally:
+                self.final_graphs, self.graphs = self.graphs, keep
+        else:
+            super().launch()
+
+    def close(self):
+        try:
+            for g in getattr(self, "final_graphs", None) or []:
+                H.retire("graph", g)
+            self.final_graphs = None
+            for ev in H.plan_events(*(getattr(self, "final_plans", None) or [])):
+                H.retire("event", ev)
+            self.final_plans = []
+        except Exception:
+            pass
+        super().close()
+
+    __del__ = close
