@@ -3,9 +3,13 @@ derivation; tests/test_errbound_cpu.py: the metric proven on seeded defects).
 
 Every case builds its reference with torch double ops on the stored operands - never with a libmmd kernel -, prefills the output
 with NaN, and admits ZERO elements outside the per-element bound.  These are the roots of the suite's "bitwise equal to ..."
-chains: the strip kernel, the ring tile, the halo tiles, the fused VideoConv, mmd_tconv, mmd_aconv and mmd_tattn_block are compared
+chains: the strip kernel, the ring tile, the halo tiles, mmd_tconv (bitwise conv_gemm), mmd_aconv (bitwise gn_apply + conv_gemm),
+mmd_gn_conv1x1_skip, the halo loader of mmd_gn_conv_gemm and the FRONT stage of mmd_tattn_block (bitwise the strip GEMM) are compared
 with tiles 64 / 128 / 129 of mmd_conv_gemm elsewhere, and here those tiles (and the others directly) meet an independent reference
-on ragged M, ragged Cout, deep K, strided views, every tap form and every frame border.
+on ragged M, ragged Cout, deep K, strided views, every tap form and every frame border.  The fused VideoConv (mmd_vconv2d1d) and
+mmd_tattn_block itself hang on NO bitwise chain - their own tests compare whole tensors by rel-L2 (and, for the VideoConv, a 97 %
+bitwise share) with the unfused paths -; they meet their float64 references element by element in
+tests/test_elementwise_fused_gpu.py (staged references with propagated bounds: tests/errbound_fused.py).
 
 Worst error / bound ratio per kernel / variant / dtype, as printed by the tests (`-s`) on an MI355X (`cases` = launches in the group):
 
