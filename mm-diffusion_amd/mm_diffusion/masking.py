@@ -70,6 +70,14 @@ def normalize(known, mask, shape):
     return out
 
 
+def to_device(cond, device):
+    """normalize's result with its tensors on `device`: a missing mask stays None, shapes, dtypes and strides stay as they are.  The
+    known values of a GPU run must be device tensors already (there is no silent upload of a clip)."""
+    if th.device(device).type == "cuda":
+        H.require_cuda(*(c.known for c in cond.values()))
+    return {k: c._replace(known=c.known.to(device), mask=None if c.mask is None else c.mask.to(device)) for k, c in cond.items()}
+
+
 def prefix_masks(video_size, audio_size, frames):
     """The masks that continue a clip: the first `frames` of the F video frames and the audio they span, floor(frames * L / F) samples.
     video_size (F, C, H, W), audio_size (C, L) -> {"video": bool [F, H, W], "audio": bool [L]}."""

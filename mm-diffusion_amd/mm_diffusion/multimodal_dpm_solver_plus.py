@@ -679,12 +679,9 @@ class DPM_Solver:
                 raise H.MMDError("sample_graph runs on the MI355X HIP path only (the model must be on a GPU); no CPU fallback")
             shape = {k: tuple(int(v) for v in shape[k]) for k in self.KEYS}
         tabs = self.graph_tables(steps, order, skip_type, solver_type, denoise, device=device)
-        cond = masking.normalize(known, mask, shape) if known is not None else {}
         if mask is not None and known is None:
             raise H.MMDError("sample_graph: mask without known")
-        for k, c in cond.items():
-            H.require_cuda(c.known)
-            cond[k] = c._replace(known=c.known.to(device), mask=None if c.mask is None else c.mask.to(device))
+        cond = masking.to_device(masking.normalize(known, mask, shape), device) if known is not None else {}
         if x_T is None:
             if ctr is not None:
                 x_T = {"video": ctr.randn(shape["video"], TAG_VIDEO, X_T, device), "audio": ctr.randn(shape["audio"], TAG_AUDIO, X_T, device)}

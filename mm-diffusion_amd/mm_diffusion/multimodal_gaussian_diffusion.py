@@ -229,6 +229,10 @@ class GaussianDiffusion:
             return ctr.randn(shape, tag, X_T, device)
         return th.randn(*shape, device="cpu").to(device)
 
+    def _x_T(self, shape, device):
+        """The x_T dict of a sampling run (video first, then audio)."""
+        return {"video": self._start_noise(shape["video"], 0, device), "audio": self._start_noise(shape["audio"], 1, device)}
+
     # ------------------------------------------------------------------ q(x_t | x_0)
     def q_sample(self, x_start, t, noise=None):
         """x_t = sqrt(ac_t) x_0 + sqrt(1-ac_t) eps (gd:187-205) as one kernel."""
@@ -268,6 +272,15 @@ class GaussianDiffusion:
             ops.ddpm_update(xs, mo, noise, res.get("sample"), tab, t.to(th.int64).contiguous(), F, C, HW, flags, **outs)
         return res
 
+    def _model_out2(self, model, x, t, model_kwargs, ctr=None):
+        """(video_output, audio_output) of the model at x_t; SpacedDiffusion maps the timesteps in here.  With a counter `ctr` this is
+        the draw of step t, and the eager forward takes its window shifts from the counter too."""
+        if ctr is None:
+            return model(x["video"], x["audio"], self._scale_timesteps(t), **(model_kwargs or {}))
+        ctr.set_draw(t)
+        with ctr.shifting(model):
+            return model(x["video"], x["audio"], self._scale_timesteps(t), **(model_kwargs or {}))
+
     def p_mean_variance(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None):
         """gd:231-343.  Returns the same nested dict ({'mean','variance','log_variance','pred_xstart','model_predict'}
         each {'video','audio'})."""
@@ -288,14 +301,8 @@ class GaussianDiffusion:
         noise is drawn for both streams (video first), also at t == 0."""
         if cond_fn is not None:
             raise NotImplementedError("cond_fn: the reference's condition_mean raises for the multimodal dict (gd:385 calls dict.float()); not built")
-        model_kwargs = model_kwargs or {}
         ctr = self._counter()
-        if ctr is not None:                  # the draw of this step; the eager forward takes its window shifts from the counter too
-            ctr.set_draw(t)
-            with ctr.shifting(model):
-                video_output, audio_output = model(x["video"], x["audio"], self._scale_timesteps(t), **model_kwargs)
-        else:
-            video_output, audio_output = model(x["video"], x["audio"], self._scale_timesteps(t), **model_kwargs)
+        video_output, audio_output = self._model_out2(model, x, t, model_kwargs, ctr)
         differentiable = th.is_grad_enabled() and any(v.requires_grad for v in (video_output, audio_output, x["video"], x["audio"]))
         if ctr is not None and not differentiable:
             noise = {"video": ctr, "audio": ctr}
@@ -318,12 +325,7 @@ class GaussianDiffusion:
     # ------------------------------------------------------------------ DDIM
     def _ddim(self, model, x, t, clip_denoised, model_kwargs, eta, reverse):
         ctr = None if reverse else self._counter()
-        if ctr is not None:
-            ctr.set_draw(t)
-            with ctr.shifting(model):
-                video_output, audio_output = model(x["video"], x["audio"], self._scale_timesteps(t), **(model_kwargs or {}))
-        else:
-            video_output, audio_output = model(x["video"], x["audio"], self._scale_timesteps(t), **(model_kwargs or {}))
+        video_output, audio_output = self._model_out2(model, x, t, model_kwargs, ctr)
         res = {"sample": {}, "pred_xstart": {}}
         flags = self._flags(clip_denoised) | (8 if reverse else 0)
         for key, mo in (("video", video_output), ("audio", audio_output)):
@@ -371,19 +373,12 @@ class GaussianDiffusion:
         if cond_fn is not None or denoised_fn is not None:
             raise NotImplementedError("cond_fn / denoised_fn: see ddim_sample")
         device = self._sampling_device(device)
-        x = {"video": self._start_noise(shape["video"], 0, device), "audio": self._start_noise(shape["audio"], 1, device)}
+        x = self._x_T(shape, device)
         indices = self._indices(progress)
-        from .sampler import GraphStepper, unwrap_unet
-        unet = unwrap_unet(model)
-        if use_graph and unet is not None and not (model_kwargs or {}):
-            stepper = GraphStepper(self, unet, shape["video"][0], device, clip_denoised, update="ddim", eta=eta)
+        stepper = self._graph_stepper(model, model_kwargs, use_graph, shape["video"][0], device, clip_denoised, update="ddim", eta=eta)
+        if stepper is not None:
             stepper.load(x["video"], x["audio"])
-            try:
-                for i in indices:
-                    stepper.step(i)
-                    yield stepper.current()
-            finally:
-                stepper.close()
+            yield from self._replay(stepper, indices)
             return
         for i in indices:
             t = th.tensor([i] * shape["video"][0], device=device)
@@ -408,6 +403,31 @@ class GaussianDiffusion:
             indices = tqdm(indices)
         return indices
 
+    def _graph_stepper(self, model, model_kwargs, use_graph, batch, device, clip_denoised, denoised_fn=None, update="ddpm", eta=0.0,
+                       lanes=None, cond=None):
+        """The sampler.GraphStepper of a call whose steps can be graph-replayed - a MultimodalUNet behind `model`, no model_kwargs, no host
+        callable on the x_0 prediction - else None: the caller then launches its steps eagerly."""
+        from .sampler import GraphStepper, unwrap_unet
+        unet = unwrap_unet(model)
+        if not use_graph or unet is None or model_kwargs or denoised_fn is not None:
+            return None
+        return GraphStepper(self, unet, batch, device, clip_denoised, update=update, eta=eta, lanes=lanes, cond=cond)
+
+    @staticmethod
+    def _replay(stepper, indices, before=None, after=None, state=True):
+        """Step a loaded stepper over `indices` and yield the state after every step (None without `state`); before(i) / after(i) run
+        around step i.  The stepper is closed when the generator ends, is closed or is dropped."""
+        try:
+            for i in indices:
+                if before is not None:
+                    before(i)
+                stepper.step(i)
+                if after is not None:
+                    after(i)
+                yield stepper.current() if state else None
+        finally:
+            stepper.close()
+
     def conditional_p_sample_loop(self, model, shape, use_fp16, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                   model_kwargs=None, device=None, progress=True, class_scale=0.):
         """class_scale == 0: replacement method; otherwise the gradient-guided method (gd:584-640)."""
@@ -421,7 +441,7 @@ class GaussianDiffusion:
     def _cond_setup(self, shape, noise, model_kwargs, device):
         device = self._sampling_device(device)
         if noise is None:
-            noise = {"video": self._start_noise(shape["video"], 0, device), "audio": self._start_noise(shape["audio"], 1, device)}
+            noise = self._x_T(shape, device)
         model_kwargs = model_kwargs if model_kwargs is not None else {}
         cond = {k: model_kwargs.pop(k) for k in ("video", "audio") if k in model_kwargs}     # popped like gd:687-691
         return device, noise, model_kwargs, cond
@@ -436,25 +456,21 @@ class GaussianDiffusion:
         device, noise, model_kwargs, cond = self._cond_setup(shape, noise, model_kwargs, device)
         x = dict(noise)
         B = shape["video"][0]
-        from .sampler import GraphStepper, unwrap_unet
-        unet = unwrap_unet(model)
-        stepper = None
-        if use_graph and unet is not None and not model_kwargs:
-            stepper = GraphStepper(self, unet, B, device, clip_denoised)
+        stepper = self._graph_stepper(model, model_kwargs, use_graph, B, device, clip_denoised)
+        if stepper is not None:
+            def replace(i):
+                t = th.tensor([i] * B, device=device)
+                for k in cond:
+                    stepper.set_x(k, self.q_sample(cond[k], t, noise=noise[k]))
             stepper.load(x["video"], x["audio"])
+            yield from self._replay(stepper, self._indices(progress), before=replace)
+            return
         for i in self._indices(progress):
             t = th.tensor([i] * B, device=device)
-            for k in ("video", "audio"):
-                if k in cond:
-                    x[k] = self.q_sample(cond[k], t, noise=noise[k])
-                    if stepper is not None:
-                        stepper.set_x(k, x[k])
-            if stepper is not None:
-                stepper.step(i)
-                x = stepper.current()
-            else:
-                with th.no_grad():
-                    x = self.p_sample(model, x, t, clip_denoised=clip_denoised, model_kwargs=model_kwargs)["sample"]
+            for k in cond:
+                x[k] = self.q_sample(cond[k], t, noise=noise[k])
+            with th.no_grad():
+                x = self.p_sample(model, x, t, clip_denoised=clip_denoised, model_kwargs=model_kwargs)["sample"]
             yield x
 
     def conditional_p_sample_loop_progressive_scale(self, model, shape, use_fp16, noise=None, clip_denoised=True, denoised_fn=None,
@@ -524,35 +540,26 @@ class GaussianDiffusion:
         conditioning noise; with a seeded.CounterNoise source x_T, the conditioning noise (regenerated in the kernel, no buffer) and the
         per-step noise all come from the counter and `noise` must be None."""
         from . import masking
-        from .sampler import GraphStepper, unwrap_unet
         if sampler not in ("ddpm", "ddim"):
             raise H.MMDError(f"masked_sample_loop: unknown sampler {sampler!r} (ddpm or ddim)")
         device = self._sampling_device(device)
-        cond = masking.normalize(known, mask, shape)
-        for k, c in cond.items():
-            H.require_cuda(c.known)
-            cond[k] = c._replace(known=c.known.to(device), mask=None if c.mask is None else c.mask.to(device))
+        cond = masking.to_device(masking.normalize(known, mask, shape), device)
         ctr = self._counter()
         if ctr is not None and noise is not None:
             raise H.MMDError("masked_sample_loop: a CounterNoise source draws x_T and the conditioning noise itself: noise must be None")
         if noise is None:
-            noise = {"video": self._start_noise(shape["video"], 0, device), "audio": self._start_noise(shape["audio"], 1, device)}
+            noise = self._x_T(shape, device)
         noise = {k: noise[k].to(device).float().contiguous() for k in ("video", "audio")}
         B = shape["video"][0]
-        unet = unwrap_unet(model)
         model_kwargs = model_kwargs or {}
-        if use_graph and unet is not None and not model_kwargs:
-            stepper = GraphStepper(self, unet, B, device, clip_denoised, update=sampler, eta=eta, lanes=lanes, cond=cond)
+        stepper = self._graph_stepper(model, model_kwargs, use_graph, B, device, clip_denoised, update=sampler, eta=eta, lanes=lanes, cond=cond)
+        if stepper is not None:
+            def paste(i):
+                if paste_known and i == 0:
+                    stepper.paste_known()
             stepper.load(noise["video"], noise["audio"])
             stepper.load_cond(cond, noise)
-            try:
-                for i in self._indices(progress):
-                    stepper.step(i)
-                    if paste_known and i == 0:
-                        stepper.paste_known()
-                    yield stepper.current()
-            finally:
-                stepper.close()
+            yield from self._replay(stepper, self._indices(progress), after=paste)
             return
         _, qtab = self.device_tables(device)
         x = dict(noise)
@@ -590,22 +597,12 @@ class GaussianDiffusion:
         if cond_fn is not None:
             raise NotImplementedError("cond_fn: see p_sample")
         device = self._sampling_device(device)
-        x = {"video": self._start_noise(shape["video"], 0, device), "audio": self._start_noise(shape["audio"], 1, device)}
-        indices = list(range(self.num_timesteps))[::-1]
-        if progress:
-            from tqdm.auto import tqdm
-            indices = tqdm(indices)
-        from .sampler import GraphStepper, unwrap_unet
-        unet = unwrap_unet(model)
-        if use_graph and unet is not None and not (model_kwargs or {}) and denoised_fn is None:
-            stepper = GraphStepper(self, unet, shape["video"][0], device, clip_denoised)
+        x = self._x_T(shape, device)
+        indices = self._indices(progress)
+        stepper = self._graph_stepper(model, model_kwargs, use_graph, shape["video"][0], device, clip_denoised, denoised_fn=denoised_fn)
+        if stepper is not None:
             stepper.load(x["video"], x["audio"])
-            try:
-                for i in indices:
-                    stepper.step(i)
-                    yield stepper.current()
-            finally:
-                stepper.close()
+            yield from self._replay(stepper, indices)
             return
         for i in indices:
             t = th.tensor([i] * shape["video"][0], device=device)
@@ -635,10 +632,6 @@ class GaussianDiffusion:
         ops.vlb_terms(x0, xt, mo, tab, t.to(th.int64).contiguous(), F, C, HW, self._flags(clip_denoised), vb, xstart_mse=xs,
                       eps_mse=em if nz is not None else None, noise=nz, pred_xstart=px0)
         return vb, xs, (em if nz is not None else None), px0
-
-    def _model_out2(self, model, x, t, model_kwargs):
-        """(video_output, audio_output) of the model at x_t; SpacedDiffusion maps the timesteps in here."""
-        return model(x["video"], x["audio"], self._scale_timesteps(t), **(model_kwargs or {}))
 
     def _vb_terms_bpd(self, model, x_start, x_t, t, clip_denoised=True, model_kwargs=None):
         """gd:1048-1092 -> {"output": {"video","audio"} [N] (KL for t > 0, decoder NLL at t == 0, bits / dim), "pred_xstart": {...}}."""
@@ -684,17 +677,12 @@ class GaussianDiffusion:
         device = x_start["video"].device
         self._sampling_device(device)
         B, T = x_start["video"].shape[0], self.num_timesteps
-        from .sampler import GraphStepper, unwrap_unet
-        unet = unwrap_unet(model)
-        if use_graph and unet is not None and not (model_kwargs or {}):
-            stepper = GraphStepper(self, unet, B, device, clip_denoised, update="vlb", lanes=lanes)
-            try:
-                stepper.load_x0(x_start["video"], x_start["audio"])
-                for i in self._indices(False):
-                    stepper.step(i)
-                tabs = stepper.results()
-            finally:
-                stepper.close()
+        stepper = self._graph_stepper(model, model_kwargs, use_graph, B, device, clip_denoised, update="vlb", lanes=lanes)
+        if stepper is not None:
+            stepper.load_x0(x_start["video"], x_start["audio"])
+            for _ in self._replay(stepper, self._indices(False), state=False):
+                pass
+            tabs = stepper.results()
         else:
             tabs = {k: tuple(th.zeros(B, T, dtype=th.float32, device=device) for _ in range(3)) for k in ("video", "audio")}
             for i in self._indices(False):

@@ -5,7 +5,13 @@ variational bound instead (calc_bpd_loop): [q_sample of both streams from static
 both streams], whose per-sample results land in device tables at the step's column.
 
 Replaces the per-step host work of the reference loop (gd:561-582 + resp:134-139): th.tensor([i]*B) H2D,
-the timestep_map tensor rebuild, ~16 table uploads and ~55k ATen dispatches."""
+the timestep_map tensor rebuild, ~16 table uploads and ~55k ATen dispatches.
+
+Structure: LaneStepper owns what every replayed step shares - the batch lanes and their engines, the conditioning buffers and the
+pre-plan that replaces the known cells, the per-step uploads, the lane events, and capture / launch / close over NAMED PLAN SETS
+(name -> per-lane plans behind the U-Net plan, and their per-lane graph execs once captured).  GraphStepper (DDPM / DDIM / variational
+bound) and DpmppStepper (DPM-Solver++) record their update plans into sets and say, in set_step, which set the next launch replays."""
+import ctypes
 import os
 
 import torch as th
@@ -39,156 +45,95 @@ def default_lanes(batch):
     return lanes if lanes >= 1 and batch % lanes == 0 else 1
 
 
-class GraphStepper:
-    """One denoising step of `batch` trajectories as one graph replay.
+STREAMS = (("video", 0), ("audio", 1))      # stream key, and its plan stream id = its counter tag
+
+
+class _PlanSet:
+    """One named plan set: the per-lane plans that follow the U-Net plan, and their per-lane graph execs (None before capture)."""
+
+    def __init__(self, plans):
+        self.plans, self.graphs = plans, None
+
+
+def _replay(ps, r, stream):
+    H.call("mmd_graph_launch", ps.graphs[r], stream)
+
+
+class LaneStepper:
+    """What a replayed step of `batch` trajectories is made of, whatever its update: lanes, conditioning, uploads, capture and launch.
 
     lanes > 1 splits the batch into independent sub-batches, each with its own engine (activation buffers, video + audio launch
     streams; packed weights are shared) and its own captured graph; the lane graphs are launched on the lanes' private streams,
     forked from and joined to the caller's stream with events.  Every sample's trajectory is independent (GroupNorm / attention
-    never mix batch elements, tests: batch sharding is bitwise exact), so the result is identical.  Noise and timestep buffers stay
-    full-batch (lanes read slices), so the RNG stream does not depend on `lanes`.  Default: see default_lanes.
+    never mix batch elements, tests: batch sharding is bitwise exact), so the result is identical.  Timestep, sample-id and noise
+    buffers stay full-batch (lanes read slices), so the RNG stream does not depend on `lanes`.  Default: see default_lanes.
 
-    With a seeded.CounterNoise as the diffusion's noise_source (update "ddpm" / "ddim") the step owns no noise buffers: the graph records
-    mmd_ddpm_update_ctr / mmd_ddim_update_ctr, which draw the noise of (seed, sample id, loop index, stream, element) in the kernel - a
-    lane reads its slice of the sample ids as it reads its slice of the timesteps - and set_step takes the window shifts from the counter.
+    A lane's launch is [pre-plan] + U-Net plan + the plans of the current set (self._set); subclasses record plans with _add_set."""
 
-    cond (masking.normalize's result; update "ddpm" / "ddim") conditions the step on known cells: every lane's graph starts with one
-    mmd_cond_replace per conditioned stream, which sets the known cells of the state to q_sample(known, t, noise = that stream's x_T)
-    and leaves the others alone (masked_sample_loop).  cond=None records nothing."""
-
-    def __init__(self, diffusion, unet, batch, device, clip_denoised=True, use_graph=True, update="ddpm", eta=0.0, lanes=None, cond=None):
-        if update not in ("ddpm", "ddim", "vlb"):
-            raise H.MMDError(f"unknown update {update!r} (ddpm, ddim or vlb)")
-        if cond and update == "vlb":
-            raise H.MMDError("masked conditioning rides the sampling steps (ddpm, ddim), not the variational bound")
-        self.diff, self.unet, self.N = diffusion, unet, int(batch)
-        self.device = th.device(device)
+    def __init__(self, unet, batch, device, lanes, use_graph, use_f32=False, ctr=None, own_ids=False):
+        self.unet, self.N, self.device = unet, int(batch), th.device(device)
         self.lanes = default_lanes(self.N) if lanes is None else int(lanes)
-        if self.N % self.lanes:
+        if self.lanes < 1 or self.N % self.lanes:
             raise H.MMDError(f"batch {self.N} does not split into {self.lanes} lanes")
-        n = self.n = self.N // self.lanes
-        self.engs = [unet.engine(n, self.device, replica=r) for r in range(self.lanes)]
-        self.eng = e = self.engs[0]
-        self.tab, _ = diffusion.device_tables(self.device)
-        self.flags = diffusion._flags(clip_denoised)
-        self.t_idx = th.zeros(self.N, dtype=th.int64, device=self.device)      # loop index (table row)
-        from .seeded import counter_source
-        self.ctr = ctr = counter_source(diffusion) if update != "vlb" else None
-        if ctr is not None:
-            self.noise_v = self.noise_a = None
+        self.n = self.N // self.lanes
+        self.engs = [unet.engine(self.n, self.device, replica=r) for r in range(self.lanes)]
+        self.eng = self.engs[0]
+        self.t_idx = th.zeros(self.N, dtype=th.int64, device=self.device)      # loop index / step number (table row)
+        self.ctr = ctr
+        if ctr is not None:      # own_ids: copies that a later source can be loaded into (DpmppStepper.retable)
             self.key, self.ids = ctr.key(self.device), ctr.ids(self.N, self.device)
-        else:
-            self.noise_v = th.zeros((self.N,) + tuple(e.x_video.shape[1:]), dtype=th.float32, device=self.device)
-            self.noise_a = th.zeros((self.N,) + tuple(e.x_audio.shape[1:]), dtype=th.float32, device=self.device)
-        # model timestep: SpacedDiffusion maps the loop index to the original step (resp:134-139)
-        tmap = getattr(diffusion, "timestep_map", None)
-        self.tmap = list(tmap) if tmap is not None else list(range(diffusion.num_timesteps))
-        self.rescale = bool(diffusion.rescale_timesteps)
-        self.orig_T = getattr(diffusion, "original_num_steps", diffusion.num_timesteps)
-        self.use_f32 = self.rescale
-        F, C, HW = e.F, e.Cv_in, e.H0 * e.W0
-        self.update_plans, self.pre_plans = [], []
-        if update == "vlb":
-            # static x_0, and per stream the (vb, xstart_mse, eps_mse) result tables [N, T] the reductions write at column t
-            T = self.tab.shape[1]
-            _, qtab = diffusion.device_tables(self.device)
-            self.x0_v, self.x0_a = th.zeros_like(self.noise_v), th.zeros_like(self.noise_a)
-            self.res = {k: tuple(th.zeros(self.N, T, dtype=th.float32, device=self.device) for _ in range(3)) for k in ("video", "audio")}
-            self._ws = [(ops.vlb_workspace(n, self.device), ops.vlb_workspace(n, self.device)) for _ in self.engs]
-        # masked conditioning (masking.normalize): per conditioned stream the static known values, one uint8 mask row per sample (none:
-        # the whole stream) and, without a counter source, the fixed conditioning noise (= that stream's x_T); load_cond fills them
-        self.cond = {}
-        for k, c in (cond or {}).items():
-            xk = e.x_video if k == "video" else e.x_audio
-            buf = {"known": th.zeros((self.N,) + tuple(xk.shape[1:]), dtype=th.float32, device=self.device),
-                   "mask": None if c.mask is None else th.zeros(self.N, F * HW if k == "video" else e.L0, dtype=th.uint8, device=self.device),
-                   "noise": None if ctr is not None else th.zeros((self.N,) + tuple(xk.shape[1:]), dtype=th.float32, device=self.device)}
-            self.cond[k] = buf
-        if self.cond:
-            _, self._qtab = diffusion.device_tables(self.device)
-        for r, e in enumerate(self.engs):
-            sl = slice(r * n, (r + 1) * n)
-            t_idx = self.t_idx[sl]
-            nv, na = (None, None) if ctr is not None else (self.noise_v[sl], self.noise_a[sl])
-            if self.cond:
-                pre = []
-                with ops.recording(pre):       # on the origin stream like the vlb pre-plan: the known cells at this step's noise level
-                    for k, tag in (("video", 0), ("audio", 1)):
-                        if k in self.cond:
-                            self._cond_replace(r, k, tag, self._qtab, t_idx, None)
-                self.pre_plans.append(pre)
-            plan = []
-            if update == "vlb":
-                pre = []
-                with ops.recording(pre):       # both on the origin stream: the U-Net plan forks its audio stream behind them
-                    ops.q_sample(self.x0_v[sl], nv, e.x_video, qtab, t_idx)
-                    ops.q_sample(self.x0_a[sl], na, e.x_audio, qtab, t_idx)
-                self.pre_plans.append(pre)
-            with ops.recording(plan):
-                # in place: x_{t-1} overwrites x_t (purely elementwise); each update rides its own stream, then join
-                if update == "vlb":
-                    rv, ra = (tuple(a[sl] for a in self.res[k]) for k in ("video", "audio"))
-                    with ops.on_stream(0):
-                        ops.vlb_terms(self.x0_v[sl], e.x_video, e.out_video, self.tab, t_idx, F, C, HW, self.flags, rv[0], xstart_mse=rv[1],
-                                      eps_mse=rv[2], noise=nv, ws=self._ws[r][0])
-                    with ops.on_stream(1):
-                        ops.vlb_terms(self.x0_a[sl], e.x_audio, e.out_audio, self.tab, t_idx, 1, e.Ca_in, e.L0, self.flags, ra[0],
-                                      xstart_mse=ra[1], eps_mse=ra[2], noise=na, ws=self._ws[r][1])
-                elif update == "ddim":       # ddim_sample (gd:821-901): same graph, different fused update
-                    tab3 = diffusion.ddim_tables(self.device)
-                    with ops.on_stream(0):
-                        if ctr is not None:
-                            ops.ddim_update_ctr(e.x_video, e.out_video, self.key, self.ids[sl], 0, e.x_video, self.tab, tab3, t_idx, F, C, HW,
-                                                self.flags, eta)
-                        else:
-                            ops.ddim_update(e.x_video, e.out_video, nv, e.x_video, self.tab, tab3, t_idx, F, C, HW, self.flags, eta)
-                    with ops.on_stream(1):
-                        if ctr is not None:
-                            ops.ddim_update_ctr(e.x_audio, e.out_audio, self.key, self.ids[sl], 1, e.x_audio, self.tab, tab3, t_idx, 1, e.Ca_in,
-                                                e.L0, self.flags, eta)
-                        else:
-                            ops.ddim_update(e.x_audio, e.out_audio, na, e.x_audio, self.tab, tab3, t_idx, 1, e.Ca_in, e.L0, self.flags, eta)
-                elif ctr is not None:
-                    with ops.on_stream(0):
-                        ops.ddpm_update_ctr(e.x_video, e.out_video, self.key, self.ids[sl], 0, e.x_video, self.tab, t_idx, F, C, HW, self.flags)
-                    with ops.on_stream(1):
-                        ops.ddpm_update_ctr(e.x_audio, e.out_audio, self.key, self.ids[sl], 1, e.x_audio, self.tab, t_idx, 1, e.Ca_in, e.L0,
-                                            self.flags)
-                else:
-                    with ops.on_stream(0):
-                        ops.ddpm_update(e.x_video, e.out_video, nv, e.x_video, self.tab, t_idx, F, C, HW, self.flags)
-                    with ops.on_stream(1):
-                        ops.ddpm_update(e.x_audio, e.out_audio, na, e.x_audio, self.tab, t_idx, 1, e.Ca_in, e.L0, self.flags)
-                ops.record_sync(1, 0)
-            self.update_plans.append(plan)
-        self.update_plan = self.update_plans[0]
-        self.graphs = None
-        self.use_graph = use_graph
+            if own_ids:
+                self.key, self.ids = self.key.clone(), self.ids.clone()
+        self.use_graph, self.use_f32 = use_graph, use_f32
+        self.cond, self.pre_plans = {}, []
+        self._sets, self._set = {}, "step"
         # per-step scalars go up through pinned rings (H.Staged): the host runs ahead of the GPU, one reused pinned buffer would race
         self._up_t = H.Staged(self.t_idx)
-        self._up_tm = [H.Staged(e.t_f32 if self.use_f32 else e.t_i64) for e in self.engs]
+        self._up_tm = [H.Staged(e.t_f32 if use_f32 else e.t_i64) for e in self.engs]
         # lane fork / join events (lane 0 rides the origin stream, lane r > 0 its engine's private `side` stream)
-        import ctypes
         self._lane_ev = []
         for _ in range(self.lanes + 1 if self.lanes > 1 else 0):
             ev = ctypes.c_void_p()
             H.call("mmd_event_create", ctypes.byref(ev))
             self._lane_ev.append(ev)
 
-    def load(self, video, audio):
-        n = self.n
-        for r, e in enumerate(self.engs):
-            e.x_video.copy_(video[r * n:(r + 1) * n])
-            e.x_audio.copy_(audio[r * n:(r + 1) * n])
+    def _lane(self, r):
+        return slice(r * self.n, (r + 1) * self.n)
 
-    def load_x0(self, video, audio):
-        """update="vlb": the clean clips every step noises afresh."""
-        self.x0_v.copy_(video)
-        self.x0_a.copy_(audio)
+    def _add_set(self, name, plans):
+        self._sets[name] = _PlanSet(plans)
+        return plans
+
+    @property
+    def graphs(self):
+        """The step set's per-lane graph execs, None before capture."""
+        return self._sets["step"].graphs
+
+    # ------------------------------------------------------------------ masked conditioning
+    def _record_cond(self, cond, qtab):
+        """cond (masking.normalize's result): per conditioned stream the static known values, one uint8 mask row per sample (none: the
+        whole stream) and, without a counter source, the fixed conditioning noise (= that stream's x_T); load_cond fills them.  Every
+        lane's pre-plan then starts the step with one mmd_cond_replace per conditioned stream, which sets the known cells of the state
+        to q_sample(known, t, noise) by the [2, T] table qtab and leaves the others alone.  cond=None records nothing."""
+        e = self.eng
+        for k, c in (cond or {}).items():
+            xk = e.x_video if k == "video" else e.x_audio
+            like = dict(size=(self.N,) + tuple(xk.shape[1:]), dtype=th.float32, device=self.device)
+            cells = e.F * e.H0 * e.W0 if k == "video" else e.L0
+            self.cond[k] = {"known": th.zeros(**like),
+                            "mask": None if c.mask is None else th.zeros(self.N, cells, dtype=th.uint8, device=self.device),
+                            "noise": None if self.ctr is not None else th.zeros(**like)}
+        for r in range(self.lanes if self.cond else 0):
+            pre = []
+            with ops.recording(pre):       # on the origin stream: the known cells at this step's noise level
+                for k, tag in STREAMS:
+                    if k in self.cond:
+                        self._cond_replace(r, k, tag, qtab, self.t_idx[self._lane(r)], None)
+            self.pre_plans.append(pre)
 
     def _cond_replace(self, r, k, tag, tab2, t, coef):
         """ops.cond_replace of stream k on lane r's state and its slices of the conditioning buffers; coef = (ca, cb) draws no noise."""
-        e, sl = self.engs[r], slice(r * self.n, (r + 1) * self.n)
+        e, sl = self.engs[r], self._lane(r)
         b = self.cond[k]
         src = {}
         if coef is None:
@@ -214,35 +159,53 @@ class GraphStepper:
     def paste_known(self):
         """The current state's known cells = the known values, bit for bit (after the last step)."""
         for r in range(self.lanes):
-            for k, tag in (("video", 0), ("audio", 1)):
+            for k, tag in STREAMS:
                 if k in self.cond:
                     self._cond_replace(r, k, tag, None, None, (1.0, 0.0))
 
-    def results(self):
-        """update="vlb": {"video" / "audio": (vb, xstart_mse, eps_mse)} [N, T] tables, column = loop index t."""
-        return self.res
+    # ------------------------------------------------------------------ state
+    def load(self, video, audio):
+        for r, e in enumerate(self.engs):
+            e.x_video.copy_(video[self._lane(r)])
+            e.x_audio.copy_(audio[self._lane(r)])
 
     def set_x(self, key, value):
         """Overwrite one stream of the current state (replacement-method conditional sampling)."""
-        n = self.n
         for r, e in enumerate(self.engs):
-            (e.x_video if key == "video" else e.x_audio).copy_(value[r * n:(r + 1) * n])
+            (e.x_video if key == "video" else e.x_audio).copy_(value[self._lane(r)])
 
     def current(self):
         if self.lanes == 1:
             return {"video": self.eng.x_video.clone(), "audio": self.eng.x_audio.clone()}
         return {"video": th.cat([e.x_video for e in self.engs]), "audio": th.cat([e.x_audio for e in self.engs])}
 
-    def _lane_launch(self, r, stream):
-        """Enqueue lane r's U-Net plan and fused update with `stream` as its video-chain stream (its engine's aux = audio chain)."""
+    # ------------------------------------------------------------------ per-step uploads
+    def _push_step(self, i, tm, shifts):
+        """Loop index i and model timestep tm into their device buffers, and the window shifts: one draw per block for the whole batch
+        (unet:619-620), from the counter with a CounterNoise (a model with a shift_source of its own keeps it)."""
+        self._up_t.host().fill_(i)
+        self._up_t.push()
+        for up in self._up_tm:
+            up.host().fill_(tm)
+            up.push()
+        if shifts is None:
+            own = self.ctr is not None and self.unet.shift_source is None
+            shifts = self.ctr.shifts(i, self.unet) if own else self.unet.draw_shifts()
+        for e in self.engs:
+            e.set_shifts(shifts)
+
+    # ------------------------------------------------------------------ capture and launch
+    def _lane_launch(self, ps, r, stream):
+        """Enqueue lane r's pre-plan, U-Net plan and its plan of set `ps` with `stream` as its video-chain stream (its engine's aux =
+        audio chain)."""
         e = self.engs[r]
         aux = e.aux.cuda_stream
         if self.pre_plans:
             ops.run_plan(self.pre_plans[r], stream, aux)
         ops.run_plan(e.plan_f32 if self.use_f32 else e.plan, stream, aux)
-        ops.run_plan(self.update_plans[r], stream, aux)
+        ops.run_plan(ps.plans[r], stream, aux)
 
-    def _capture(self):
+    def _capture(self, ps):
         """One graph PER LANE, each captured with the lane's own private stream as the capture origin and its engine's aux stream
         as the only forked stream.  (All lanes in one capture would need two non-origin streams - a lane's video and audio chains
         - that wait on each other at every cross-attention; the HIP runtime re-parents the waiting stream on each such wait, the
@@ -252,45 +215,168 @@ class GraphStepper:
         cur = th.cuda.current_stream(self.device)
         for r, e in enumerate(self.engs):
             e.side.wait_stream(cur)
-            self._lane_launch(r, e.side.cuda_stream)        # warm-up: one-time function attributes, lazy module load
+            self._lane_launch(ps, r, e.side.cuda_stream)        # warm-up: one-time function attributes, lazy module load
         th.cuda.synchronize(self.device)
         graphs = []
         for r, e in enumerate(self.engs):
             with H.capture(e.side.cuda_stream) as cap:
-                self._lane_launch(r, e.side.cuda_stream)
+                self._lane_launch(ps, r, e.side.cuda_stream)
             graphs.append(cap.exec)
-        self.graphs = graphs
+        ps.graphs = graphs
 
-    def _fan(self, body):
-        """Run body(r, stream) for every lane: lane streams fork from the current stream and join it again (plain events)."""
+    def _fan(self, body, ps):
+        """Run body(ps, r, stream) for every lane: lane streams fork from the current stream and join it again (plain events)."""
         cur = H.stream_handle()
         if self.lanes == 1:
-            body(0, cur)
+            body(ps, 0, cur)
             return
         lib = H.lib()
         lib.mmd_event_record(self._lane_ev[0], cur)
         for r, e in enumerate(self.engs):
             ls = e.side.cuda_stream
             lib.mmd_stream_wait_event(ls, self._lane_ev[0])
-            body(r, ls)
+            body(ps, r, ls)
             lib.mmd_event_record(self._lane_ev[r + 1], ls)
         for r in range(self.lanes):
             if lib.mmd_stream_wait_event(cur, self._lane_ev[r + 1]):
                 raise H.MMDError(f"lane join failed: {lib.mmd_last_error().decode()}")
 
+    def launch(self):
+        """Replay the current set (set_step chose it); a set is warmed up and captured the first time it is launched."""
+        ps = self._sets[self._set]
+        if self.use_graph:
+            if ps.graphs is None:
+                # capture replays the step once as warm-up: keep x intact around it
+                keep = [(e.x_video.clone(), e.x_audio.clone()) for e in self.engs]
+                self._capture(ps)
+                for e, (xv, xa) in zip(self.engs, keep):
+                    e.x_video.copy_(xv)
+                    e.x_audio.copy_(xa)
+            self._fan(_replay, ps)
+        else:
+            if self.lanes == 1:
+                self.eng.aux.wait_stream(th.cuda.current_stream(self.device))
+            self._fan(self._lane_launch, ps)
+
+    def step(self, i, shifts=None, noise=None):
+        self.set_step(i, shifts, noise)
+        self.launch()
+
+    def close(self):
+        """Retire every set's graph execs and its plans' join events, and the lane events (destroyed by H.reap() at the next safe
+        point, never here: this also runs as a finaliser from the cyclic GC, possibly on a half-built stepper)."""
+        try:
+            for ps in getattr(self, "_sets", {}).values():
+                for g in ps.graphs or []:
+                    H.retire("graph", g)
+                for ev in H.plan_events(*ps.plans):
+                    H.retire("event", ev)
+                ps.graphs = None
+                del ps.plans[:]
+            for ev in getattr(self, "_lane_ev", []):
+                H.retire("event", ev)
+            self.update_plan, self._lane_ev = [], []
+        except Exception:
+            pass
+
+    __del__ = close
+
+
+class GraphStepper(LaneStepper):
+    """One denoising step of `batch` trajectories as one graph replay per lane (LaneStepper): update "ddpm" / "ddim", or one step of the
+    variational bound ("vlb").
+
+    With a seeded.CounterNoise as the diffusion's noise_source (update "ddpm" / "ddim") the step owns no noise buffers: the graph records
+    mmd_ddpm_update_ctr / mmd_ddim_update_ctr, which draw the noise of (seed, sample id, loop index, stream, element) in the kernel - a
+    lane reads its slice of the sample ids as it reads its slice of the timesteps - and set_step takes the window shifts from the counter.
+
+    cond (masking.normalize's result; update "ddpm" / "ddim") conditions the step on known cells: every lane's graph starts with one
+    mmd_cond_replace per conditioned stream, with noise = that stream's x_T (masked_sample_loop).  cond=None records nothing."""
+
+    def __init__(self, diffusion, unet, batch, device, clip_denoised=True, use_graph=True, update="ddpm", eta=0.0, lanes=None, cond=None):
+        if update not in ("ddpm", "ddim", "vlb"):
+            raise H.MMDError(f"unknown update {update!r} (ddpm, ddim or vlb)")
+        if cond and update == "vlb":
+            raise H.MMDError("masked conditioning rides the sampling steps (ddpm, ddim), not the variational bound")
+        from .seeded import counter_source
+        ctr = counter_source(diffusion) if update != "vlb" else None
+        self.rescale = bool(diffusion.rescale_timesteps)
+        super().__init__(unet, batch, device, lanes, use_graph, use_f32=self.rescale, ctr=ctr)
+        self.diff, self.update, self.eta = diffusion, update, eta
+        self.tab, qtab = diffusion.device_tables(self.device)
+        self.flags = diffusion._flags(clip_denoised)
+        e, n = self.eng, self.n
+        self.noise_v = self.noise_a = None
+        if ctr is None:
+            self.noise_v = th.zeros((self.N,) + tuple(e.x_video.shape[1:]), dtype=th.float32, device=self.device)
+            self.noise_a = th.zeros((self.N,) + tuple(e.x_audio.shape[1:]), dtype=th.float32, device=self.device)
+        self._noise = {"video": self.noise_v, "audio": self.noise_a}
+        # model timestep: SpacedDiffusion maps the loop index to the original step (resp:134-139)
+        tmap = getattr(diffusion, "timestep_map", None)
+        self.tmap = list(tmap) if tmap is not None else list(range(diffusion.num_timesteps))
+        self.orig_T = getattr(diffusion, "original_num_steps", diffusion.num_timesteps)
+        self._record_cond(cond, qtab)
+        if update == "vlb":
+            # static x_0, and per stream the (vb, xstart_mse, eps_mse) result tables [N, T] the reductions write at column t
+            T = self.tab.shape[1]
+            self.x0_v, self.x0_a = th.zeros_like(self.noise_v), th.zeros_like(self.noise_a)
+            self._x0 = {"video": self.x0_v, "audio": self.x0_a}
+            self.res = {k: tuple(th.zeros(self.N, T, dtype=th.float32, device=self.device) for _ in range(3)) for k in ("video", "audio")}
+            self._ws = [(ops.vlb_workspace(n, self.device), ops.vlb_workspace(n, self.device)) for _ in self.engs]
+        elif update == "ddim":       # ddim_sample (gd:821-901): same graph, different fused update
+            self._tab3 = diffusion.ddim_tables(self.device)
+        plans = self.update_plans = self._add_set("step", [])
+        for r, e in enumerate(self.engs):
+            sl = self._lane(r)
+            # per stream: (stream id, key, state, model output, (F, C, HW), counter tag)
+            rows = ((0, "video", e.x_video, e.out_video, (e.F, e.Cv_in, e.H0 * e.W0), 0),
+                    (1, "audio", e.x_audio, e.out_audio, (1, e.Ca_in, e.L0), 1))
+            if update == "vlb":
+                pre = []
+                with ops.recording(pre):       # both on the origin stream: the U-Net plan forks its audio stream behind them
+                    for _, k, xk, *_ in rows:
+                        ops.q_sample(self._x0[k][sl], self._noise[k][sl], xk, qtab, self.t_idx[sl])
+                self.pre_plans.append(pre)
+            plan = []
+            with ops.recording(plan):
+                # in place: x_{t-1} overwrites x_t (purely elementwise); each update rides its own stream, then join
+                for row in rows:
+                    with ops.on_stream(row[0]):
+                        self._record_update(r, *row[1:])
+                ops.record_sync(1, 0)
+            plans.append(plan)
+        self.update_plan = plans[0]
+
+    def _record_update(self, r, k, x, out, geom, tag):
+        """Record lane r's update of one stream.  The noise source of the lane: (key, its sample ids, the stream's tag) for the kernels
+        that draw by counter, else (its slice of the stream's noise buffer,)."""
+        sl = self._lane(r)
+        t_idx, (F, C, HW) = self.t_idx[sl], geom
+        src = (self.key, self.ids[sl], tag) if self.ctr is not None else (self._noise[k][sl],)
+        if self.update == "vlb":
+            vb, xs, em = (a[sl] for a in self.res[k])
+            ops.vlb_terms(self._x0[k][sl], x, out, self.tab, t_idx, F, C, HW, self.flags, vb, xstart_mse=xs, eps_mse=em, noise=src[0],
+                          ws=self._ws[r][tag])
+        elif self.update == "ddim":
+            fn = ops.ddim_update_ctr if self.ctr is not None else ops.ddim_update
+            fn(x, out, *src, x, self.tab, self._tab3, t_idx, F, C, HW, self.flags, self.eta)
+        else:
+            fn = ops.ddpm_update_ctr if self.ctr is not None else ops.ddpm_update
+            fn(x, out, *src, x, self.tab, t_idx, F, C, HW, self.flags)
+
+    def load_x0(self, video, audio):
+        """update="vlb": the clean clips every step noises afresh."""
+        self.x0_v.copy_(video)
+        self.x0_a.copy_(audio)
+
+    def results(self):
+        """update="vlb": {"video" / "audio": (vb, xstart_mse, eps_mse)} [N, T] tables, column = loop index t."""
+        return self.res
+
     def set_step(self, i, shifts=None, noise=None):
         """Refresh the per-step device state: timestep, shifts, noise (video first, then audio - gd:453-454)."""
-        self._up_t.host().fill_(int(i))
-        self._up_t.push()
         tm = self.tmap[int(i)]
-        for up in self._up_tm:
-            up.host().fill_(float(tm) * (1000.0 / self.orig_T) if self.use_f32 else int(tm))
-            up.push()
-        if shifts is None:      # one draw per block for the whole batch (unet:619-620)
-            own = self.ctr is not None and self.unet.shift_source is None      # (a model with a shift_source of its own keeps it)
-            shifts = self.ctr.shifts(i, self.unet) if own else self.unet.draw_shifts()
-        for e in self.engs:
-            e.set_shifts(shifts)
+        self._push_step(int(i), float(tm) * (1000.0 / self.orig_T) if self.use_f32 else int(tm), shifts)
         if self.ctr is not None:
             if noise is not None:
                 raise H.MMDError("this step draws its noise in the update kernels (CounterNoise): it takes no noise tensors")
@@ -306,40 +392,6 @@ class GraphStepper:
             self.noise_v.normal_()
             self.noise_a.normal_()
 
-    def launch(self):
-        if self.use_graph:
-            if self.graphs is None:
-                # capture replays the step once as warm-up: keep x intact around it
-                keep = [(e.x_video.clone(), e.x_audio.clone()) for e in self.engs]
-                self._capture()
-                for e, (xv, xa) in zip(self.engs, keep):
-                    e.x_video.copy_(xv)
-                    e.x_audio.copy_(xa)
-            self._fan(lambda r, stream: H.call("mmd_graph_launch", self.graphs[r], stream))
-        else:
-            if self.lanes == 1:
-                self.eng.aux.wait_stream(th.cuda.current_stream(self.device))
-            self._fan(self._lane_launch)
-
-    def step(self, i, shifts=None, noise=None):
-        self.set_step(i, shifts, noise)
-        self.launch()
-
-    def close(self):
-        """Retire the graph exec and the update plan's join event (destroyed by H.reap() at the next safe point, never here: this
-        also runs as a finaliser from the cyclic GC)."""
-        try:
-            gs, self.graphs = getattr(self, "graphs", None) or [], None
-            for g in gs:
-                H.retire("graph", g)
-            for ev in H.plan_events(*(getattr(self, "update_plans", None) or [])) + list(getattr(self, "_lane_ev", [])):
-                H.retire("event", ev)
-            self.update_plans, self.update_plan, self._lane_ev = [], [], []
-        except Exception:
-            pass
-
-    __del__ = close
-
 
 # Which kernel a recorded DPM-Solver++ step takes its thresholding quantile from: "multi" = the three-level multi-workgroup selection
 # whose first level rides mmd_dpmpp_x0, "block" = mmd_abs_quantile (one workgroup per sample).  The two return the same bits; the choice
@@ -347,13 +399,13 @@ class GraphStepper:
 DPMPP_SELECT = "multi"
 
 
-class DpmppStepper(GraphStepper):
+class DpmppStepper(LaneStepper):
     """One evaluation of the fixed-grid multistep DPM-Solver / DPM-Solver++ loop (multimodal_dpm_solver_plus.DPM_Solver.sample_graph)
     as one graph replay per lane: [mmd_cond_replace of each conditioned stream] + U-Net plan + per stream on its own stream
     [mmd_dpmpp_x0 (+ the quantile selection) + mmd_dpmpp_update] + join.  Every coefficient sits in the device tables of
     DPM_Solver.graph_tables, indexed by the step number in t_idx, so the graph of one step serves them all.  The noise-prediction solver
-    updates from the model output directly; its closing denoise evaluation is a data prediction and has a second plan ("final").
-    Lanes, conditioning buffers, capture and launch are GraphStepper's.
+    updates from the model output directly; its closing denoise evaluation is a data prediction and has a second plan set ("final"),
+    which set_step selects at the denoise row.  Lanes, conditioning buffers, capture and launch are LaneStepper's.
 
     The tables have a fixed capacity (ROWS_CAP rows, the stride the recorded launches carry), so a stepper outlives one sampling call:
     retable() loads another time grid, order or seed into the same buffers and the captured graphs are replayed as they are
@@ -361,47 +413,25 @@ class DpmppStepper(GraphStepper):
     ROWS_CAP = 1024
 
     def __init__(self, solver, unet, batch, device, tabs, use_graph=True, lanes=None, cond=None, ctr=None, select=None):
-        self.diff, self.unet, self.N = None, unet, int(batch)
-        self.device = th.device(device)
-        self.lanes = default_lanes(self.N) if lanes is None else int(lanes)
-        if self.lanes < 1 or self.N % self.lanes:
-            raise H.MMDError(f"batch {self.N} does not split into {self.lanes} lanes")
-        n = self.n = self.N // self.lanes
         select = DPMPP_SELECT if select is None else select
         if select not in ("multi", "block"):
             raise H.MMDError(f"unknown selection {select!r} (multi or block)")
-        self.engs = [unet.engine(n, self.device, replica=r) for r in range(self.lanes)]
-        self.eng = e = self.engs[0]
+        super().__init__(unet, batch, device, lanes, use_graph, ctr=ctr, own_ids=True)      # own ids: retable() refills them
+        self.diff = None
         self.tab = {k: th.zeros(ops.DPMPP_TAB_ROWS, self.ROWS_CAP, dtype=th.float32, device=self.device) for k in ("video", "audio")}
         self._qtab = th.zeros(2, self.ROWS_CAP, dtype=th.float32, device=self.device)
-        self.t_idx = th.zeros(self.N, dtype=th.int64, device=self.device)      # step number (table row)
-        self.ctr = ctr
-        if ctr is not None:      # own copies: retable() refills them for another seed or other sample ids
-            self.key, self.ids = ctr.key(self.device).clone(), ctr.ids(self.N, self.device).clone()
-        self.predict_x0 = bool(solver.predict_x0)
         self.retable(tabs, ctr)
-        self.use_f32 = False
-        F, HW = e.F, e.H0 * e.W0
-        geom = {"video": (F, e.Cv_in, unet.video_out_channels, HW), "audio": (1, e.Ca_in, unet.audio_out_channels, e.L0)}
-        self.cond = {}
-        for k, c in (cond or {}).items():
-            xk = e.x_video if k == "video" else e.x_audio
-            self.cond[k] = {"known": th.zeros((self.N,) + tuple(xk.shape[1:]), dtype=th.float32, device=self.device),
-                            "mask": None if c.mask is None else th.zeros(self.N, F * HW if k == "video" else e.L0, dtype=th.uint8, device=self.device),
-                            "noise": None if ctr is not None else th.zeros((self.N,) + tuple(xk.shape[1:]), dtype=th.float32, device=self.device)}
-        predict_x0, thresholding, max_val = bool(solver.predict_x0), bool(solver.thresholding), float(solver.max_val)
+        self._record_cond(cond, self._qtab)
+        n, e = self.n, self.eng
+        geom = {"video": (e.F, e.Cv_in, unet.video_out_channels, e.H0 * e.W0), "audio": (1, e.Ca_in, unet.audio_out_channels, e.L0)}
+        self.predict_x0 = predict_x0 = bool(solver.predict_x0)
+        thresholding, max_val = bool(solver.thresholding), float(solver.max_val)
         self.has_final = not predict_x0      # the noise-prediction solver's denoise row needs the data-prediction plan
-        self.update_plans, self.final_plans, self.pre_plans, self._bufs = [], [], [], []
+        self.update_plans, self.final_plans, self._bufs = self._add_set("step", []), [], []
+        if self.has_final:
+            self._add_set("final", self.final_plans)
         for r, e in enumerate(self.engs):
-            sl = slice(r * n, (r + 1) * n)
-            t_idx = self.t_idx[sl]
-            if self.cond:
-                pre = []
-                with ops.recording(pre):
-                    for k, tag in (("video", 0), ("audio", 1)):
-                        if k in self.cond:
-                            self._cond_replace(r, k, tag, self._qtab, t_idx, None)
-                self.pre_plans.append(pre)
+            t_idx = self.t_idx[self._lane(r)]
             streams = []
             for sid, k, xk, ok in ((0, "video", e.x_video, e.out_video), (1, "audio", e.x_audio, e.out_audio)):
                 buf = {"m1": th.zeros_like(xk), "x0": th.empty_like(xk), "s": th.zeros(n, dtype=th.float32, device=self.device),
@@ -432,17 +462,6 @@ class DpmppStepper(GraphStepper):
             if self.has_final:
                 self.final_plans.append(record(True))
         self.update_plan = self.update_plans[0]
-        self.graphs = self.final_graphs = None
-        self.use_graph = use_graph
-        self._final = False
-        self._up_t = H.Staged(self.t_idx)
-        self._up_tm = [H.Staged(e.t_i64) for e in self.engs]
-        import ctypes
-        self._lane_ev = []
-        for _ in range(self.lanes + 1 if self.lanes > 1 else 0):
-            ev = ctypes.c_void_p()
-            H.call("mmd_event_create", ctypes.byref(ev))
-            self._lane_ev.append(ev)
 
     def retable(self, tabs, ctr=None):
         """Load the tables of DPM_Solver.graph_tables (and the key and sample ids of `ctr`) into the buffers the recorded plans read."""
@@ -469,51 +488,9 @@ class DpmppStepper(GraphStepper):
 
     def set_step(self, i, shifts=None, noise=None):
         """Refresh the per-evaluation device state: the step number, the model timestep and the window shifts (one draw per
-        evaluation, in the eager loop's order; from the counter with a CounterNoise)."""
+        evaluation, in the eager loop's order; from the counter with a CounterNoise), and choose the plan set of this row."""
         i = int(i)
         if not 0 <= i < self.rows:
             raise H.MMDError(f"step {i} is outside the {self.rows} rows of the tables")
-        self._final = self.has_final and self.kinds[i] == ops.DPMPP_KIND_DENOISE
-        self._up_t.host().fill_(i)
-        self._up_t.push()
-        for up in self._up_tm:
-            up.host().fill_(int(self.tm[i]))
-            up.push()
-        if shifts is None:
-            own = self.ctr is not None and self.unet.shift_source is None
-            shifts = self.ctr.shifts(i, self.unet) if own else self.unet.draw_shifts()
-        for e in self.engs:
-            e.set_shifts(shifts)
-
-    def _lane_launch(self, r, stream):
-        e = self.engs[r]
-        aux = e.aux.cuda_stream
-        if self.pre_plans:
-            ops.run_plan(self.pre_plans[r], stream, aux)
-        ops.run_plan(e.plan, stream, aux)
-        ops.run_plan((self.final_plans if self._final else self.update_plans)[r], stream, aux)
-
-    def launch(self):
-        # the step plan and the final plan have a graph each; GraphStepper.launch captures and replays whichever self.graphs names
-        if self._final:
-            self.graphs, keep = self.final_graphs, self.graphs
-            try:
-                super().launch()
-            finally:
-                self.final_graphs, self.graphs = self.graphs, keep
-        else:
-            super().launch()
-
-    def close(self):
-        try:
-            for g in getattr(self, "final_graphs", None) or []:
-                H.retire("graph", g)
-            self.final_graphs = None
-            for ev in H.plan_events(*(getattr(self, "final_plans", None) or [])):
-                H.retire("event", ev)
-            self.final_plans = []
-        except Exception:
-            pass
-        super().close()
-
-    __del__ = close
+        self._set = "final" if self.has_final and self.kinds[i] == ops.DPMPP_KIND_DENOISE else "step"
+        self._push_step(i, int(self.tm[i]), shifts)

@@ -256,6 +256,36 @@ def test_graph_and_eager_launch_and_lane_counts_agree():
         assert same(o["video"], outs[0]["video"]) and same(o["audio"], outs[0]["audio"])
 
 
+def test_kept_stepper_replays_both_plan_sets_on_another_grid():
+    """The noise-prediction solver with denoise=True launches two plan sets, the step and the closing data prediction ("final"), each with
+    graphs of its own.  A second call with another grid, order and step count reuses the kept stepper - both sets' captured graphs
+    against reloaded tables - and must give the bits of a fresh solver and of the eager multistep loop (run under torch.no_grad(): see
+    test_sample_graph_is_bitwise_the_eager_multistep_loop)."""
+    fl, model, solver = _solver(torch.float32, False, False)
+    x_T = _x_T(fl, 2, 7)
+    calls = [dict(steps=4, order=2, skip_type="time_uniform", denoise=True), dict(steps=6, order=1, skip_type="logSNR", denoise=True)]
+
+    def run(fn, kw, **more):
+        _replay(model, 13)
+        with torch.no_grad():
+            return fn({k: v.clone() for k, v in x_T.items()}, **kw, **more)
+    try:
+        got, kept = [], []
+        for kw in calls:
+            got.append(run(solver.sample_graph, kw))
+            kept.append(solver._stepper[1])
+        assert kept[1] is kept[0] and kept[0].final_plans, "the second call did not reuse the stepper, or it has no final plan set"
+        for kw, g in zip(calls, got):
+            fresh = run(_solver(torch.float32, False, False)[2].sample_graph, kw)
+            eager = run(solver.sample, kw, method="multistep")
+            for k in ("video", "audio"):
+                assert torch.isfinite(g[k]).all()
+                assert same(g[k], fresh[k]), (kw, k, "fresh solver", rel_l2(g[k].cpu(), fresh[k].cpu()))
+                assert same(g[k], eager[k]), (kw, k, "eager loop", rel_l2(g[k].cpu(), eager[k].cpu()))
+    finally:
+        model.shift_source = None
+
+
 @pytest.mark.parametrize("px,thr", [(True, True), (False, False)])
 def test_counter_noise_samples_are_addressable(px, thr):
     from mm_diffusion.seeded import CounterNoise

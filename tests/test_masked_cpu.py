@@ -112,6 +112,20 @@ def test_normalize_refuses_an_empty_condition():
             masking.normalize(known, None, SHAPE)
 
 
+def test_to_device_keeps_a_missing_mask_and_every_shape_and_dtype():
+    from mm_diffusion import masking
+    B, F, _, Hh, Ww = SHAPE["video"]
+    cond = masking.normalize(_known(), {"video": torch.ones(B, F, Hh, Ww, dtype=torch.bool)}, SHAPE)
+    out = masking.to_device(cond, "cpu")
+    assert set(out) == {"video", "audio"} and out["audio"].mask is None
+    for k, c in cond.items():
+        assert out[k].stride == c.stride and torch.equal(out[k].known, c.known)
+        assert out[k].known.dtype == torch.float32 and out[k].known.shape == c.known.shape and out[k].known.device.type == "cpu"
+    m = out["video"].mask
+    assert m.dtype == torch.uint8 and m.shape == cond["video"].mask.shape and torch.equal(m, cond["video"].mask)
+    assert masking.to_device({}, "cpu") == {}
+
+
 @pytest.mark.parametrize("vs,as_", [((8, 3, 16, 16), (1, 512)), ((16, 3, 64, 64), (1, 25600))])
 def test_prefix_masks(vs, as_):
     from mm_diffusion import masking
