@@ -168,6 +168,21 @@ int mmd_gn_conv1x1_skip(int dtype, const void* h, int64_t ldh, const float* gn_a
                         const void* W_skip, const float* bias_skip, void* Y, int64_t ldy, int M, int Cout, int K1, float* stats,
                         int64_t stats_ld, void* stream);
 
+/* The same ResBlock tail for the deeper levels, with K STREAMED instead of register-stationary (mmd_rtail.hip; the mapping of
+ * mmd_aconv): Y[m, :] = bf16( (W . act(h[m, :] * ga[s] + gb[s]) + bias) + float( bf16( W2 . x[m, :] + bias2 ) ) ), s = m / L.
+ * h [M, ldh] (K1 columns), x [M, ldx] (K2 columns), W [Cout][K1], W2 [Cout][K2] (mmd_conv_gemm's weight layout), ga / gb [M / L, K1]
+ * fp32 or BOTH null (h is already normalised: the launch then runs behind mmd_gn_apply), act: 0 none, 1 SiLU (ignored without the
+ * affine).  Bitwise equal - Y and the statistics records - to mmd_conv_gemm(x, W2, bias2) -> sk followed by the out conv the layer
+ * runs on the row-strip tile (mmd_gn_conv1x1[_stats](h, ..., R = sk, tile 131), or mmd_gn_apply + mmd_conv_gemm[_stats](tile 131)):
+ * the records are folded in that launch's order - one row fragment per wave at K1 >= 384 and at K1 = 128 with the affine and
+ * L >= 16384, two fragments otherwise.  stats (nullable) / stats_ld as mmd_conv_gemm_stats (M % 64 == 0).
+ * bf16; K1 in {128, 256, 384, 512}, K2 % 64 == 0 (64 ... 1024), Cout % 64 == 0, L >= 128, M % L == 0 (M need not be a multiple of
+ * the 128-row block); pointers and row strides 16-byte multiples; h and x must not overlap Y (whole address ranges are compared).
+ * Anything else is an argument error before any launch: no fallback inside the library. */
+int mmd_res_tail(const void* h, int64_t ldh, const float* ga, const float* gb, int act, const void* W, const float* bias, const void* x,
+                 int64_t ldx, const void* W2, const float* bias2, void* Y, int64_t ldy, int M, int L, int K1, int K2, int Cout,
+                 float* stats, int64_t stats_ld, void* stream);
+
 /* Spatial 3x3 conv whose input GroupNorm32(+FiLM)(+SiLU) is applied to the staged halo tile in LDS (tile 130, bf16, the nine
  * (0, dh, dw) taps, slices of whole frames): Y = conv3x3(act(A * gn_a[s(m)] + gn_b[s(m)])) + bias (+ R), zero padding of the
  * NORMALISED activation.  Replaces GroupNorm32 -> SiLU -> video_conv_spatial of the ResBlock in_layers (unet:339-340,83-99,

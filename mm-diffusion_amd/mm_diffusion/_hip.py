@@ -46,6 +46,7 @@ _PROTOS = {
     "mmd_conv_gemm_stats": (i32, [i32, vp, i64, vp, vp, vp, i64, vp, i64, i32, i32, i32, i32, C.POINTER(i32), i32, i32, i32, i32, vp, i64, vp]),
     "mmd_gn_conv1x1_stats": (i32, [i32, vp, i64, vp, vp, i32, i32, i64, vp, vp, vp, i64, vp, i64, i32, i32, i32, i32, vp, i64, vp]),
     "mmd_gn_conv1x1_skip": (i32, [i32, vp, i64, vp, vp, i32, i32, i64, vp, vp, vp, i64, i32, vp, vp, vp, i64, i32, i32, i32, vp, i64, vp]),
+    "mmd_res_tail": (i32, [vp, i64, vp, vp, i32, vp, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp, i64, vp]),
     "mmd_gn_conv_gemm": (i32, [i32, vp, i64, vp, vp, i32, i32, i64, vp, vp, vp, i64, vp, i64, i32, i32, i32, i32, C.POINTER(i32), i32, i32, i32, i32, vp]),
     "mmd_tconv_weight_bytes": (i64, [i32, i32]),
     "mmd_tconv_pack": (i32, [vp, vp, i32, i32, vp]),

@@ -29,6 +29,7 @@ _UP_LOWRES = ops._flag("MMD_UP_LOWRES")                   # _res_side
 _CROSS_SERIAL = ops._flag("MMD_CROSS_SERIAL")             # _cross
 _RESAMPLE_STATS = ops._flag("MMD_RESAMPLE_STATS")         # _resample_stats
 _SKIP_FUSE = ops._flag("MMD_SKIP_FUSE")                   # _res_tail
+_TAIL_STREAM = ops._TAIL_STREAM                           # _res_tail (MMD_TAIL_STREAM)
 
 
 class _Pool:
@@ -270,16 +271,33 @@ class UNetEngine:
         """The tail of a ResBlock half: out = out_conv(SiLU(norm(h))) + skip(xs).  make_out() allocates (or returns) the output buffer.
         A channel-changing block whose shapes the two-operand strip launch takes (ops.skip_fusable: the ds1 level) runs the 1x1 skip conv
         INSIDE the out conv's launch - the skip tensor is never allocated, written or read back; bitwise the two launches, which every other
-        block (and MMD_SKIP_FUSE=0) still runs."""
-        if s.cin != s.cout and _SKIP_FUSE and ops.skip_fusable(h, xs, s.cout, geom):
+        block (and MMD_SKIP_FUSE=0) still runs.  The deeper channel-changing blocks (ops.res_tail_ok: ds2 / ds4 / ds8, and the audio ds1 block
+        with a 512-channel skip input) do the same on the streamed launch (mmd_res_tail; MMD_TAIL_STREAM=0: the two launches), with the
+        out-conv norm inside it or behind gn_apply (ops.res_tail_norm_fused)."""
+        changing = s.cin != s.cout
+        strip = changing and ops.skip_fusable(h, xs, s.cout, geom)      # the strip fusion's shapes are its own: never the streamed launch
+        stream = changing and not strip and _TAIL_STREAM and ops.res_tail_ok(h, xs, s.cout, geom) and ops.res_tail_pays(h, xs)
+        if (strip and _SKIP_FUSE) or stream:
             dest = make_out()
             will_emit = True if self._rec_slice(dest)[0] is not None else None      # (as _gn_pw: the launch emits dest's statistics)
-            if ops.skip_fusable(h, xs, s.cout, geom, will_emit, dest):
+            (wo, bo), (wk, bk) = self._wb(s.out_conv), self._wb(s.skip)
+            if strip and ops.skip_fusable(h, xs, s.cout, geom, will_emit, dest):
                 a, b = self._gn_affine(h, s.out_norm, geom, film)
-                (wo, bo), (wk, bk) = self._wb(s.out_conv), self._wb(s.skip)
                 ops.gn_conv1x1_skip(h, a, b, geom, True, self._gemm_w(wo), self._f32(bo), xs, self._gemm_w(wk), self._f32(bk), out=dest,
                                     stats=self._stats_for(dest))
                 self._release(a, b)
+                return dest
+            if stream and ops.res_tail_ok(h, xs, s.cout, geom, will_emit, dest):
+                if ops.res_tail_norm_fused(h, s.cout, geom, will_emit):
+                    a, b = self._gn_affine(h, s.out_norm, geom, film)
+                    ops.res_tail(h, a, b, geom, True, self._gemm_w(wo), self._f32(bo), xs, self._gemm_w(wk), self._f32(bk), out=dest,
+                                 stats=self._stats_for(dest))
+                    self._release(a, b)
+                else:
+                    n1 = self._gn(h, s.out_norm, geom, True, film=film)
+                    ops.res_tail(n1, None, None, geom, True, self._gemm_w(wo), self._f32(bo), xs, self._gemm_w(wk), self._f32(bk), out=dest,
+                                 stats=self._stats_for(dest))
+                    self._release(n1)
                 return dest
             sk = self._pw(xs, *self._wb(s.skip))      # (the output buffer's stride or alignment rules the fused launch out)
         else:

@@ -623,6 +623,90 @@ def gn_conv1x1_skip(h, a, b, geom: Geom, act, w, bias, x, w_skip, bias_skip, out
     return out
 
 
+# The same tail for the deeper levels, K streamed (include/mmd.h: mmd_res_tail): 128 - 512 channels into the out conv, up to 1024 into
+# the skip conv.  Bitwise the two launches it replaces - Y and records - so the switch (MMD_TAIL_STREAM=0: the two launches) is a pure
+# speed choice, independent of MMD_SKIP_FUSE (the row-strip fusion of the ds1 level, which the engine tries first).
+_TAIL_STREAM = _flag("MMD_TAIL_STREAM")
+# Whether the out-conv norm rides in the launch (every column range of a row block redoes it: 2 - 8 times) or a gn_apply launch
+# materialises it first, per K1 of the out conv: both are bitwise equal, the choice is the kernel-level measurement of
+# tools/restail_bench.py (profiles/restail_ab.txt).  MMD_TAIL_NORM=0 / 1 forces one mode for every level (A/B).
+_TAIL_NORM = os.environ.get("MMD_TAIL_NORM", "")
+# measured (batch 2 and 4, cache-cold graph replays): at 256 channels the in-launch norm wins at every shape (ds2: +7 ... +17 us against
+# +0 ... +9 behind gn_apply); at 384 it is 0 - 5 us ahead of gn_apply first - and it drops that launch; at 512 (ds8: 8 column ranges
+# redo the norm) gn_apply first is 1 - 2 us ahead at batch 2
+_TAIL_NORM_FUSED_K1 = (256, 384)
+
+
+def res_tail_ok(h, x, cout, geom: Geom, stats=None, out=None):
+    """Whether the ResBlock out conv of h and the 1x1 skip conv of x can run as ONE streamed launch (mmd_res_tail) that is bitwise
+    equal - Y and statistics records - to conv_gemm(x) followed by the out conv with residual = sk.  Layer geometry and alignment only:
+    bf16 rows of whole per-sample slices of >= 128 rows, K1 in {128, 256, 384, 512}, K2 a multiple of 64 up to 1024, Cout % 64 == 0,
+    16-byte aligned rows; records need M % 64 == 0.  The two-launch path's out conv must be the row-strip tile (its record fold is the
+    one the launch reproduces).  In the base model: the channel-changing blocks of the ds2 / ds4 / ds8 levels, video and audio, and
+    the audio ds1 block with a 512-channel skip input."""
+    if h.dtype != torch.bfloat16 or x.dtype != torch.bfloat16 or h.dim() != 2 or x.dim() != 2 or h.shape[0] != x.shape[0]:
+        return False
+    M, K1 = h.shape
+    K2 = x.shape[1]
+    if K1 not in (128, 256, 384, 512) or K2 % 64 or not 64 <= K2 <= 1024 or cout % 64 or cout <= 0:
+        return False
+    if not (geom.covers(M) and geom.Tn >= 128) or (stats is not None and M % 64):
+        return False
+    if not strip_tile_pinned(h, cout, stats=stats):
+        return False
+    if K1 == 128 and geom.Tn >= 16384 and not _STRIP_K128_RF1:
+        return False                                   # (the library's A/B switch moves the two-launch path to another record fold)
+    ts = (h, x) + (() if out is None else (out,))
+    if any(t.stride(1) != 1 or t.stride(0) % 8 or t.data_ptr() % 16 for t in ts):
+        return False
+    return out is None or not (_ranges_overlap(h, out) or _ranges_overlap(x, out))
+
+
+def res_tail_pays(h, x):
+    """Where the engine uses the streamed tail among the launches res_tail_ok accepts: the shapes at which it beat the two launches
+    by more than their run-to-run spread (tools/restail_bench.py, profiles/restail_ab.txt).  A speed rule between bitwise-equal paths,
+    so it is free to look at anything.  Not shown as a win and left on two launches: 512 channels with a skip operand no wider than
+    the out conv's (ds8, 384 -> 512: 32 us of launches of 16 - 32 row blocks; within the spread or 1 - 2 us behind at every batch)."""
+    return h.shape[1] != 512 or x.shape[1] > 512
+
+
+def res_tail_norm_fused(h, cout, geom: Geom, stats=None):
+    """Whether the streamed tail applies the out-conv norm itself (True) or runs behind gn_apply (False).  At K1 = 128 the two-launch
+    path's record fold depends on whether ITS norm is fused (mmd_gemm.hip: dispatch_conv1x1_strip), so the mode follows gn_fusable there;
+    everywhere else the two modes are bitwise equal and the choice is a measured speed rule."""
+    K1 = h.shape[1]
+    if K1 == 128:
+        return strip_tile_pinned(h, cout, stats=stats, geom=geom) and gn_fusable(geom, K1, cout, h, stats, act=True)
+    if _TAIL_NORM in ("0", "1"):
+        return _TAIL_NORM == "1"
+    return K1 in _TAIL_NORM_FUSED_K1
+
+
+def res_tail(h, a, b, geom: Geom, act, w, bias, x, w_skip, bias_skip, out=None, stats=None):
+    """out = (w . act(h * a + b) + bias) + bf16(w_skip . x + bias_skip) with K streamed (include/mmd.h: mmd_res_tail); a = b = None: h
+    is already normalised.  Bitwise conv_gemm(x, w_skip, bias_skip) -> sk, then the out conv of h with residual = sk."""
+    _chk2d(h)
+    _chk2d(x)
+    M, K1 = h.shape
+    K2 = x.shape[1]
+    Cout = w.shape[0]
+    _chk_conv_w("res_tail", h, w, 1)
+    _chk_conv_w("res_tail", x, w_skip, 1)
+    if x.shape[0] != M or w_skip.shape[0] != Cout or h.dtype != torch.bfloat16 or not geom.covers(M) or (a is None) != (b is None):
+        raise H.MMDError(f"res_tail: h {tuple(h.shape)} {h.dtype} / x {tuple(x.shape)} / skip weight {tuple(w_skip.shape)} do not match, "
+                         "or the slices are not whole contiguous samples")
+    if a is not None and not all(tuple(t.shape) == (geom.S, K1) and t.dtype == torch.float32 and t.is_contiguous() for t in (a, b)):
+        raise H.MMDError(f"res_tail: the fused affine must be two contiguous fp32 [S, K1] tensors (got {tuple(a.shape)}, {tuple(b.shape)})")
+    out = alloc(M, Cout, dtype=h.dtype, device=h.device) if out is None else out
+    _chk2d(out)
+    meta = (f"res_tail<bf16,stream>[M={M},K={K1}+{K2},N={Cout}]", 2 * M * (K1 + K2) * Cout,
+            2 * (M * (K1 + K2) + M * Cout + Cout * (K1 + K2)) + 8 * Cout)
+    _dispatch("mmd_res_tail", h.data_ptr(), h.stride(0), H.ptr(a), H.ptr(b), 1 if act else 0, w.data_ptr(), H.ptr(bias), x.data_ptr(),
+              x.stride(0), w_skip.data_ptr(), H.ptr(bias_skip), out.data_ptr(), out.stride(0), M, geom.Tn, K1, K2, Cout,
+              *_stats_args(stats, M, Cout), meta=meta)
+    return out
+
+
 # GroupNorm(+FiLM)(+SiLU) of the INPUT of a 3x3 conv applied to the staged halo tile in LDS (mmd_gn_conv_gemm): the gn_apply pass in
 # front of the ResBlock in-convs disappears wherever the conv runs on tile 130.  Bitwise equal to gn_apply + conv_gemm(tile 130), so
 # the switch (MMD_HALO_GN=0: separate pass) is a pure speed choice.

@@ -42,7 +42,7 @@ ARMS = {
 }
 for _k, _v in [("MMD_TCONV", "0"), ("MMD_HALO_GN", "0"), ("MMD_VCONV_FUSED", "0"), ("MMD_ACONV", "0"), ("MMD_TATTN_FUSED", "0"),
                ("MMD_TATTN_PRE", "0"), ("MMD_GN_GROUP", "0"), ("MMD_GN_SMALL", "0"), ("MMD_GN_EPILOGUE", "0"), ("MMD_UP_LOWRES", "0"),
-               ("MMD_RESAMPLE_STATS", "0"), ("MMD_SKIP_FUSE", "0"), ("MMD_CROSS_SERIAL", "0"), ("MMD_HEAD_GEMM", "0"), ("MMD_EMB_AUX", "0"),
+               ("MMD_RESAMPLE_STATS", "0"), ("MMD_SKIP_FUSE", "0"), ("MMD_TAIL_STREAM", "0"), ("MMD_CROSS_SERIAL", "0"), ("MMD_HEAD_GEMM", "0"), ("MMD_EMB_AUX", "0"),
                ("MMD_GEMM_STRIP", "0"), ("MMD_GEMM_STRIP", "base"), ("MMD_GEMM_HALO", "0"), ("MMD_GEMM_HALO", "1"), ("MMD_HALO16", "0"),
                ("MMD_GEMM_RING", "0")]:
     ARMS[f"full-bf16-b2-{_k}={_v}"] = _arm("full", "bf16", 2, **{_k: _v})
