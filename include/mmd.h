@@ -470,6 +470,21 @@ int mmd_dpmpp_x0(const float* x, const float* model_out, float* x0raw, const flo
 int mmd_dpmpp_select(const float* x, void* workspace, int level0_done, int N, int64_t per_sample, float q, float* out, void* stream);
 int mmd_dpmpp_update(float* x, const float* m0, float* M1, const float* s, float max_val, const float* tab, const int64_t* k, int rows, int N,
                      int F, int C, int Cm, int HW, void* stream);
+/* One evaluation of the single-step DPM-Solver / DPM-Solver++ loop (multimodal_dpm_solver_plus.py:1277-1294; orders 1-3, dpm:532-887)
+ * from the same kind of table (fp32 [6][rows] = cx, ce, c0, c1, c2, kind; k as above; a sample whose k is outside [0, rows) writes
+ * nothing: not x, not XB, not MS).  A step of order p is p evaluations; its later stages combine the state and the model value at the
+ * step's START with the newest model value, so the step keeps two histories, both fp32 [N,F,C,HW]: XB, the state there, and MS, the
+ * model value there.  XB and MS must overlap neither x nor each other (x is updated in place; checked).
+ *   m0     form 0: the first C of src's Cm channels (src fp32 [N,F,Cm,HW], Cm = C or 2C: the model output for the noise-prediction
+ *          solver, or the x0raw that mmd_dpmpp_x0 filled, Cm = C), then clamp(m0, -s, s) / (s / max_val), s = max(s[n], 1), when s != NULL
+ *          form 1: cx[k] x + ce[k] eps, eps = the first C channels of src (the data prediction without thresholding, the bits of
+ *          mmd_dpmpp_x0 followed by form 0 without that launch); s must be NULL
+ *   kind   0 open, the first evaluation of a step of any order: XB = x, MS = m0, x = c0 x + c1 m0
+ *          1 stage, the second or third evaluation: x = c0 XB + c1 MS + c2 m0; XB and MS are not written
+ *          2 denoise (denoise_fn, dpm:526-530): x = m0; XB and MS are not written
+ * The sums are mmd_lincomb's, term by term (one product, then one fma per further term). */
+int mmd_dpm_single_update(float* x, const float* src, int form, float* XB, float* MS, const float* s, float max_val, const float* tab,
+                          const int64_t* k, int rows, int N, int F, int C, int Cm, int HW, void* stream);
 /* adaptive-step error term (dpm:1088-1149): out[n] += sum(((hi - lo) / max(atol, rtol max(|lo|, |prev|)))^2), fp64, caller zeroes. */
 int mmd_dpm_err(const float* hi, const float* lo, const float* prev, float atol, float rtol, int N, int64_t per_sample, double* out,
                 void* stream);

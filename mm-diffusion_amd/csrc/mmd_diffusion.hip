@@ -1068,3 +1068,63 @@ extern "C" int mmd_dpmpp_update(float* x, const float* m0, float* M1, const floa
   const DpmppTab t{tab, k, rows};
   return mmd_launch<dpmpp_update_kernel>("dpmpp_update", dim3(ew_grid((int64_t)N * F * C * HW)), dim3(256), 0, (hipStream_t)stream, p, t, x, M1, s, max_val);
 }
+
+// ----------------------------------------------------------------------------- DPM-Solver / DPM-Solver++ single-step step, graph form
+// One evaluation of the single-step loop (DPM_Solver.sample(method="singlestep"), dpm:1277-1300, with dpm_solver_first_update
+// dpm:532-590, singlestep_dpm_solver_second_update dpm:590-704 and singlestep_dpm_solver_third_update dpm:706-887) from the same tables:
+// a step of order p is p evaluations, and every later stage combines the state and the model value at the START of the step with the
+// newest model value, so the step keeps two histories, XB (the state there) and MS (the model value there).  The row's kind:
+//   0 open (first evaluation of a step)  XB = x, MS = m0, x = c0 x + c1 m0     1 stage  x = c0 XB + c1 MS + c2 m0 (XB, MS kept)
+//   2 denoise  x = m0 (XB, MS kept)
+// X0FORM: m0 = cx x + ce eps in the kernel (the data prediction without thresholding: mmd_dpmpp_x0's value without its launch), else
+// m0 = the source's first C channels, clamp-scaled by s[n] when s is given.
+template <bool X0FORM>
+__global__ __launch_bounds__(256) void dpm_single_update_kernel(const DiffusionParams p, const DpmppTab t, float* x, float* XB, float* MS,
+                                                                const float* __restrict__ s, float max_val) {
+  const int64_t per = (int64_t)p.F * p.C * p.HW;
+  const int64_t total = per * p.N;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int64_t n = i / per;
+    const int64_t ki = t.k[n];
+    if (ki < 0 || ki >= t.rows) continue;
+    const float c0 = t.tab[2 * t.rows + ki], c1 = t.tab[3 * t.rows + ki], c2 = t.tab[4 * t.rows + ki];
+    const int kind = (int)t.tab[5 * t.rows + ki];
+    const ElemAddr a = elem_addr(p, n, i % per);
+    const float xv = x[i];
+    float m0 = p.mo[a.mean];
+    if (X0FORM) m0 = lincomb_add(lincomb_first(t.tab[ki], xv), t.tab[t.rows + ki], m0);
+    else if (s) m0 = clamp_scale_elem(m0, s[n], max_val);
+    if (kind == 0) {
+      XB[i] = xv;
+      MS[i] = m0;
+      x[i] = lincomb_add(lincomb_first(c0, xv), c1, m0);
+    } else if (kind == 1) {
+      x[i] = lincomb_add(lincomb_add(lincomb_first(c0, XB[i]), c1, MS[i]), c2, m0);
+    } else {
+      x[i] = m0;
+    }
+  }
+}
+
+// [a, a + n) and [b, b + n) floats share no byte
+static bool dpm_disjoint(const float* a, const float* b, int64_t n) {
+  const uintptr_t ua = (uintptr_t)a, ub = (uintptr_t)b, len = (uintptr_t)n * sizeof(float);
+  return ua + len <= ub || ub + len <= ua;
+}
+
+extern "C" int mmd_dpm_single_update(float* x, const float* src, int form, float* XB, float* MS, const float* s, float max_val, const float* tab,
+                                     const int64_t* k, int rows, int N, int F, int C, int Cm, int HW, void* stream) {
+  MMD_REQUIRE(x && src && XB && MS && tab && k, "dpm_single_update: needs x, the source of m0, XB, MS, the table and the step numbers");
+  MMD_REQUIRE(form == 0 || form == 1, "dpm_single_update: form is 0 (m0 = the source) or 1 (m0 = cx x + ce eps); got %d", form);
+  MMD_REQUIRE(!s || form == 0, "dpm_single_update: thresholding (s != NULL) goes with form 0 only: the quantile is taken of the stored x0raw");
+  MMD_REQUIRE(!s || max_val > 0.f, "dpm_single_update: max_val must be positive with thresholding (s != NULL)");
+  if (int rc = dpmpp_geom_ok("dpm_single_update", rows, N, F, C, Cm, HW)) return rc;
+  const int64_t total = (int64_t)N * F * C * HW;
+  MMD_REQUIRE(dpm_disjoint(x, XB, total) && dpm_disjoint(x, MS, total) && dpm_disjoint(XB, MS, total),
+              "dpm_single_update: XB and MS must overlap neither x nor each other (x is updated in place, the stages read both)");
+  const DiffusionParams p{nullptr, src, nullptr, nullptr, 0, N, F, C, HW, Cm == C ? 0 : 4};
+  const DpmppTab t{tab, k, rows};
+  const dim3 grid(ew_grid(total));
+  if (form == 1) return mmd_launch<dpm_single_update_kernel<true>>("dpm_single_update", grid, dim3(256), 0, (hipStream_t)stream, p, t, x, XB, MS, s, max_val);
+  return mmd_launch<dpm_single_update_kernel<false>>("dpm_single_update", grid, dim3(256), 0, (hipStream_t)stream, p, t, x, XB, MS, s, max_val);
+}

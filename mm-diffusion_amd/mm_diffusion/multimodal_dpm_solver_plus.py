@@ -15,7 +15,10 @@ exact radix-select quantile + clamp (mmd_abs_quantile / mmd_clamp_scale); the ad
 `DPM_Solver.sample_graph` runs the fixed-grid multistep method (orders 1 and 2) without any of those host scalars in the launch path:
 the coefficients go into device tables indexed by the step number (`graph_tables`, built from the helpers the eager updates call) and
 one evaluation is one graph replay per lane (sampler.DpmppStepper: mmd_dpmpp_x0 / mmd_dpmpp_select / mmd_dpmpp_update), bitwise the
-eager loop, with batch lanes, seeded.CounterNoise and the partial masks of masked_sample_loop.
+eager loop, with batch lanes, seeded.CounterNoise and the partial masks of masked_sample_loop.  `DPM_Solver.sample_graph_singlestep`
+does the same for the single-step method of orders 1-3 (the reference sampling script's call): `singlestep_tables` has one row per network
+evaluation - a step of order p is p rows, at s, s1 and s2 - and the recorded update is mmd_dpm_single_update (sampler.DpmSingleStepper).
+The two share one driver (`_graph_loop`) and the stepper kept from the last call.
 
 Reference behaviours reproduced knowingly:
   * the noise-prediction first-order update moves the AUDIO stream with the x0-form coefficients
@@ -298,6 +301,27 @@ class DPM_Solver:
             return [1, ] * steps
         raise ValueError("'order' must be '1' or '2' or '3'.")
 
+    def _single_grid(self, steps, order, skip_type, method, t_T, t_0):
+        """(orders, host time grid) of the single-step loop (dpm:1277-1284): 'singlestep' spends `steps` evaluations on steps of the
+        orders get_orders_for_singlestep_solver lists, 'singlestep_fixed' on steps // order steps of the full order."""
+        if method == "singlestep":
+            orders = self.get_orders_for_singlestep_solver(steps=steps, order=order)
+            timesteps = self.get_time_steps(skip_type=skip_type, t_T=t_T, t_0=t_0, N=steps, device="cpu")
+        else:
+            K = steps // order
+            orders = [order, ] * K
+            timesteps = self.get_time_steps(skip_type=skip_type, t_T=t_T, t_0=t_0, N=(K * order), device="cpu")
+        return orders, timesteps
+
+    def _single_ratios(self, timesteps, i, order):
+        """(r1, r2) of the step of `order` that starts at grid point i: where its inner grid points lie in lambda (dpm:1290-1292)."""
+        ns = self.noise_schedule
+        tc = timesteps.detach().float().cpu()
+        h = ns.marginal_lambda(tc[i + order]) - ns.marginal_lambda(tc[i])
+        r1 = None if order <= 1 else (ns.marginal_lambda(tc[i + 1]) - ns.marginal_lambda(tc[i])) / h
+        r2 = None if order <= 2 else (ns.marginal_lambda(tc[i + 2]) - ns.marginal_lambda(tc[i])) / h
+        return r1, r2
+
     def denoise_fn(self, x, s):
         return self.data_prediction_fn(x, s)
 
@@ -359,6 +383,70 @@ class DPM_Solver:
             cd = -0.5 * _f(sig_t * (torch.exp(h) - 1.))
         return c0, c1 + cd * inv_r0, -cd * inv_r0
 
+    @staticmethod
+    def _ratio(r):
+        """a step ratio r1 / r2 (host tensor of sample(), or a number) as a host fp32 tensor [1]."""
+        return r.detach().float().cpu().reshape(-1)[:1] if torch.is_tensor(r) else torch.tensor([float(r)])
+
+    def _single_second_coefs(self, s, t, r1, solver_type):
+        """The single-step second-order update s -> t (dpm:590-704): (s1, (a1, b1), (c0, c1, c2)) with x_s1 = a1 x + b1 m_s and
+        x_t = c0 x + c1 m_s + c2 m_s1 (c1 has the -c2 of c2 (m_s1 - m_s) in it, formed in double and rounded once by the kernel's argument)."""
+        if solver_type not in ["dpm_solver", "taylor"]:
+            raise ValueError(f"'solver_type' must be either 'dpm_solver' or 'taylor', got {solver_type}")
+        r1t = self._ratio(0.5 if r1 is None else r1)
+        (lam_s, la_s, sig_s), (lam_t, la_t, sig_t) = self._sc(s, t)
+        h = lam_t - lam_s
+        s1 = self.noise_schedule.inverse_lambda(lam_s + r1t * h)
+        (_, la_s1, sig_s1), = self._sc(s1)
+        alpha_s1, alpha_t = torch.exp(la_s1), torch.exp(la_t)
+        r1f = _f(r1t)
+        if self.predict_x0:
+            phi_11, phi_1 = torch.expm1(-r1t * h), torch.expm1(-h)
+            a1, b1 = _f(sig_s1 / sig_s), -_f(alpha_s1 * phi_11)
+            c0, c1 = _f(sig_t / sig_s), -_f(alpha_t * phi_1)
+            c2 = (-(0.5 / r1f) * _f(alpha_t * phi_1)) if solver_type == "dpm_solver" else \
+                ((1. / r1f) * _f(alpha_t * ((torch.exp(-h) - 1.) / h + 1.)))
+        else:
+            phi_11, phi_1 = torch.expm1(r1t * h), torch.expm1(h)
+            a1, b1 = _f(torch.exp(la_s1 - la_s)), -_f(sig_s1 * phi_11)
+            c0, c1 = _f(torch.exp(la_t - la_s)), -_f(sig_t * phi_1)
+            c2 = (-(0.5 / r1f) * _f(sig_t * phi_1)) if solver_type == "dpm_solver" else \
+                (-(1. / r1f) * _f(sig_t * ((torch.exp(h) - 1.) / h - 1.)))
+        return s1, (a1, b1), (c0, c1 - c2, c2)
+
+    def _single_third_coefs(self, s, t, r1, r2, solver_type):
+        """The single-step third-order update s -> t (dpm:706-887): (s1, s2, (a1, b1), (a2, b2, d2), (c0, c1, c2)) with
+        x_s1 = a1 x + b1 m_s, x_s2 = a2 x + b2 m_s + d2 m_s1 and x_t = c0 x + c1 m_s + c2 m_s2 (b2 and c1 hold the -d2 and -c2 of the
+        differences, formed in double)."""
+        if solver_type not in ["dpm_solver", "taylor"]:
+            raise ValueError(f"'solver_type' must be either 'dpm_solver' or 'taylor', got {solver_type}")
+        if solver_type == "taylor":
+            raise NotImplementedError("third-order 'taylor' update: the reference subtracts stream dicts (dpm:761-764) / reads an "
+                                      "undefined name (dpm:873) and raises")
+        r1t, r2t = self._ratio(1. / 3. if r1 is None else r1), self._ratio(2. / 3. if r2 is None else r2)
+        ns = self.noise_schedule
+        (lam_s, la_s, sig_s), (lam_t, la_t, sig_t) = self._sc(s, t)
+        h = lam_t - lam_s
+        s1, s2 = ns.inverse_lambda(lam_s + r1t * h), ns.inverse_lambda(lam_s + r2t * h)
+        (_, la_s1, sig_s1), (_, la_s2, sig_s2) = self._sc(s1, s2)
+        alpha_s1, alpha_s2, alpha_t = torch.exp(la_s1), torch.exp(la_s2), torch.exp(la_t)
+        r1f, r2f = _f(r1t), _f(r2t)
+        if self.predict_x0:
+            phi_11, phi_12, phi_1 = torch.expm1(-r1t * h), torch.expm1(-r2t * h), torch.expm1(-h)
+            phi_22 = torch.expm1(-r2t * h) / (r2t * h) + 1.
+            phi_2 = phi_1 / h + 1.
+            a1, b1 = _f(sig_s1 / sig_s), -_f(alpha_s1 * phi_11)
+            a2, b2, d2 = _f(sig_s2 / sig_s), -_f(alpha_s2 * phi_12), (r2f / r1f) * _f(alpha_s2 * phi_22)
+            c0, c1, c2 = _f(sig_t / sig_s), -_f(alpha_t * phi_1), (1. / r2f) * _f(alpha_t * phi_2)
+        else:
+            phi_11, phi_12, phi_1 = torch.expm1(r1t * h), torch.expm1(r2t * h), torch.expm1(h)
+            phi_22 = torch.expm1(r2t * h) / (r2t * h) - 1.
+            phi_2 = phi_1 / h - 1.
+            a1, b1 = _f(torch.exp(la_s1 - la_s)), -_f(sig_s1 * phi_11)
+            a2, b2, d2 = _f(torch.exp(la_s2 - la_s)), -_f(sig_s2 * phi_12), -(r2f / r1f) * _f(sig_s2 * phi_22)
+            c0, c1, c2 = _f(torch.exp(la_t - la_s)), -_f(sig_t * phi_1), -(1. / r2f) * _f(sig_t * phi_2)
+        return s1, s2, (a1, b1), (a2, b2 - d2, d2), (c0, c1 - c2, c2)
+
     # ------------------------------------------------------------------ first order (DDIM)
     def dpm_solver_first_update(self, x, s, t, model_s=None, return_intermediate=False):
         c = self._first_coefs(s, t)
@@ -370,88 +458,31 @@ class DPM_Solver:
 
     # ------------------------------------------------------------------ single-step second order
     def singlestep_dpm_solver_second_update(self, x, s, t, r1=0.5, model_s=None, return_intermediate=False, solver_type="dpm_solver"):
-        if solver_type not in ["dpm_solver", "taylor"]:
-            raise ValueError(f"'solver_type' must be either 'dpm_solver' or 'taylor', got {solver_type}")
-        if r1 is None:
-            r1 = 0.5
-        ns = self.noise_schedule
-        r1t = r1.detach().float().cpu().reshape(-1)[:1] if torch.is_tensor(r1) else torch.tensor([float(r1)])
-        (lam_s, la_s, sig_s), (lam_t, la_t, sig_t) = self._sc(s, t)
-        h = lam_t - lam_s
-        s1 = ns.inverse_lambda(lam_s + r1t * h)
-        (_, la_s1, sig_s1), = self._sc(s1)
-        alpha_s1, alpha_t = torch.exp(la_s1), torch.exp(la_t)
+        s1, (a1, b1), (c0, c1, c2) = self._single_second_coefs(s, t, r1, solver_type)
         x = self._prep(x)
         B = self._batch(x)
         if model_s is None:
             model_s = self.model_fn(x, s)
-        r1f = _f(r1t)
-        if self.predict_x0:
-            phi_11, phi_1 = torch.expm1(-r1t * h), torch.expm1(-h)
-            a1, b1 = _f(sig_s1 / sig_s), -_f(alpha_s1 * phi_11)
-            x_s1 = self._streams(lambda k: _comb([(a1, x[k]), (b1, model_s[k])]))
-            model_s1 = self.model_fn(x_s1, s1.expand(B))
-            c0, c1 = _f(sig_t / sig_s), -_f(alpha_t * phi_1)
-            c2 = (-(0.5 / r1f) * _f(alpha_t * phi_1)) if solver_type == "dpm_solver" else \
-                ((1. / r1f) * _f(alpha_t * ((torch.exp(-h) - 1.) / h + 1.)))
-        else:
-            phi_11, phi_1 = torch.expm1(r1t * h), torch.expm1(h)
-            a1, b1 = _f(torch.exp(la_s1 - la_s)), -_f(sig_s1 * phi_11)
-            x_s1 = self._streams(lambda k: _comb([(a1, x[k]), (b1, model_s[k])]))
-            model_s1 = self.model_fn(x_s1, s1.expand(B))
-            c0, c1 = _f(torch.exp(la_t - la_s)), -_f(sig_t * phi_1)
-            c2 = (-(0.5 / r1f) * _f(sig_t * phi_1)) if solver_type == "dpm_solver" else \
-                (-(1. / r1f) * _f(sig_t * ((torch.exp(h) - 1.) / h - 1.)))
+        x_s1 = self._streams(lambda k: _comb([(a1, x[k]), (b1, model_s[k])]))
+        model_s1 = self.model_fn(x_s1, s1.expand(B))
         # c0 x + c1 m_s + c2 (m_s1 - m_s)
-        x_t = self._streams(lambda k: _comb([(c0, x[k]), (c1 - c2, model_s[k]), (c2, model_s1[k])]))
+        x_t = self._streams(lambda k: _comb([(c0, x[k]), (c1, model_s[k]), (c2, model_s1[k])]))
         return (x_t, {"model_s": model_s, "model_s1": model_s1}) if return_intermediate else x_t
 
     # ------------------------------------------------------------------ single-step third order
     def singlestep_dpm_solver_third_update(self, x, s, t, r1=1. / 3., r2=2. / 3., model_s=None, model_s1=None, return_intermediate=False,
                                            solver_type="dpm_solver"):
-        if solver_type not in ["dpm_solver", "taylor"]:
-            raise ValueError(f"'solver_type' must be either 'dpm_solver' or 'taylor', got {solver_type}")
-        if solver_type == "taylor":
-            raise NotImplementedError("third-order 'taylor' update: the reference subtracts stream dicts (dpm:761-764) / reads an "
-                                      "undefined name (dpm:873) and raises")
-        r1 = 1. / 3. if r1 is None else r1
-        r2 = 2. / 3. if r2 is None else r2
-        ns = self.noise_schedule
-        tt = lambda r: r.detach().float().cpu().reshape(-1)[:1] if torch.is_tensor(r) else torch.tensor([float(r)])   # noqa: E731
-        r1t, r2t = tt(r1), tt(r2)
-        (lam_s, la_s, sig_s), (lam_t, la_t, sig_t) = self._sc(s, t)
-        h = lam_t - lam_s
-        s1, s2 = ns.inverse_lambda(lam_s + r1t * h), ns.inverse_lambda(lam_s + r2t * h)
-        (_, la_s1, sig_s1), (_, la_s2, sig_s2) = self._sc(s1, s2)
-        alpha_s1, alpha_s2, alpha_t = torch.exp(la_s1), torch.exp(la_s2), torch.exp(la_t)
+        s1, s2, (a1, b1), (a2, b2, d2), (c0, c1, c2) = self._single_third_coefs(s, t, r1, r2, solver_type)
         x = self._prep(x)
         B = self._batch(x)
-        r1f, r2f = _f(r1t), _f(r2t)
         if model_s is None:
             model_s = self.model_fn(x, s)
-        if self.predict_x0:
-            phi_11, phi_12, phi_1 = torch.expm1(-r1t * h), torch.expm1(-r2t * h), torch.expm1(-h)
-            phi_22 = torch.expm1(-r2t * h) / (r2t * h) + 1.
-            phi_2 = phi_1 / h + 1.
-            if model_s1 is None:
-                a1, b1 = _f(sig_s1 / sig_s), -_f(alpha_s1 * phi_11)
-                x_s1 = self._streams(lambda k: _comb([(a1, x[k]), (b1, model_s[k])]))
-                model_s1 = self.model_fn(x_s1, s1.expand(B))
-            a2, b2, d2 = _f(sig_s2 / sig_s), -_f(alpha_s2 * phi_12), (r2f / r1f) * _f(alpha_s2 * phi_22)
-            c0, c1, c2 = _f(sig_t / sig_s), -_f(alpha_t * phi_1), (1. / r2f) * _f(alpha_t * phi_2)
-        else:
-            phi_11, phi_12, phi_1 = torch.expm1(r1t * h), torch.expm1(r2t * h), torch.expm1(h)
-            phi_22 = torch.expm1(r2t * h) / (r2t * h) - 1.
-            phi_2 = phi_1 / h - 1.
-            if model_s1 is None:
-                a1, b1 = _f(torch.exp(la_s1 - la_s)), -_f(sig_s1 * phi_11)
-                x_s1 = self._streams(lambda k: _comb([(a1, x[k]), (b1, model_s[k])]))
-                model_s1 = self.model_fn(x_s1, s1.expand(B))
-            a2, b2, d2 = _f(torch.exp(la_s2 - la_s)), -_f(sig_s2 * phi_12), -(r2f / r1f) * _f(sig_s2 * phi_22)
-            c0, c1, c2 = _f(torch.exp(la_t - la_s)), -_f(sig_t * phi_1), -(1. / r2f) * _f(sig_t * phi_2)
-        x_s2 = self._streams(lambda k: _comb([(a2, x[k]), (b2 - d2, model_s[k]), (d2, model_s1[k])]))
+        if model_s1 is None:
+            x_s1 = self._streams(lambda k: _comb([(a1, x[k]), (b1, model_s[k])]))
+            model_s1 = self.model_fn(x_s1, s1.expand(B))
+        x_s2 = self._streams(lambda k: _comb([(a2, x[k]), (b2, model_s[k]), (d2, model_s1[k])]))
         model_s2 = self.model_fn(x_s2, s2.expand(B))
-        x_t = self._streams(lambda k: _comb([(c0, x[k]), (c1 - c2, model_s[k]), (c2, model_s2[k])]))
+        x_t = self._streams(lambda k: _comb([(c0, x[k]), (c1, model_s[k]), (c2, model_s2[k])]))
         if return_intermediate:
             return x_t, {"model_s": model_s, "model_s1": model_s1, "model_s2": model_s2}
         return x_t
@@ -569,21 +600,11 @@ class DPM_Solver:
                     if step < steps:                      # the final model value is never used
                         model_prev_list[-1] = self.model_fn(x, vec_t)
             elif method in ["singlestep", "singlestep_fixed"]:
-                if method == "singlestep":
-                    orders = self.get_orders_for_singlestep_solver(steps=steps, order=order)
-                    timesteps = self.get_time_steps(skip_type=skip_type, t_T=t_T, t_0=t_0, N=steps, device="cpu")
-                else:
-                    K = steps // order
-                    orders = [order, ] * K
-                    timesteps = self.get_time_steps(skip_type=skip_type, t_T=t_T, t_0=t_0, N=(K * order), device="cpu")
-                ns = self.noise_schedule
-                tc = timesteps.detach().float().cpu()
+                orders, timesteps = self._single_grid(steps, order, skip_type, method, t_T, t_0)
                 i = 0
                 for order in orders:
                     vec_s, vec_t = timesteps[i].expand(B), timesteps[i + order].expand(B)
-                    h = ns.marginal_lambda(tc[i + order]) - ns.marginal_lambda(tc[i])
-                    r1 = None if order <= 1 else (ns.marginal_lambda(tc[i + 1]) - ns.marginal_lambda(tc[i])) / h
-                    r2 = None if order <= 2 else (ns.marginal_lambda(tc[i + 2]) - ns.marginal_lambda(tc[i])) / h
+                    r1, r2 = self._single_ratios(timesteps, i, order)
                     x = self.singlestep_dpm_solver_update(x, vec_s, vec_t, order, solver_type=solver_type, r1=r1, r2=r2)
                     i += order
         if denoise:
@@ -648,23 +669,31 @@ class DPM_Solver:
         conditioning noise come from the counter, and sample k of a seed is the same at any batch and lane count.  known / mask: the
         replacement method of masked_sample_loop (masking.normalize has the shapes): before every evaluation the known cells are set to
         alpha(t) known + sigma(t) eps with eps = that stream's x_T; with paste_known the result carries `known` itself there.  Orders 1
-        and 2 of the fixed-grid multistep method only; batch 1 is accepted."""
-        from . import masking
-        from .sampler import DpmppStepper, unwrap_unet
-        from .seeded import CounterNoise, TAG_AUDIO, TAG_VIDEO, X_T
+        and 2 of the fixed-grid multistep method only (the single-step method: sample_graph_singlestep); batch 1 is accepted."""
+        from .sampler import DpmppStepper
         if method != "multistep":
-            raise H.MMDError(f"sample_graph: only method 'multistep' is recorded; the single-step and adaptive solvers ({method!r}) choose "
-                             "their evaluations on the host - use sample()")
+            raise H.MMDError(f"sample_graph: only method 'multistep' is recorded here, got {method!r}: the single-step solver has "
+                             "sample_graph_singlestep, the adaptive solver chooses its evaluations on the host - use sample()")
+        return self._graph_loop("sample_graph", DpmppStepper, lambda: self._graph_check(steps, order, solver_type),
+                                lambda device: self.graph_tables(steps, order, skip_type, solver_type, denoise, device=device),
+                                x_T, shape, known, mask, noise_source, paste_known, use_graph, lanes)
+
+    def _graph_loop(self, who, stepper_cls, check, tables, x_T, shape, known, mask, noise_source, paste_known, use_graph, lanes):
+        """What the graph-replayed loops share: the argument checks (check() has the method's own), the drawing of x_T, the conditioning,
+        the kept stepper of class stepper_cls with the tables of tables(device), and one stepper.step per table row."""
+        from . import masking, sampler
+        from .sampler import unwrap_unet
+        from .seeded import CounterNoise, TAG_AUDIO, TAG_VIDEO, X_T
         if self.model_kwargs:
-            raise H.MMDError("sample_graph: model_kwargs cannot be recorded into the step graph - use sample()")
-        self._graph_check(steps, order, solver_type)
+            raise H.MMDError(f"{who}: model_kwargs cannot be recorded into the step graph - use sample()")
+        check()
         ctr = noise_source
         if ctr is not None and not isinstance(ctr, CounterNoise):
-            raise H.MMDError("sample_graph: noise_source must be a seeded.CounterNoise or None")
+            raise H.MMDError(f"{who}: noise_source must be a seeded.CounterNoise or None")
         if ctr is not None and x_T is not None:
-            raise H.MMDError("sample_graph: a CounterNoise source draws x_T itself: x_T must be None")
+            raise H.MMDError(f"{who}: a CounterNoise source draws x_T itself: x_T must be None")
         if x_T is None and shape is None:
-            raise H.MMDError("sample_graph: give x_T or shape")
+            raise H.MMDError(f"{who}: give x_T or shape")
         if x_T is not None:
             for k in self.KEYS:
                 H.require_cuda(x_T[k])
@@ -672,15 +701,15 @@ class DPM_Solver:
             shape = {k: tuple(x_T[k].shape) for k in self.KEYS}
         unet = unwrap_unet(self.raw_model)
         if unet is None:
-            raise H.MMDError("sample_graph: the model is no MultimodalUNet (or a wrapper of one)")
+            raise H.MMDError(f"{who}: the model is no MultimodalUNet (or a wrapper of one)")
         if x_T is None:
             device = next(unet.parameters()).device
             if device.type != "cuda":
-                raise H.MMDError("sample_graph runs on the MI355X HIP path only (the model must be on a GPU); no CPU fallback")
+                raise H.MMDError(f"{who} runs on the MI355X HIP path only (the model must be on a GPU); no CPU fallback")
             shape = {k: tuple(int(v) for v in shape[k]) for k in self.KEYS}
-        tabs = self.graph_tables(steps, order, skip_type, solver_type, denoise, device=device)
+        tabs = tables(device)
         if mask is not None and known is None:
-            raise H.MMDError("sample_graph: mask without known")
+            raise H.MMDError(f"{who}: mask without known")
         cond = masking.to_device(masking.normalize(known, mask, shape), device) if known is not None else {}
         if x_T is None:
             if ctr is not None:
@@ -688,12 +717,11 @@ class DPM_Solver:
             else:
                 x_T = {k: torch.randn(*shape[k]).to(device) for k in self.KEYS}
         x_T = {k: x_T[k].float().contiguous() for k in self.KEYS}
-        # the stepper of the last call is kept: another call of the same shape and structure reloads its tables and replays its graphs
-        from . import sampler
+        # the stepper of the last call is kept: another call of the same kind, shape and structure reloads its tables and replays its graphs
         B = shape["video"][0]
-        key = (B, sampler.default_lanes(B) if lanes is None else int(lanes), bool(use_graph), ctr is not None, sampler.DPMPP_SELECT,
-               tuple((k, c.mask is not None) for k, c in sorted(cond.items())), bool(self.predict_x0), bool(self.thresholding),
-               float(self.max_val), str(device), id(unet))
+        key = (stepper_cls.__name__, B, sampler.default_lanes(B) if lanes is None else int(lanes), bool(use_graph), ctr is not None,
+               sampler.DPMPP_SELECT, tuple((k, c.mask is not None) for k, c in sorted(cond.items())), bool(self.predict_x0),
+               bool(self.thresholding), float(self.max_val), str(device), id(unet))
         kept = getattr(self, "_stepper", None)
         self._stepper = None
         with torch.no_grad():
@@ -703,7 +731,7 @@ class DPM_Solver:
             else:
                 if kept is not None:
                     kept[1].close()
-                stepper = DpmppStepper(self, unet, B, device, tabs, use_graph=use_graph, lanes=lanes, cond=cond, ctr=ctr)
+                stepper = stepper_cls(self, unet, B, device, tabs, use_graph=use_graph, lanes=lanes, cond=cond, ctr=ctr)
             try:
                 stepper.load(x_T["video"], x_T["audio"])
                 if cond:
@@ -719,6 +747,84 @@ class DPM_Solver:
                 raise
             self._stepper = (key, stepper)
             return out
+
+    # ------------------------------------------------------------------ graph-replayed single-step loop
+    def _single_check(self, steps, order, method, solver_type):
+        who = "sample_graph_singlestep"
+        if method not in ("singlestep", "singlestep_fixed"):
+            raise H.MMDError(f"{who}: method must be 'singlestep' or 'singlestep_fixed', got {method!r}: the multistep method has sample_graph, "
+                             "the adaptive solver chooses its evaluations on the host - use sample()")
+        if order not in (1, 2, 3):
+            raise H.MMDError(f"{who}: order must be 1, 2 or 3; got {order}")
+        if solver_type not in ("dpm_solver", "taylor"):
+            raise H.MMDError(f"{who}: solver_type must be 'dpm_solver' or 'taylor', got {solver_type!r}")
+        if solver_type == "taylor" and order == 3:
+            raise H.MMDError(f"{who}: third-order 'taylor' update: the reference subtracts stream dicts (dpm:761-764) / reads an undefined "
+                             "name (dpm:873) and raises")
+        steps = int(steps)
+        if steps < 1:
+            raise H.MMDError(f"{who}: steps ({steps}) must be at least 1")
+        if method == "singlestep_fixed" and steps < order:
+            raise H.MMDError(f"{who}: 'singlestep_fixed' takes steps // order steps: steps ({steps}) must be at least the order ({order})")
+        return steps
+
+    def singlestep_tables(self, steps, order=3, skip_type="logSNR", method="singlestep", solver_type="dpm_solver", denoise=False, device="cpu"):
+        """The per-evaluation tables of sample_graph_singlestep, graph_tables' dictionary: one row per network evaluation in the eager
+        loop's order, from the helpers the eager updates call on the same host grid.  A step of order p from timesteps[i] to
+        timesteps[i + p] gives p rows - an open row at s, then stage rows at s1 = inverse_lambda(lam_s + r1 h) and (order 3) s2 - whose
+        c0, c1, c2 are what the eager update hands to mmd_lincomb for the state it evaluates the model on next; with denoise one more
+        row at t_0.  Kinds: ops.DPM1_KIND_*; "timesteps" are the evaluation times."""
+        import numpy as np
+        steps = self._single_check(steps, order, method, solver_type)
+        key = (steps, order, skip_type, method, solver_type, bool(denoise), str(device), bool(self.predict_x0))
+        cache = self.__dict__.setdefault("_single_tables", {})
+        if key not in cache:
+            cache[key] = self._build_single_tables(np, steps, order, skip_type, method, solver_type, denoise, device)
+        return cache[key]
+
+    def _build_single_tables(self, np, steps, order, skip_type, method, solver_type, denoise, device):
+        t_0, t_T = 1. / self.noise_schedule.total_N, self.noise_schedule.T
+        orders, grid = self._single_grid(steps, order, skip_type, method, t_T, t_0)
+        OPEN, STAGE, same = ops.DPM1_KIND_OPEN, ops.DPM1_KIND_STAGE, lambda c: {k: c for k in self.KEYS}      # noqa: E731
+        evals = []          # (time [1], {stream: (c0, c1, c2, kind)})
+        i = 0
+        for p in orders:
+            s, t = grid[i:i + 1], grid[i + p:i + p + 1]
+            r1, r2 = self._single_ratios(grid, i, p)
+            if p == 1:      # per stream: the noise-prediction form moves the audio stream with other coefficients (_first_coefs)
+                evals.append((s, {k: v + (0.0, OPEN) for k, v in self._first_coefs(s, t).items()}))
+            elif p == 2:
+                s1, first, last = self._single_second_coefs(s, t, r1, solver_type)
+                evals += [(s, same(first + (0.0, OPEN))), (s1, same(last + (STAGE,)))]
+            else:
+                s1, s2, first, mid, last = self._single_third_coefs(s, t, r1, r2, solver_type)
+                evals += [(s, same(first + (0.0, OPEN))), (s1, same(mid + (STAGE,))), (s2, same(last + (STAGE,)))]
+            i += p
+        if denoise:
+            evals.append((torch.ones((1,)) * t_0, same((0.0, 0.0, 0.0, ops.DPM1_KIND_DENOISE))))
+        rows = len(evals)
+        tab = {k: np.zeros((ops.DPMPP_TAB_ROWS, rows), dtype=np.float32) for k in self.KEYS}
+        tab2 = np.zeros((2, rows), dtype=np.float32)
+        for j, (tau, c) in enumerate(evals):
+            tab2[:, j] = self._alpha_sigma(tau)
+            cx, ce = self._x0_coefs(tau) if (self.predict_x0 or c[self.KEYS[0]][3] == ops.DPM1_KIND_DENOISE) else (0.0, 0.0)
+            for k in self.KEYS:
+                tab[k][:, j] = (cx, ce) + tuple(c[k])
+        times = torch.cat([tau.reshape(-1)[:1] for tau, _ in evals])
+        tm = self.model.get_model_input_time(times.to(device))
+        return {"rows": rows, "timesteps": times, "tab": tab, "tab2": tab2, "tm": [int(v) for v in tm.cpu()]}
+
+    def sample_graph_singlestep(self, x_T=None, *, shape=None, steps, order=3, skip_type="logSNR", method="singlestep", solver_type="dpm_solver",
+                                denoise=False, known=None, mask=None, noise_source=None, paste_known=True, use_graph=True, lanes=None):
+        """sample(method="singlestep" / "singlestep_fixed") of orders 1-3 as one graph replay per lane and network evaluation
+        (sampler.DpmSingleStepper, the tables of singlestep_tables): the same x_T and window-shift stream - one draw per evaluation, in
+        the eager order - give the same bits.  x_T / shape, noise_source, known / mask / paste_known, use_graph and lanes as in
+        sample_graph; the known cells are set before EVERY evaluation, the stage evaluations at s1 and s2 included, to
+        alpha(tau) known + sigma(tau) eps at that evaluation's time tau.  Batch 1 is accepted."""
+        from .sampler import DpmSingleStepper
+        return self._graph_loop("sample_graph_singlestep", DpmSingleStepper, lambda: self._single_check(steps, order, method, solver_type),
+                                lambda device: self.singlestep_tables(steps, order, skip_type, method, solver_type, denoise, device=device),
+                                x_T, shape, known, mask, noise_source, paste_known, use_graph, lanes)
 
 
 def expand_dims(v, dims):

@@ -1260,6 +1260,27 @@ def dpmpp_update(x, m0, M1, tab, k, F, C, Cm, HW, s=None, max_val=1.0):
     return x
 
 
+DPM1_KIND_OPEN, DPM1_KIND_STAGE, DPM1_KIND_DENOISE = 0, 1, 2      # row kinds of mmd_dpm_single_update (include/mmd.h)
+
+
+def dpm_single_update(x, src, XB, MS, tab, k, F, C, Cm, HW, form=0, s=None, max_val=1.0):
+    """One evaluation of the single-step solver, in place, by the row's kind (include/mmd.h): open XB = x, MS = m0, x = c0[k] x + c1[k] m0;
+    stage x = c0[k] XB + c1[k] MS + c2[k] m0; denoise x = m0.  form 0: m0 = the first C of src's Cm channels [N,F,Cm,HW], clamp-scaled by
+    s [N] when s is given; form 1: m0 = cx[k] x + ce[k] eps with eps = those channels (no s)."""
+    H.require_cuda(x, src, XB, MS, tab, k, s)
+    N = x.shape[0]
+    _dpmpp_args("dpm_single_update", tab, k, N, (("x", x), ("src", src), ("XB", XB), ("MS", MS), ("s", s)))
+    if form not in (0, 1) or (s is not None and form != 0):
+        raise H.MMDError("dpm_single_update: form is 0 or 1, and s goes with form 0 only")
+    if x.numel() != N * F * C * HW or XB.numel() != x.numel() or MS.numel() != x.numel() or src.numel() != N * F * Cm * HW or \
+            (s is not None and s.numel() != N):
+        raise H.MMDError(f"dpm_single_update: x / XB / MS must hold N F C HW = {N * F * C * HW}, src N F Cm HW = {N * F * Cm * HW} elements and s "
+                         "one per sample")
+    _dispatch("mmd_dpm_single_update", x.data_ptr(), src.data_ptr(), int(form), XB.data_ptr(), MS.data_ptr(), H.ptr(s), float(max_val),
+              tab.data_ptr(), k.data_ptr(), tab.shape[1], N, F, C, Cm, HW, meta=("dpm_single_update", 0, 24 * x.numel()))
+    return x
+
+
 def dpm_err(hi, lo, prev, atol, rtol, out):
     """out[n] (fp64, pre-zeroed) += squared scaled difference of two solver orders (adaptive step-size control)."""
     H.require_cuda(hi, lo, prev, out)

@@ -10,7 +10,8 @@ the timestep_map tensor rebuild, ~16 table uploads and ~55k ATen dispatches.
 Structure: LaneStepper owns what every replayed step shares - the batch lanes and their engines, the conditioning buffers and the
 pre-plan that replaces the known cells, the per-step uploads, the lane events, and capture / launch / close over NAMED PLAN SETS
 (name -> per-lane plans behind the U-Net plan, and their per-lane graph execs once captured).  GraphStepper (DDPM / DDIM / variational
-bound) and DpmppStepper (DPM-Solver++) record their update plans into sets and say, in set_step, which set the next launch replays."""
+bound) and SolverStepper (DPM-Solver / DPM-Solver++: DpmppStepper multistep, DpmSingleStepper single-step) record their update plans into
+sets and say, in set_step, which set the next launch replays."""
 import ctypes
 import os
 
@@ -399,18 +400,22 @@ class GraphStepper(LaneStepper):
 DPMPP_SELECT = "multi"
 
 
-class DpmppStepper(LaneStepper):
-    """One evaluation of the fixed-grid multistep DPM-Solver / DPM-Solver++ loop (multimodal_dpm_solver_plus.DPM_Solver.sample_graph)
-    as one graph replay per lane: [mmd_cond_replace of each conditioned stream] + U-Net plan + per stream on its own stream
-    [mmd_dpmpp_x0 (+ the quantile selection) + mmd_dpmpp_update] + join.  Every coefficient sits in the device tables of
-    DPM_Solver.graph_tables, indexed by the step number in t_idx, so the graph of one step serves them all.  The noise-prediction solver
-    updates from the model output directly; its closing denoise evaluation is a data prediction and has a second plan set ("final"),
-    which set_step selects at the denoise row.  Lanes, conditioning buffers, capture and launch are LaneStepper's.
+class SolverStepper(LaneStepper):
+    """One evaluation of a fixed-grid DPM-Solver / DPM-Solver++ loop as one graph replay per lane: [mmd_cond_replace of each conditioned
+    stream] + U-Net plan + per stream on its own stream [the model value m0 + the solver's update] + join.  Every coefficient sits in
+    device tables (fp32 [6, rows] per stream, include/mmd.h), indexed by the evaluation number in t_idx, so the graph of one evaluation
+    serves them all.  The noise-prediction solver updates from the model output directly; its closing denoise evaluation is a data
+    prediction and has a second plan set ("final"), which set_step selects at the denoise row.  Lanes, conditioning buffers, capture and
+    launch are LaneStepper's.  A subclass names the solver's update: its history buffers (_history) and the launch that consumes m0
+    (_update); with FUSED_X0 that launch forms an unthresholded data prediction itself and mmd_dpmpp_x0 is recorded only where the
+    quantile selection has to read x0raw.
 
     The tables have a fixed capacity (ROWS_CAP rows, the stride the recorded launches carry), so a stepper outlives one sampling call:
     retable() loads another time grid, order or seed into the same buffers and the captured graphs are replayed as they are
-    (DPM_Solver.sample_graph keeps its last stepper; a capture costs about as much as five evaluations of a 50-evaluation call)."""
+    (DPM_Solver keeps its last stepper; a capture costs about as much as five evaluations of a 50-evaluation call)."""
     ROWS_CAP = 1024
+    FUSED_X0 = False
+    WHO = "sample_graph"
 
     def __init__(self, solver, unet, batch, device, tabs, use_graph=True, lanes=None, cond=None, ctr=None, select=None):
         select = DPMPP_SELECT if select is None else select
@@ -434,8 +439,8 @@ class DpmppStepper(LaneStepper):
             t_idx = self.t_idx[self._lane(r)]
             streams = []
             for sid, k, xk, ok in ((0, "video", e.x_video, e.out_video), (1, "audio", e.x_audio, e.out_audio)):
-                buf = {"m1": th.zeros_like(xk), "x0": th.empty_like(xk), "s": th.zeros(n, dtype=th.float32, device=self.device),
-                       "ws": ops.dpmpp_workspace(n, self.device)}
+                buf = dict(self._history(xk), x0=th.empty_like(xk), s=th.zeros(n, dtype=th.float32, device=self.device),
+                           ws=ops.dpmpp_workspace(n, self.device))
                 self._bufs.append(buf)
                 streams.append((sid, k, xk, ok, buf))
 
@@ -445,17 +450,16 @@ class DpmppStepper(LaneStepper):
                     for sid, k, xk, ok, b in streams:
                         Fk, C, Cm, HWk = geom[k]
                         with ops.on_stream(sid):
-                            if data_form:
+                            if data_form and (thresholding or not self.FUSED_X0):
                                 multi = thresholding and select == "multi"
                                 ops.dpmpp_x0(xk, ok, b["x0"], self.tab[k], t_idx, Fk, C, Cm, HWk, hist=b["ws"] if multi else None)
                                 if multi:
                                     ops.dpmpp_select(b["x0"], 0.995, b["s"], b["ws"], level0_done=True)      # p of the Imagen paper
                                 elif thresholding:
                                     ops.abs_quantile(b["x0"], 0.995, out=b["s"])
-                                ops.dpmpp_update(xk, b["x0"], b["m1"], self.tab[k], t_idx, Fk, C, C, HWk, s=b["s"] if thresholding else None,
-                                                 max_val=max_val)
+                                self._update(xk, b["x0"], False, b, self.tab[k], t_idx, Fk, C, C, HWk, b["s"] if thresholding else None, max_val)
                             else:
-                                ops.dpmpp_update(xk, ok, b["m1"], self.tab[k], t_idx, Fk, C, Cm, HWk)
+                                self._update(xk, ok, data_form, b, self.tab[k], t_idx, Fk, C, Cm, HWk, None, max_val)
                     ops.record_sync(1, 0)
                 return plan
             self.update_plans.append(record(predict_x0))
@@ -463,10 +467,20 @@ class DpmppStepper(LaneStepper):
                 self.final_plans.append(record(True))
         self.update_plan = self.update_plans[0]
 
+    def _history(self, xk):
+        """{name: buffer}: what the update keeps of one stream between evaluations."""
+        raise NotImplementedError
+
+    def _update(self, x, src, x0_form, b, tab, t_idx, F, C, Cm, HW, s, max_val):
+        """Record the update of one stream from m0 = the first C of src's Cm channels, clamp-scaled by s if given; x0_form (FUSED_X0
+        only): src is the model output and m0 its data prediction."""
+        raise NotImplementedError
+
     def retable(self, tabs, ctr=None):
-        """Load the tables of DPM_Solver.graph_tables (and the key and sample ids of `ctr`) into the buffers the recorded plans read."""
+        """Load the tables of DPM_Solver.graph_tables / singlestep_tables (and the key and sample ids of `ctr`) into the buffers the
+        recorded plans read."""
         if tabs["rows"] > self.ROWS_CAP:
-            raise H.MMDError(f"sample_graph: {tabs['rows']} evaluations exceed the table capacity of {self.ROWS_CAP} rows")
+            raise H.MMDError(f"{self.WHO}: {tabs['rows']} evaluations exceed the table capacity of {self.ROWS_CAP} rows")
         if (ctr is None) != (self.ctr is None):
             raise H.MMDError("the noise source's kind is fixed when the stepper is built")
         self.rows, self.tm = tabs["rows"], tabs["tm"]
@@ -492,5 +506,35 @@ class DpmppStepper(LaneStepper):
         i = int(i)
         if not 0 <= i < self.rows:
             raise H.MMDError(f"step {i} is outside the {self.rows} rows of the tables")
-        self._set = "final" if self.has_final and self.kinds[i] == ops.DPMPP_KIND_DENOISE else "step"
+        self._set = "final" if self.has_final and self.kinds[i] == ops.DPMPP_KIND_DENOISE else "step"      # = DPM1_KIND_DENOISE
         self._push_step(i, int(self.tm[i]), shifts)
+
+
+class DpmppStepper(SolverStepper):
+    """The fixed-grid multistep loop (multimodal_dpm_solver_plus.DPM_Solver.sample_graph): per stream [mmd_dpmpp_x0 (+ the quantile
+    selection) + mmd_dpmpp_update], with the previous evaluation's model value m1 as the history."""
+
+    def _history(self, xk):
+        return {"m1": th.zeros_like(xk)}
+
+    def _update(self, x, src, x0_form, b, tab, t_idx, F, C, Cm, HW, s, max_val):
+        ops.dpmpp_update(x, src, b["m1"], tab, t_idx, F, C, Cm, HW, s=s, max_val=max_val)
+
+
+class DpmSingleStepper(SolverStepper):
+    """The single-step loop of orders 1-3 (DPM_Solver.sample_graph_singlestep): one row per network evaluation, open / stage / denoise
+    (ops.DPM1_KIND_*), per stream ONE launch of mmd_dpm_single_update - the data prediction is formed inside it - or, with thresholding,
+    mmd_dpmpp_x0 + the quantile selection + that launch.  History: XB, the state at the step's start, and MS, the model value there.
+
+    The first launch of a plan set is its capture's warm-up run, which writes XB and MS (LaneStepper.launch keeps only x around it).
+    That is harmless: row 0 is always an open row, which the replay that follows rewrites from the restored x with the same values
+    before any stage row reads them, and the denoise row of the "final" set writes neither."""
+    FUSED_X0 = True
+    WHO = "sample_graph_singlestep"
+
+    def _history(self, xk):
+        return {"xb": th.zeros_like(xk), "ms": th.zeros_like(xk)}
+
+    def _update(self, x, src, x0_form, b, tab, t_idx, F, C, Cm, HW, s, max_val):
+        ops.dpm_single_update(x, src, b["xb"], b["ms"], tab, t_idx, F, C, Cm, HW, form=1 if x0_form else 0, s=s, max_val=max_val)
+
