@@ -399,7 +399,9 @@ int mmd_ddim_update(const float* x, const float* model_out, const float* noise, 
  * depend on its batch position, the batch size, the lane or the rank.  Philox4x32-10 (Salmon et al., SC'11; multipliers 0xD2511F53 /
  * 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85), key = the 64-bit seed, low word first (key: device, 2 words), counter
  *   c0 = r >> 2   r = the element's index inside its sample in API layout ([F,C,H,W] video, [C,L] audio, [C,H,W] SR image)
- *   c1 = draw     the loop index t[n] the update kernels read (SpacedDiffusion: the respaced index); 0xFFFFFFFF = x_T
+ *   c1 = draw     the loop index t[n] the update kernels read (SpacedDiffusion: the respaced index); 0xFFFFFFFF = x_T; the resampled
+ *                 masked loop hands its draws in (mmd_ddpm_update_ctr_at, mmd_renoise_ctr): i + r T for visit r of step i, 0x80000000 + k
+ *                 for the k-th forward jump
  *   c2 = sample id  ids[n] (device int64 [N]); the low 32 bits are used and the HOST refuses ids outside [0, 2^32) (mm_diffusion/seeded.py:
  *                 the library cannot look into device memory without a sync)
  *   c3 = tag      0 video, 1 audio, 2 SR image, 3 window shifts (host only)
@@ -420,6 +422,22 @@ int mmd_ddpm_update_ctr(const float* x, const float* model_out, const uint32_t* 
 int mmd_ddim_update_ctr(const float* x, const float* model_out, const uint32_t* key, const int64_t* ids, int tag, float* out, float* x0_out,
                         const float* tables, const float* tab3, const int64_t* t, int T, int N, int F, int C, int HW, int flags, float eta,
                         void* stream);
+/* mmd_ddpm_update_ctr with counter word c1 = the low 32 bits of draw[n] (device int64 [N]) instead of t[n]: a loop that runs a timestep
+ * more than once (the resampling jumps of masked sampling) gives every visit noise of its own.  Bitwise the memory form fed with
+ * mmd_ctr_fill(draw); with draw == t bitwise mmd_ddpm_update_ctr.  Draw convention of the resampled loop (mm_diffusion/masking.py,
+ * repaint_schedule): visit r = 0, 1, ... of step i of T draws i + r T (below 2^31, so the first visit draws what the plain loop draws),
+ * the k-th forward jump draws 0x80000000 + k, and 0xFFFFFFFF stays x_T. */
+int mmd_ddpm_update_ctr_at(const float* x, const float* model_out, const uint32_t* key, const int64_t* ids, int tag, float* out, float* x0_out,
+                           float* mean_out, float* logvar_out, const float* tables, const int64_t* t, const int64_t* draw, int T, int N,
+                           int F, int C, int HW, int flags, void* stream);
+/* The forward jump of resampled masked sampling (RePaint, Lugmayr et al., CVPR 2022), in place on x fp32 [N, F, C, HW]: x = a x + b z
+ * with a = jtab[m[n]], b = jtab[T + m[n]] and z = the counter normal of (element, draw[n], ids[n], tag).  jtab fp32 [2, T]: a[m] =
+ * sqrt(ac[m + J] / ac[m]), b[m] = sqrt(1 - ac[m + J] / ac[m]) for a jump of J levels (the host computes them in float64; entries with
+ * m + J > T - 1 are zero and never used).  The element is mmd_q_sample's, so the result is bitwise mmd_ctr_fill(draw) followed by
+ * mmd_q_sample(x, eps, x, jtab, m) - which is also the memory form of the jump.  One quad per thread; an m[n] outside [0, T) writes
+ * nothing. */
+int mmd_renoise_ctr(float* x, const uint32_t* key, const int64_t* ids, int tag, const float* jtab, const int64_t* m, const int64_t* draw,
+                    int T, int N, int F, int C, int HW, void* stream);
 /* Masked conditioning of the replacement method (gd:642-720 overwrites a whole stream with q_sample(condition, t, noise = that stream's
  * x_T) before every step; here any part of it): in place, x = A known + B eps where the mask cell is set; elsewhere x is NOT written.
  * x / known / noise fp32 [N, F, C, HW] (audio: F = 1, HW = L).  mask uint8, one cell per (frame, position) shared by the channels: element

@@ -60,6 +60,8 @@ __device__ __forceinline__ R post_mean(const PostCoef<R>& q, R x0, R xv) { retur
 // N(0,1) values that are a pure function of (seed, sample id, draw, stream tag, element): Philox4x32-10 (Salmon et al., SC'11) keyed
 // with the 64-bit seed (low word first) on the counter
 //   c0 = r >> 2   r = the element's index inside its sample in API layout     c1 = draw (the loop index t[n]; 0xFFFFFFFF = x_T)
+//                 resampled loops (mmd_ddpm_update_ctr_at, mmd_renoise_ctr) hand the draw in: visit r of step i of T draws i + r T (< 2^31),
+//                 the k-th forward jump 0x80000000 + k
 //   c2 = sample id (low 32 bits of ids[n]; the host refuses ids outside [0, 2^32))   c3 = tag (0 video, 1 audio, 2 SR image, 3 shifts)
 // The four output words belong to elements 4 c0 ... 4 c0 + 3; words past the end of a sample are dropped.  Nothing in the counter
 // depends on the batch position, the batch size, the lane or the rank.  Word w -> u = ((w >> 9) + 0.5) 2^-23, exact in fp32 and inside
@@ -113,6 +115,15 @@ struct NoiseFromCounter {
   CtrKey k;
   __device__ __forceinline__ bool present() const { return true; }
   __device__ __forceinline__ void draw(int64_t n, int64_t r0, int64_t, int ti, float* z) const { ctr_normals(k, n, r0, (uint32_t)ti, z); }
+};
+// The counter source with the draw handed in per sample (c1 = the low 32 bits of at[n]) instead of taken from the timestep: a loop that
+// visits a timestep more than once (resampling jumps) gives every visit its own draw.
+struct NoiseFromCounterAt {
+  static constexpr int W = 4;
+  CtrKey k;
+  const int64_t* at;
+  __device__ __forceinline__ bool present() const { return true; }
+  __device__ __forceinline__ void draw(int64_t n, int64_t r0, int64_t, int, float* z) const { ctr_normals(k, n, r0, (uint32_t)at[n], z); }
 };
 
 // kind 0: fp32 normals, kind 1: the raw words; out [N, per]
@@ -203,6 +214,18 @@ extern "C" int mmd_ddpm_update_ctr(const float* x, const float* model_out, const
   const DiffusionParams p{x, model_out, tables, t, T, N, F, C, HW, flags};
   return mmd_launch<ddpm_update_kernel<NoiseFromCounter>>("ddpm_update_ctr", dim3(ew_grid((per + 3) / 4 * N)), dim3(256), 0, (hipStream_t)stream, p,
                                                           NoiseFromCounter{{key, ids, tag}}, out, x0_out, mean_out, logvar_out);
+}
+extern "C" int mmd_ddpm_update_ctr_at(const float* x, const float* model_out, const uint32_t* key, const int64_t* ids, int tag, float* out,
+                                      float* x0_out, float* mean_out, float* logvar_out, const float* tables, const int64_t* t,
+                                      const int64_t* draw, int T, int N, int F, int C, int HW, int flags, void* stream) {
+  MMD_REQUIRE(x && model_out && tables && t && T > 0 && N > 0 && F > 0 && C > 0 && HW > 0, "ddpm_update_ctr_at: bad argument");
+  MMD_REQUIRE(ctr_args_ok(key, ids, tag), "ddpm_update_ctr_at: needs the key, the sample ids and a stream tag in [0, 3]");
+  MMD_REQUIRE(draw, "ddpm_update_ctr_at: needs one draw per sample");
+  const int64_t per = (int64_t)F * C * HW;
+  MMD_REQUIRE(per <= MMD_CTR_MAX_PER, "ddpm_update_ctr_at: sample too large");
+  const DiffusionParams p{x, model_out, tables, t, T, N, F, C, HW, flags};
+  return mmd_launch<ddpm_update_kernel<NoiseFromCounterAt>>("ddpm_update_ctr_at", dim3(ew_grid((per + 3) / 4 * N)), dim3(256), 0, (hipStream_t)stream,
+                                                            p, NoiseFromCounterAt{{key, ids, tag}, draw}, out, x0_out, mean_out, logvar_out);
 }
 
 // Backward of the sampling update through the posterior mean (gradient-guided conditional sampling, gd:722-817):
@@ -393,6 +416,39 @@ extern "C" int mmd_cond_replace_ctr(float* x, const float* known, const uint32_t
   const CondReplaceParams p{x, known, mask, mask_stride, tab2, t, ca, cb, T, N, F, C, HW};
   return mmd_launch<cond_replace_kernel<NoiseFromCounter>>("cond_replace_ctr", dim3(ew_grid((per + 3) / 4 * N)), dim3(256), 0, (hipStream_t)stream, p,
                                                            NoiseFromCounter{{key, ids, tag}});
+}
+
+// The forward jump of resampled masked sampling (RePaint, Lugmayr et al., CVPR 2022): the state at level m goes back up to level m + J,
+//   x = a[m] x + b[m] z in place,   a[m] = sqrt(ac[m + J] / ac[m]),  b[m] = sqrt(1 - ac[m + J] / ac[m])      jtab = [2][T] fp32: a, b
+// with q_sample's element, so the result is bitwise mmd_ctr_fill(draw) followed by mmd_q_sample(x, eps, x, jtab, m).  z = the counter
+// normal of (element, draw[n], ids[n], tag).  One quad per thread; an m[n] outside [0, T) writes nothing.
+__global__ __launch_bounds__(256) void renoise_ctr_kernel(float* x, const CtrKey k, const float* __restrict__ jtab, const int64_t* __restrict__ m,
+                                                          const int64_t* __restrict__ draw, int T, int64_t per, int N) {
+  const int64_t ups = (per + 3) / 4, total = ups * N;
+  for (int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x; u < total; u += (int64_t)gridDim.x * 256) {
+    const int64_t n = u / ups, r0 = (u % ups) * 4;
+    const int64_t mi = m[n];
+    if (mi < 0 || mi >= T) continue;
+    const float a = jtab[mi], b = jtab[T + mi];
+    float z[4];
+    ctr_normals(k, n, r0, (uint32_t)draw[n], z);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int64_t r = r0 + j, i = n * per + r;
+      if (r >= per) break;
+      x[i] = q_sample_elem(a, x[i], b, z[j]);
+    }
+  }
+}
+extern "C" int mmd_renoise_ctr(float* x, const uint32_t* key, const int64_t* ids, int tag, const float* jtab, const int64_t* m,
+                               const int64_t* draw, int T, int N, int F, int C, int HW, void* stream) {
+  MMD_REQUIRE(x && jtab && m && draw, "renoise_ctr: needs x, the jump table, the levels and the draws");
+  MMD_REQUIRE(T > 0 && N > 0 && F > 0 && C > 0 && HW > 0, "renoise_ctr: T, N, F, C, HW must be positive");
+  MMD_REQUIRE(ctr_args_ok(key, ids, tag), "renoise_ctr: needs the key, the sample ids and a stream tag in [0, 3]");
+  const int64_t per = (int64_t)F * C * HW;
+  MMD_REQUIRE(per <= MMD_CTR_MAX_PER, "renoise_ctr: sample too large");
+  return mmd_launch<renoise_ctr_kernel>("renoise_ctr", dim3(ew_grid((per + 3) / 4 * N)), dim3(256), 0, (hipStream_t)stream, x, CtrKey{key, ids, tag}, jtab,
+                                        m, draw, T, per, N);
 }
 
 // out[n, i] = (ca[t_n] a + cb[t_n] b) * cs[t_n]    per-sample coefficients looked up from fp32 tables of length T

@@ -115,6 +115,8 @@ _PROTOS = {
     "mmd_ddim_update_ctr": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp]),
     "mmd_cond_replace": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, f32, i32, i32, i32, i32, i32, vp]),
     "mmd_cond_replace_ctr": (i32, [vp, vp, vp, vp, i32, vp, i64, vp, vp, f32, f32, i32, i32, i32, i32, i32, vp]),
+    "mmd_ddpm_update_ctr_at": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "mmd_renoise_ctr": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "mmd_dpmpp_workspace_bytes": (i64, [i32]),
     "mmd_dpmpp_x0": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]),
     "mmd_dpmpp_select": (i32, [vp, vp, i32, i32, i64, f32, vp, vp]),

@@ -2,7 +2,8 @@
 
 A mask has one cell per (frame, position) of a stream, shared by the channels: video [F, H, W] or [B, F, H, W], audio [L] or [B, L],
 bool or uint8, non-zero = known.  A stream of `known` without a mask is known as a whole.  normalize() turns what the caller hands in
-into what mmd_cond_replace reads (include/mmd.h): contiguous fp32 values, contiguous uint8 cells and the batch stride of the cells."""
+into what mmd_cond_replace reads (include/mmd.h): contiguous fp32 values, contiguous uint8 cells and the batch stride of the cells.
+repaint_schedule() / jump_table() are the evaluation order and the coefficients of the loop's resampling jumps (jump_length, n_resample)."""
 from collections import namedtuple
 
 import torch as th
@@ -76,6 +77,63 @@ def to_device(cond, device):
     if th.device(device).type == "cuda":
         H.require_cuda(*(c.known for c in cond.values()))
     return {k: c._replace(known=c.known.to(device), mask=None if c.mask is None else c.mask.to(device)) for k, c in cond.items()}
+
+
+JUMP_DRAW = 0x80000000                # the draw of the schedule's first forward jump; the k-th draws JUMP_DRAW + k
+
+
+def repaint_schedule(T, jump_length=None, n_resample=1):
+    """The evaluation order of masked sampling with resampling jumps (RePaint, Lugmayr et al., CVPR 2022) over T reverse steps: a list of
+    ("step", i, draw) - reverse step i, whose input is the state at level i (marginal alphas_cumprod[i]) - and ("jump", m, draw) - the
+    state at level m diffused forward to level m + jump_length.  The jump levels are the multiples m of jump_length with
+    m + jump_length <= T - 1; each is jumped from n_resample - 1 times, the first time it is reached from above with jumps left.  So the
+    jump_length steps above a jump level run n_resample times: T + (n_resample - 1) jump_length |levels| evaluations.
+
+    The draws are the counter word of seeded.CounterNoise: execution r = 0, 1, ... of step i draws i + r T, so a first visit draws what the
+    plain loop draws, and the k-th jump draws 0x80000000 + k.  jump_length=None or n_resample=1: the plain T - 1 ... 0."""
+    T, U = int(T), int(n_resample)
+    if T < 1:
+        raise H.MMDError(f"repaint_schedule: T must be at least 1, got T={T}")
+    if U < 1:
+        raise H.MMDError(f"repaint_schedule: n_resample must be at least 1, got n_resample={U}")
+    if U * T >= 1 << 31:
+        raise H.MMDError(f"repaint_schedule: n_resample * T must stay below 2^31 (the draws of the steps), got n_resample={U} with T={T}")
+    if jump_length is None:
+        J, left = None, {}
+    else:
+        J = int(jump_length)
+        if J < 1:
+            raise H.MMDError(f"repaint_schedule: jump_length must be at least 1, got jump_length={J}")
+        if U > 1 and J > T - 1:
+            raise H.MMDError(f"repaint_schedule: jump_length={J} exceeds T - 1 = {T - 1}: no level to jump from")
+        left = {m: U - 1 for m in range(0, T - J, J)}
+    out, visits, level = [], [0] * T, T - 1
+    jumps = 0
+    while level >= 0:
+        out.append(("step", level, level + visits[level] * T))
+        visits[level] += 1
+        level -= 1
+        if left.get(level, 0) > 0:
+            left[level] -= 1
+            out.append(("jump", level, JUMP_DRAW + jumps))
+            jumps += 1
+            level += J
+    return out
+
+
+def jump_table(alphas_cumprod, jump_length):
+    """float64 [2, T]: row 0 a[m] = sqrt(ac[m + J] / ac[m]), row 1 b[m] = sqrt(1 - ac[m + J] / ac[m]), the coefficients that take the state
+    at level m to level m + J (x = a x + b z: q(x_{m+J} | x_m)); entries with m + J > T - 1 are zero (never used)."""
+    import numpy as np
+    ac = np.asarray(alphas_cumprod, dtype=np.float64)
+    T, J = ac.shape[0], int(jump_length)
+    if not 1 <= J <= max(T - 1, 1):
+        raise H.MMDError(f"jump_table: jump_length must be in [1, {T - 1}], got jump_length={J}")
+    tab = np.zeros((2, T), dtype=np.float64)
+    ratio = ac[J:] / ac[:T - J]
+    tab[0, :T - J] = np.sqrt(ratio)
+    tab[1, :T - J] = np.sqrt(1.0 - ratio)
+    return tab
 
 
 def prefix_masks(video_size, audio_size, frames):

@@ -150,6 +150,15 @@ class GaussianDiffusion:
             self._dev_tables[key] = th.from_numpy(tab).float().to(device).contiguous()
         return self._dev_tables[key]
 
+    def jump_tables(self, jump_length, device):
+        """[2, T] fp32 table of the forward jump over `jump_length` levels (masking.jump_table, computed in float64) for mmd_renoise_ctr
+        and, as its memory form, mmd_q_sample."""
+        from . import masking
+        key = ("jump", int(jump_length), str(device))
+        if key not in self._dev_tables:
+            self._dev_tables[key] = th.from_numpy(masking.jump_table(self.alphas_cumprod, jump_length)).float().to(device).contiguous()
+        return self._dev_tables[key]
+
     def _tab(self, arr, name, device):
         """fp32 device copy of one fp64 coefficient table (cached by name) for mmd_lincomb_t."""
         key = (name, str(device))
@@ -266,8 +275,13 @@ class GaussianDiffusion:
         outs = dict(x0_out=res.get("pred_xstart"), mean_out=res.get("mean"), logvar_out=res.get("log_variance"))
         from .seeded import CounterNoise
         if isinstance(noise, CounterNoise):      # drawn in the kernel: counter (element, t, sample id, stream)
-            ops.ddpm_update_ctr(xs, mo, noise.key(xs.device), noise.ids(xs.shape[0], xs.device), 0 if key == "video" else 1, res.get("sample"), tab,
-                                t.to(th.int64).contiguous(), F, C, HW, flags, **outs)
+            src = (xs, mo, noise.key(xs.device), noise.ids(xs.shape[0], xs.device), 0 if key == "video" else 1, res.get("sample"), tab,
+                   t.to(th.int64).contiguous())
+            draws = noise.draws(xs.shape[0], xs.device)
+            if draws is None:
+                ops.ddpm_update_ctr(*src, F, C, HW, flags, **outs)
+            else:                                # CounterNoise.drawing_at: the loop names the draw (resampling jumps)
+                ops.ddpm_update_ctr_at(*src, draws, F, C, HW, flags, **outs)
         else:
             ops.ddpm_update(xs, mo, noise, res.get("sample"), tab, t.to(th.int64).contiguous(), F, C, HW, flags, **outs)
         return res
@@ -404,14 +418,14 @@ class GaussianDiffusion:
         return indices
 
     def _graph_stepper(self, model, model_kwargs, use_graph, batch, device, clip_denoised, denoised_fn=None, update="ddpm", eta=0.0,
-                       lanes=None, cond=None):
+                       lanes=None, cond=None, jump_length=None):
         """The sampler.GraphStepper of a call whose steps can be graph-replayed - a MultimodalUNet behind `model`, no model_kwargs, no host
         callable on the x_0 prediction - else None: the caller then launches its steps eagerly."""
         from .sampler import GraphStepper, unwrap_unet
         unet = unwrap_unet(model)
         if not use_graph or unet is None or model_kwargs or denoised_fn is not None:
             return None
-        return GraphStepper(self, unet, batch, device, clip_denoised, update=update, eta=eta, lanes=lanes, cond=cond)
+        return GraphStepper(self, unet, batch, device, clip_denoised, update=update, eta=eta, lanes=lanes, cond=cond, jump_length=jump_length)
 
     @staticmethod
     def _replay(stepper, indices, before=None, after=None, state=True):
@@ -520,17 +534,20 @@ class GaussianDiffusion:
 
     # ------------------------------------------------------------------ masked conditional sampling
     def masked_sample_loop(self, model, shape, known, mask=None, *, sampler="ddpm", eta=0.0, noise=None, clip_denoised=True,
-                           model_kwargs=None, device=None, progress=False, paste_known=True, use_graph=True, lanes=None):
+                           model_kwargs=None, device=None, progress=False, paste_known=True, use_graph=True, lanes=None,
+                           jump_length=None, n_resample=1):
         """The last state of masked_sample_loop_progressive."""
         final = None
         for sample in self.masked_sample_loop_progressive(model, shape, known, mask, sampler=sampler, eta=eta, noise=noise,
                                                           clip_denoised=clip_denoised, model_kwargs=model_kwargs, device=device,
-                                                          progress=progress, paste_known=paste_known, use_graph=use_graph, lanes=lanes):
+                                                          progress=progress, paste_known=paste_known, use_graph=use_graph, lanes=lanes,
+                                                          jump_length=jump_length, n_resample=n_resample):
             final = sample
         return final
 
     def masked_sample_loop_progressive(self, model, shape, known, mask=None, *, sampler="ddpm", eta=0.0, noise=None, clip_denoised=True,
-                                       model_kwargs=None, device=None, progress=False, paste_known=True, use_graph=True, lanes=None):
+                                       model_kwargs=None, device=None, progress=False, paste_known=True, use_graph=True, lanes=None,
+                                       jump_length=None, n_resample=1):
         """The replacement method (gd:642-720) with partial masks, for the DDPM and the DDIM stepper.  known: {"video": [B,F,C,H,W],
         "audio": [B,C,L]}, either or both; mask: the known cells of these streams (masking.normalize has the shapes; a stream without a
         mask is known as a whole).  Before every step the known cells are set to q_sample(known, t, noise = that stream's x_T) by one
@@ -538,10 +555,22 @@ class GaussianDiffusion:
         ddim_sample ("ddim", eta) follows, the reference's order.  With paste_known the LAST yielded state carries `known` itself on
         its known cells; the states before it are the raw step outputs.  noise: an optional x_T dict that doubles as the fixed
         conditioning noise; with a seeded.CounterNoise source x_T, the conditioning noise (regenerated in the kernel, no buffer) and the
-        per-step noise all come from the counter and `noise` must be None."""
+        per-step noise all come from the counter and `noise` must be None.
+
+        jump_length, n_resample (sampler="ddpm"): RePaint's resampling (Lugmayr et al., CVPR 2022).  The loop runs
+        masking.repaint_schedule(T, jump_length, n_resample): whenever the state reaches a multiple m of jump_length with jumps left it is
+        diffused forward again to level m + jump_length (one mmd_renoise_ctr per stream, or mmd_q_sample on fresh noise: video first,
+        then audio) and those steps run again, n_resample times in all, so that the unknown cells are harmonised with the known ones.
+        Every reverse step yields a state, a jump yields none, and the paste follows the last evaluation.  A repeated step draws noise
+        and window shifts of its own (the schedule's draws).  The default, n_resample=1, is the plain loop."""
         from . import masking
         if sampler not in ("ddpm", "ddim"):
             raise H.MMDError(f"masked_sample_loop: unknown sampler {sampler!r} (ddpm or ddim)")
+        sched = masking.repaint_schedule(self.num_timesteps, jump_length, n_resample)
+        if sampler == "ddim" and int(n_resample) > 1:
+            raise H.MMDError(f"masked_sample_loop: resampling jumps (n_resample={int(n_resample)}) ride the ddpm stepper, not ddim")
+        if len(sched) == self.num_timesteps:
+            sched = None                     # no jumps: the plain loop below, as it has always been
         device = self._sampling_device(device)
         cond = masking.to_device(masking.normalize(known, mask, shape), device)
         ctr = self._counter()
@@ -552,17 +581,25 @@ class GaussianDiffusion:
         noise = {k: noise[k].to(device).float().contiguous() for k in ("video", "audio")}
         B = shape["video"][0]
         model_kwargs = model_kwargs or {}
-        stepper = self._graph_stepper(model, model_kwargs, use_graph, B, device, clip_denoised, update=sampler, eta=eta, lanes=lanes, cond=cond)
+        stepper = self._graph_stepper(model, model_kwargs, use_graph, B, device, clip_denoised, update=sampler, eta=eta, lanes=lanes, cond=cond,
+                                      jump_length=None if sched is None else int(jump_length))
         if stepper is not None:
             def paste(i):
                 if paste_known and i == 0:
                     stepper.paste_known()
             stepper.load(noise["video"], noise["audio"])
             stepper.load_cond(cond, noise)
-            yield from self._replay(stepper, self._indices(progress), after=paste)
+            if sched is None:
+                yield from self._replay(stepper, self._indices(progress), after=paste)
+            else:
+                yield from self._replay_schedule(stepper, self._progress(sched, progress), paste_known)
             return
         _, qtab = self.device_tables(device)
         x = dict(noise)
+        if sched is not None:
+            yield from self._resampled_host_loop(model, x, noise, cond, sched, int(jump_length), B, device, clip_denoised, model_kwargs,
+                                                 progress, paste_known)
+            return
         for i in self._indices(progress):
             t = th.tensor([i] * B, device=device)
             x = dict(x)                      # the state yielded last, and at first x_T itself, stay as they are: a new dict, and copies below
@@ -575,6 +612,59 @@ class GaussianDiffusion:
                     x = self.ddim_sample(model, x, t, clip_denoised=clip_denoised, model_kwargs=model_kwargs, eta=eta)["sample"]
                 else:
                     x = self.p_sample(model, x, t, clip_denoised=clip_denoised, model_kwargs=model_kwargs)["sample"]
+            if paste_known and i == 0:
+                for k, c in cond.items():
+                    ops.cond_replace(x[k], c.known, None, None, mask=c.mask, coef=(1.0, 0.0))
+            yield x
+
+    @staticmethod
+    def _progress(sched, progress):
+        if progress:
+            from tqdm.auto import tqdm
+            sched = tqdm(sched)
+        return sched
+
+    @staticmethod
+    def _replay_schedule(stepper, sched, paste_known):
+        """Run masking.repaint_schedule's operations on a loaded stepper: a step replays the step graph at its own draw and yields the
+        state, a jump replays the jump graph and yields nothing; the last operation of a schedule is step 0, after which the known cells
+        are pasted.  The stepper is closed when the generator ends, is closed or is dropped."""
+        try:
+            for op, i, draw in sched:
+                if op == "jump":
+                    stepper.jump(i, draw)
+                    continue
+                stepper.step(i, draw=draw)
+                if paste_known and i == 0:
+                    stepper.paste_known()
+                yield stepper.current()
+        finally:
+            stepper.close()
+
+    def _resampled_host_loop(self, model, x, noise, cond, sched, jump_length, B, device, clip_denoised, model_kwargs, progress, paste_known):
+        """masked_sample_loop's host loop over a schedule with jumps, launch by launch: the same operations at the same draws as the
+        graph-replayed loop (a CounterNoise takes the schedule's draw through drawing_at; any other source is called in the same order)."""
+        import contextlib
+        ctr = self._counter()
+        _, qtab = self.device_tables(device)
+        jtab = self.jump_tables(jump_length, device)
+        for op, i, draw in self._progress(sched, progress):
+            t = th.tensor([i] * B, device=device)
+            x = dict(x)                      # the state yielded last stays as it is
+            if op == "jump":
+                for k, tag in (("video", 0), ("audio", 1)):
+                    x[k] = x[k].clone()
+                    if ctr is not None:
+                        ops.renoise_ctr(x[k], ctr.key(device), ctr.ids(B, device), tag, jtab, t, th.full_like(t, draw))
+                    else:
+                        ops.q_sample(x[k], self._randn_like(x[k]).float().contiguous(), x[k], jtab, t)
+                continue
+            for k, c in cond.items():
+                x[k] = x[k].clone()
+                src = dict(ctr=(ctr.key(device), ctr.ids(B, device), 0 if k == "video" else 1)) if ctr is not None else dict(noise=noise[k])
+                ops.cond_replace(x[k], c.known, qtab, t, mask=c.mask, **src)
+            with th.no_grad(), (ctr.drawing_at(draw) if ctr is not None else contextlib.nullcontext()):
+                x = self.p_sample(model, x, t, clip_denoised=clip_denoised, model_kwargs=model_kwargs)["sample"]
             if paste_known and i == 0:
                 for k, c in cond.items():
                     ops.cond_replace(x[k], c.known, None, None, mask=c.mask, coef=(1.0, 0.0))

@@ -1131,6 +1131,46 @@ def ddpm_update_ctr(x, model_out, key, ids, tag, out, tables, t, F, C, HW, flags
     return out
 
 
+def _per_sample_i64(what, name, v, N):
+    if v.dtype != torch.int64 or v.numel() != N or not v.is_contiguous():
+        raise H.MMDError(f"{what}: {name} must be one contiguous int64 per sample ({N}), got {v.dtype} {tuple(v.shape)}")
+
+
+def ddpm_update_ctr_at(x, model_out, key, ids, tag, out, tables, t, draw, F, C, HW, flags, x0_out=None, mean_out=None, logvar_out=None):
+    """ddpm_update_ctr with the counter's draw word taken from draw[n] (int64 [N], low 32 bits) instead of t[n]."""
+    H.require_cuda(x, model_out, key, ids, out, tables, t, draw)
+    _per_sample_i64("ddpm_update_ctr_at", "draw", draw, x.shape[0])
+    _dispatch("mmd_ddpm_update_ctr_at", x.data_ptr(), model_out.data_ptr(), key.data_ptr(), ids.data_ptr(), int(tag), H.ptr(out), H.ptr(x0_out),
+              H.ptr(mean_out), H.ptr(logvar_out), tables.data_ptr(), t.data_ptr(), draw.data_ptr(), tables.shape[1], x.shape[0], F, C, HW, flags,
+              meta=("ddpm_update_ctr_at", 0, 12 * x.numel()))
+    return out
+
+
+def renoise_ctr(x, key, ids, tag, jtab, m, draw):
+    """In place: x = jtab[0, m[n]] x + jtab[1, m[n]] z, z = the counter normal of (element, draw[n], ids[n], tag): the forward jump of
+    resampled masked sampling (include/mmd.h: mmd_renoise_ctr).  x: fp32 contiguous video [N,F,C,H,W] (or [N,F,C,HW]) or audio [N,C,L];
+    jtab: fp32 contiguous [2, T]; m, draw, ids: int64 [N].  A level outside [0, T) leaves its sample as it is."""
+    H.require_cuda(x, key, ids, jtab, m, draw)
+    if x.dim() == 5:
+        F, C, HW = x.shape[1], x.shape[2], x.shape[3] * x.shape[4]
+    elif x.dim() == 4:
+        F, C, HW = x.shape[1:]
+    elif x.dim() == 3:
+        F, C, HW = 1, x.shape[1], x.shape[2]
+    else:
+        raise H.MMDError(f"renoise_ctr: x must be video [N,F,C,H,W] / [N,F,C,HW] or audio [N,C,L], got {tuple(x.shape)}")
+    N = x.shape[0]
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise H.MMDError("renoise_ctr: x must be contiguous fp32")
+    if jtab.dtype != torch.float32 or jtab.dim() != 2 or jtab.shape[0] != 2 or not jtab.is_contiguous():
+        raise H.MMDError("renoise_ctr: needs a contiguous fp32 [2, T] jump table")
+    for name, v in (("ids", ids), ("m", m), ("draw", draw)):
+        _per_sample_i64("renoise_ctr", name, v, N)
+    _dispatch("mmd_renoise_ctr", x.data_ptr(), key.data_ptr(), ids.data_ptr(), int(tag), jtab.data_ptr(), m.data_ptr(), draw.data_ptr(),
+              jtab.shape[1], N, F, C, HW, meta=("renoise_ctr", 0, 8 * x.numel()))
+    return x
+
+
 def ddim_update_ctr(x, model_out, key, ids, tag, out, tables, tab3, t, F, C, HW, flags, eta, x0_out=None):
     H.require_cuda(x, model_out, key, ids, tables, tab3, t)
     _dispatch("mmd_ddim_update_ctr", x.data_ptr(), model_out.data_ptr(), key.data_ptr(), ids.data_ptr(), int(tag), H.ptr(out), H.ptr(x0_out),

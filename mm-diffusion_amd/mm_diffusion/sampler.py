@@ -11,7 +11,8 @@ Structure: LaneStepper owns what every replayed step shares - the batch lanes an
 pre-plan that replaces the known cells, the per-step uploads, the lane events, and capture / launch / close over NAMED PLAN SETS
 (name -> per-lane plans behind the U-Net plan, and their per-lane graph execs once captured).  GraphStepper (DDPM / DDIM / variational
 bound) and SolverStepper (DPM-Solver / DPM-Solver++: DpmppStepper multistep, DpmSingleStepper single-step) record their update plans into
-sets and say, in set_step, which set the next launch replays."""
+sets and say, in set_step, which set the next launch replays.  A set may be `bare`: launched without the pre-plan and the U-Net plan (the
+forward jump of masked sampling with resampling, GraphStepper.jump)."""
 import ctypes
 import os
 
@@ -50,10 +51,11 @@ STREAMS = (("video", 0), ("audio", 1))      # stream key, and its plan stream id
 
 
 class _PlanSet:
-    """One named plan set: the per-lane plans that follow the U-Net plan, and their per-lane graph execs (None before capture)."""
+    """One named plan set: the per-lane plans that follow the U-Net plan, and their per-lane graph execs (None before capture).  A
+    `bare` set is launched on its own, without the pre-plan and the U-Net plan in front of it."""
 
-    def __init__(self, plans):
-        self.plans, self.graphs = plans, None
+    def __init__(self, plans, bare=False):
+        self.plans, self.graphs, self.bare = plans, None, bare
 
 
 def _replay(ps, r, stream):
@@ -101,8 +103,8 @@ class LaneStepper:
     def _lane(self, r):
         return slice(r * self.n, (r + 1) * self.n)
 
-    def _add_set(self, name, plans):
-        self._sets[name] = _PlanSet(plans)
+    def _add_set(self, name, plans, bare=False):
+        self._sets[name] = _PlanSet(plans, bare)
         return plans
 
     @property
@@ -201,9 +203,10 @@ class LaneStepper:
         audio chain)."""
         e = self.engs[r]
         aux = e.aux.cuda_stream
-        if self.pre_plans:
-            ops.run_plan(self.pre_plans[r], stream, aux)
-        ops.run_plan(e.plan_f32 if self.use_f32 else e.plan, stream, aux)
+        if not ps.bare:
+            if self.pre_plans:
+                ops.run_plan(self.pre_plans[r], stream, aux)
+            ops.run_plan(e.plan_f32 if self.use_f32 else e.plan, stream, aux)
         ops.run_plan(ps.plans[r], stream, aux)
 
     def _capture(self, ps):
@@ -292,11 +295,21 @@ class GraphStepper(LaneStepper):
     lane reads its slice of the sample ids as it reads its slice of the timesteps - and set_step takes the window shifts from the counter.
 
     cond (masking.normalize's result; update "ddpm" / "ddim") conditions the step on known cells: every lane's graph starts with one
-    mmd_cond_replace per conditioned stream, with noise = that stream's x_T (masked_sample_loop).  cond=None records nothing."""
+    mmd_cond_replace per conditioned stream, with noise = that stream's x_T (masked_sample_loop).  cond=None records nothing.
 
-    def __init__(self, diffusion, unet, batch, device, clip_denoised=True, use_graph=True, update="ddpm", eta=0.0, lanes=None, cond=None):
+    jump_length (update "ddpm") equips the stepper for masked sampling with resampling jumps (masking.repaint_schedule), where a step
+    runs more than once: a full-batch device `draw` buffer sits next to t_idx and is pushed with it; with a counter source the step set
+    records mmd_ddpm_update_ctr_at, which draws at draw[n] instead of t[n], and the window shifts come from ctr.shifts(draw); and a
+    second, bare plan set "jump" - no pre-plan, no U-Net plan - holds the forward jump of t_idx[n] = m over jump_length levels: per
+    stream on its own stream one mmd_renoise_ctr at draw[n], or without a counter source one mmd_q_sample on the stream's noise buffer
+    (jump() refills it: video first, then audio), then the join.  jump_length=None records none of this."""
+
+    def __init__(self, diffusion, unet, batch, device, clip_denoised=True, use_graph=True, update="ddpm", eta=0.0, lanes=None, cond=None,
+                 jump_length=None):
         if update not in ("ddpm", "ddim", "vlb"):
             raise H.MMDError(f"unknown update {update!r} (ddpm, ddim or vlb)")
+        if jump_length is not None and update != "ddpm":
+            raise H.MMDError(f"resampling jumps ride the ddpm update, not {update!r}")
         if cond and update == "vlb":
             raise H.MMDError("masked conditioning rides the sampling steps (ddpm, ddim), not the variational bound")
         from .seeded import counter_source
@@ -317,6 +330,12 @@ class GraphStepper(LaneStepper):
         self.tmap = list(tmap) if tmap is not None else list(range(diffusion.num_timesteps))
         self.orig_T = getattr(diffusion, "original_num_steps", diffusion.num_timesteps)
         self._record_cond(cond, qtab)
+        self.draw = self._up_d = self.jtab = None
+        if jump_length is not None:
+            self.draw = th.zeros(self.N, dtype=th.int64, device=self.device)      # the counter's draw word of the step or the jump
+            self._up_d = H.Staged(self.draw)
+            self.jtab = diffusion.jump_tables(jump_length, self.device)
+            self.jump_levels = self.jtab.shape[1] - int(jump_length)               # levels m with m + jump_length <= T - 1
         if update == "vlb":
             # static x_0, and per stream the (vb, xstart_mse, eps_mse) result tables [N, T] the reductions write at column t
             T = self.tab.shape[1]
@@ -327,6 +346,7 @@ class GraphStepper(LaneStepper):
         elif update == "ddim":       # ddim_sample (gd:821-901): same graph, different fused update
             self._tab3 = diffusion.ddim_tables(self.device)
         plans = self.update_plans = self._add_set("step", [])
+        self.jump_plans = self._add_set("jump", [], bare=True) if self.jtab is not None else []
         for r, e in enumerate(self.engs):
             sl = self._lane(r)
             # per stream: (stream id, key, state, model output, (F, C, HW), counter tag)
@@ -346,6 +366,18 @@ class GraphStepper(LaneStepper):
                         self._record_update(r, *row[1:])
                 ops.record_sync(1, 0)
             plans.append(plan)
+            if self.jtab is not None:
+                jump = []
+                with ops.recording(jump):      # the audio stream forks from the origin here: no U-Net plan in front has done it
+                    ops.record_sync(0, 1)
+                    for sid, k, xk, _, _, tag in rows:
+                        with ops.on_stream(sid):
+                            if ctr is not None:
+                                ops.renoise_ctr(xk, self.key, self.ids[sl], tag, self.jtab, self.t_idx[sl], self.draw[sl])
+                            else:
+                                ops.q_sample(xk, self._noise[k][sl], xk, self.jtab, self.t_idx[sl])
+                    ops.record_sync(1, 0)
+                self.jump_plans.append(jump)
         self.update_plan = plans[0]
 
     def _record_update(self, r, k, x, out, geom, tag):
@@ -362,6 +394,9 @@ class GraphStepper(LaneStepper):
             fn = ops.ddim_update_ctr if self.ctr is not None else ops.ddim_update
             fn(x, out, *src, x, self.tab, self._tab3, t_idx, F, C, HW, self.flags, self.eta)
         else:
+            if self.ctr is not None and self.draw is not None:
+                ops.ddpm_update_ctr_at(x, out, *src, x, self.tab, t_idx, self.draw[sl], F, C, HW, self.flags)
+                return
             fn = ops.ddpm_update_ctr if self.ctr is not None else ops.ddpm_update
             fn(x, out, *src, x, self.tab, t_idx, F, C, HW, self.flags)
 
@@ -374,9 +409,57 @@ class GraphStepper(LaneStepper):
         """update="vlb": {"video" / "audio": (vb, xstart_mse, eps_mse)} [N, T] tables, column = loop index t."""
         return self.res
 
-    def set_step(self, i, shifts=None, noise=None):
-        """Refresh the per-step device state: timestep, shifts, noise (video first, then audio - gd:453-454)."""
+    def _push_draw(self, draw):
+        self._up_d.host().fill_(int(draw))
+        self._up_d.push()
+
+    def _fresh_noise(self):
+        """Both noise buffers from the diffusion's source: video first, then audio."""
+        if self.diff.noise_source is not None:
+            self.noise_v.copy_(self.diff.noise_source(self.noise_v))
+            self.noise_a.copy_(self.diff.noise_source(self.noise_a))
+        else:
+            self.noise_v.normal_()
+            self.noise_a.normal_()
+
+    def jump(self, m, draw, noise=None):
+        """The forward jump from level m (jump_length levels up) at `draw`: refresh t_idx, the draw and - without a counter source - the
+        noise (`noise` = {"video", "audio"}, else drawn video first, then audio), and replay the jump set."""
+        if self.jtab is None:
+            raise H.MMDError("this stepper was built without jump_length: it has no jump set")
+        m = int(m)
+        if not 0 <= m < self.jump_levels:
+            raise H.MMDError(f"jump: level {m} is outside [0, {self.jump_levels}): the jump would end above the last level")
+        self._set = "jump"
+        self._up_t.host().fill_(m)
+        self._up_t.push()
+        self._push_draw(draw)
+        if self.ctr is not None:
+            if noise is not None:
+                raise H.MMDError("this jump draws its noise in the kernel (CounterNoise): it takes no noise tensors")
+        elif noise is not None:
+            self.noise_v.copy_(noise["video"])
+            self.noise_a.copy_(noise["audio"])
+        else:
+            self._fresh_noise()
+        self.launch()
+
+    def step(self, i, shifts=None, noise=None, draw=None):
+        self.set_step(i, shifts, noise, draw)
+        self.launch()
+
+    def set_step(self, i, shifts=None, noise=None, draw=None):
+        """Refresh the per-step device state: timestep, shifts, noise (video first, then audio - gd:453-454).  draw (a stepper with
+        jump_length only; default i): the counter's draw word of this visit of step i, for the noise and the window shifts."""
         tm = self.tmap[int(i)]
+        self._set = "step"
+        if self.draw is not None:
+            draw = int(i) if draw is None else int(draw)
+            self._push_draw(draw)
+            if shifts is None and self.ctr is not None and self.unet.shift_source is None:
+                shifts = self.ctr.shifts(draw, self.unet)
+        elif draw is not None and int(draw) != int(i):
+            raise H.MMDError("a draw other than the step's index needs a stepper built with jump_length")
         self._push_step(int(i), float(tm) * (1000.0 / self.orig_T) if self.use_f32 else int(tm), shifts)
         if self.ctr is not None:
             if noise is not None:
@@ -384,14 +467,10 @@ class GraphStepper(LaneStepper):
         elif noise is not None:
             self.noise_v.copy_(noise["video"])
             self.noise_a.copy_(noise["audio"])
-        elif self.diff.noise_source is not None:
+        else:
             if hasattr(self.diff.noise_source, "set_draw"):      # update="vlb" keeps its noise in memory: the callable form at this index
                 self.diff.noise_source.set_draw(int(i))
-            self.noise_v.copy_(self.diff.noise_source(self.noise_v))
-            self.noise_a.copy_(self.diff.noise_source(self.noise_a))
-        else:
-            self.noise_v.normal_()
-            self.noise_a.normal_()
+            self._fresh_noise()
 
 
 # Which kernel a recorded DPM-Solver++ step takes its thresholding quantile from: "multi" = the three-level multi-workgroup selection

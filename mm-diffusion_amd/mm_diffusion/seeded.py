@@ -6,6 +6,8 @@ Sample k of seed s then comes out bitwise the same at any batch position, batch 
 eager path, whatever else the process drew before: x_T, the per-step noise (drawn inside the update kernels, mmd_ddpm_update_ctr /
 mmd_ddim_update_ctr) and the window shifts all come from Philox4x32-10 on the counter layout of include/mmd.h (mmd_ctr_fill):
     c0 = element >> 2, c1 = draw (the loop index; X_T for the start noise), c2 = sample id, c3 = stream tag.
+A loop that runs a step more than once names its draws itself (masked_sample_loop with resampling jumps, masking.repaint_schedule: visit r
+of step i draws at i + r T, the k-th forward jump at 0x80000000 + k; drawing_at() is the route through p_sample).
 The reference's scripts carry a `--seed` flag that seeds nothing (common.py:103-114), and seeding torch by hand gives a clip that depends
 on its batch position, the rank and the window shifts handed out before; with `noise_source` unset (or any other callable) all of that
 stays exactly as it is.  The training-side noise (q_sample in the losses, dropout) and the variational-bound stepper are not covered."""
@@ -48,7 +50,7 @@ class CounterNoise:
     """callable(like) -> N(0,1) tensor, as every `noise_source`; the sampling loops recognise the class and draw in-kernel instead.
 
     seed: 64-bit; the samples of a batch of B are first_sample ... first_sample + B - 1, or `sample_ids` (any ids in [0, 2^32), one per
-    batch row).  `draw` is the loop index the callable form reads; p_sample / ddim_sample set it from t."""
+    batch row).  `draw` is the loop index the callable form reads; p_sample / ddim_sample set it from t, or from drawing_at(draw)."""
 
     def __init__(self, seed, first_sample=0, sample_ids=None):
         seed = int(seed)
@@ -61,6 +63,7 @@ class CounterNoise:
         for i in (self.sample_ids if self.sample_ids is not None else [self.first_sample]):
             self._check_id(i)
         self.draw = None
+        self.explicit = None
         self._dev = {}
 
     @staticmethod
@@ -102,6 +105,9 @@ class CounterNoise:
     def set_draw(self, t):
         """The draw of the callable form and of shifts(): an int, or the timestep tensor of a step, which must be uniform across the batch
         (one window-shift draw serves the whole batch)."""
+        if self.explicit is not None:      # drawing_at(): the loop names the draw, the timestep does not
+            self.draw = self.explicit
+            return self.draw
         if th.is_tensor(t):
             lo, hi = int(t.min()), int(t.max())
             if lo != hi:
@@ -109,6 +115,23 @@ class CounterNoise:
             t = lo
         self.draw = int(t) & MASK
         return self.draw
+
+    @contextlib.contextmanager
+    def drawing_at(self, draw):
+        """While active, every step draws at `draw` whatever its timestep: set_draw(t) keeps `draw`, and p_sample's update kernel reads
+        it from draws() (mmd_ddpm_update_ctr_at).  A loop that runs a timestep more than once (masked_sample_loop with resampling jumps,
+        masking.repaint_schedule) gives every visit a draw of its own this way."""
+        prev, self.explicit = self.explicit, int(draw) & MASK
+        try:
+            yield self
+        finally:
+            self.explicit = prev
+
+    def draws(self, batch, device):
+        """device int64 [batch] filled with the draw of drawing_at(), or None outside it (the draw is then the timestep)."""
+        if self.explicit is None:
+            return None
+        return th.full((int(batch),), self.explicit, dtype=th.int64, device=device)
 
     def randn(self, shape, tag, draw, device=None):
         """fp32 N(0,1) tensor of `shape` [N, ...] for stream `tag` at `draw`, rows = this source's samples (mmd_ctr_fill)."""
