@@ -16,13 +16,12 @@
 //     applies the fused affine + SiLU in registers (affine rows of the at most two samples of a workgroup in LDS), and multiplies with
 //     the step's weight slab [columns][64] that the four waves share through a two-stage LDS ring (global_load_lds, the row-strip
 //     kernel's swizzled image);
-//   * epilogue from the accumulators as in the row-strip kernel: v_permlane32_swap pairs -> 8 consecutive channels per lane, bias,
-//     16-byte stores, quad statistics (sum, sum of squares per 64-row record and channel quad) of the values as stored.
+//   * the row-wave epilogue (mmd_rowwave.h): 8 consecutive channels per lane, bias, 16-byte stores, quad statistics records.
 // The normalisation is redone per tap and per column range (3 x 1 .. 8 times): ~8 VALU instructions per element, which makes this a
 // VALU-bound kernel - by design: it runs beside the video chain's MFMA-bound launches and no longer round-trips the normalised tensor.
 // K order (tap-major, channels ascending, 16-channel MFMA steps) and every rounding point (the normalised value is rounded to bf16 like
 // gn_apply's output) equal gn_apply + conv_gemm: the output is bitwise equal to the two launches it replaces.
-#include "mmd_common.h"
+#include "mmd_rowwave.h"
 
 struct AConvParams {
   const char* X; int64_t ldx;
@@ -49,30 +48,17 @@ __global__ __launch_bounds__(256, 2) void aconv_kernel(const AConvParams p, cons
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int half = lane >> 5, l31 = lane & 31;
   // the nsplit workgroups of one row block get consecutive ids inside one XCD's contiguous range: they share the block's rows in that L2
-  const int nwg = gridDim.x;
-  int wgid;
-  {
-    const int bid = blockIdx.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int wgid = xcd_block_id(blockIdx.x, gridDim.x);
   const int sp = wgid % nsplit, mt = wgid / nsplit;
   const int cbase = sp * CS, m0 = mt * 128;
   const int K = 3 * p.Cin, nck = p.Cin >> 6, nsteps = 3 * nck;
 
-  typedef const __attribute__((address_space(1))) void* gptr_t;
-  typedef __attribute__((address_space(3))) void* lptr_t;
-  const int lrow = lane >> 3, pc = lane & 7;
   const char* w_ptr[GP];
 #pragma unroll
-  for (int ih = 0; ih < GP; ++ih) {
-    const int row = 8 * (ih * 4 + wave) + lrow;            // row of the slab this lane fetches 16 bytes of
-    const int logical = pc ^ ((row >> 1) & 7);
-    w_ptr[ih] = p.W + ((int64_t)(cbase + row) * K + logical * 8) * 2;
-  }
+  for (int ih = 0; ih < GP; ++ih) w_ptr[ih] = slab_row_ptr(p.W, cbase, K, ih, wave, lane);
   auto issue_w = [&](int stage, int s) {                   // step s = (tap, chunk): K offset s * 64 (tap-major: tap * Cin + chunk * 64)
 #pragma unroll
-    for (int ih = 0; ih < GP; ++ih)
-      __builtin_amdgcn_global_load_lds((gptr_t)(w_ptr[ih] + (int64_t)s * 128), (lptr_t)(sW + stage * STAGE_B + (ih * 4 + wave) * 1024), 16, 0, 0);
+    for (int ih = 0; ih < GP; ++ih) slab_issue(w_ptr[ih] + (int64_t)s * 128, sW + stage * STAGE_B, ih, wave);
   };
   // this lane's row, its sample and position; the workgroup's rows touch at most two samples (L >= 128)
   const int row = m0 + wave * 32 + l31;
@@ -97,14 +83,7 @@ __global__ __launch_bounds__(256, 2) void aconv_kernel(const AConvParams p, cons
   load_x(0, xc, okc);
   // bias of the column range and the affine rows of the two samples -> LDS
   if (tid < CS) sBias[tid] = p.bias ? p.bias[cbase + tid] : 0.f;
-  {
-    const int nS = p.M / p.L;
-    for (int i = tid; i < 4 * p.Cin; i += 256) {
-      const int sl = i / (2 * p.Cin), ab = (i / p.Cin) & 1, c = i % p.Cin;
-      const int sidx = min(s0 + sl, nS - 1);
-      sAB[i] = (ab ? p.gb : p.ga)[(int64_t)sidx * p.Cin + c];
-    }
-  }
+  load_affine_rows(sAB, p.ga, p.gb, s0, p.M / p.L, p.Cin, tid);
   f32x16 acc[CSUB];
 #pragma unroll
   for (int a = 0; a < CSUB; ++a)
@@ -125,20 +104,8 @@ __global__ __launch_bounds__(256, 2) void aconv_kernel(const AConvParams p, cons
     u32x4 xb[4];
 #pragma unroll
     for (int cg = 0; cg < 4; ++cg) {
-      float x[8];
-      Elt<__bf16>::unpack(xc[cg], x);
       const float* ap = sAB + gsel + ck * 64 + cg * 16 + half * 8;
-      const float* bp = ap + p.Cin;
-#pragma unroll
-      for (int e = 0; e < 8; e += 4) {
-        const f32x4 av = *(const f32x4*)(ap + e), bv = *(const f32x4*)(bp + e);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const float y = x[e + k] * av[k] + bv[k];
-          x[e + k] = p.act ? silu_f(y) : y;
-        }
-      }
-      u32x4 y = Elt<__bf16>::pack(x);
+      u32x4 y = affine_act_octet(xc[cg], ap, ap + p.Cin, p.act);
 #pragma unroll
       for (int k = 0; k < 4; ++k) y[k] = okc ? y[k] : 0u;
       xb[cg] = y;
@@ -148,7 +115,7 @@ __global__ __launch_bounds__(256, 2) void aconv_kernel(const AConvParams p, cons
     for (int cg = 0; cg < 4; ++cg)
 #pragma unroll
       for (int a = 0; a < CSUB; ++a) {
-        const u32x4 fw = *(const u32x4*)(bW + a * 32 * 128 + (((2 * cg + half) ^ xsw) * 16));
+        const u32x4 fw = *(const u32x4*)(bW + a * 32 * 128 + swz_frag_off(cg, half, xsw));
         acc[a] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fw), __builtin_bit_cast(bf16x8, xb[cg]), acc[a], 0, 0, 0);
       }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -158,8 +125,7 @@ __global__ __launch_bounds__(256, 2) void aconv_kernel(const AConvParams p, cons
     okc = okn;
   }
 
-  // ---- epilogue: acc[a][4 q + j] = channel 32 a + 8 q + 4 half + j of row l31.  Pair q = 2 j2 (vdst) with q = 2 j2 + 1 (src): afterwards
-  //      this lane holds the 8 consecutive channels 32 a + 16 j2 + 8 half .. + 8 of its row
+  // ---- epilogue (mmd_rowwave.h): this lane's octets are the channels 32 a + 16 j2 + 8 half .. + 8 of its row
   const bool wave_ok = (int64_t)m0 + wave * 32 < p.M;      // wave-uniform (M % 64 == 0 when statistics are on: wave pairs are whole records)
   const int64_t rec = ((int64_t)m0 + wave * 32) / 64;
   float srec[CSUB][2][2];
@@ -168,38 +134,20 @@ __global__ __launch_bounds__(256, 2) void aconv_kernel(const AConvParams p, cons
 #pragma unroll
     for (int j2 = 0; j2 < 2; ++j2) {
       const int cb = a * 32 + 16 * j2 + 8 * half;
-      const f32x4 b0 = *(const f32x4*)(sBias + cb), b1 = *(const f32x4*)(sBias + cb + 4);
+      const Octet b = load_octet(sBias + cb);
       float v[8];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[a][8 * j2 + j]), __float_as_uint(acc[a][8 * j2 + 4 + j]), false, false);
-        v[j] = __uint_as_float(sw[0]);
-        v[4 + j] = __uint_as_float(sw[1]);
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { v[j] += b0[j]; v[4 + j] += b1[j]; }
+      acc_octet(acc[a], j2, v);
+      octet_add(v, b);
       const u32x4 pk = Elt<__bf16>::pack(v);
       if (rok) *(u32x4*)(p.Y + ((int64_t)rowc * p.ldy + cbase + cb) * 2) = pk;
-      if (p.stats) {                                       // statistics of the values as STORED: the lane's 8 channels = two quads
-        float rf[8], u[4] = {0.f, 0.f, 0.f, 0.f};
-        Elt<__bf16>::unpack(pk, rf);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          u[0] += rf[j];
-          u[1] += rf[4 + j];
-          u[2] += rf[j] * rf[j];
-          u[3] += rf[4 + j] * rf[4 + j];
-        }
-        // lanes 16 / 17 of each half end up with the (sum, sum of squares) of quad 0 / 1 of the lane group's 8 channels
-        const float t0 = halfwave_total(u[0]), t1 = halfwave_total(u[1]), t2 = halfwave_total(u[2]), t3 = halfwave_total(u[3]);
-        const float msum = (l31 & 1) ? t1 : t0, msq = (l31 & 1) ? t3 : t2;
-        srec[a][j2][0] = msum;
-        srec[a][j2][1] = msq;
-        if ((wave & 1) && (l31 >> 1) == 8) {               // a wave holds HALF a record (32 rows): the odd wave parks its half
-          float* d = sRec + (((wave * CSUB + a) * 2 + j2) * 2 + half) * 4 + (l31 & 1) * 2;
-          d[0] = msum;
-          d[1] = msq;
-        }
+      if (p.stats) {                                       // a wave holds HALF a record (32 rows): the odd wave parks its half
+        float u[4] = {0.f, 0.f, 0.f, 0.f};
+        quad_sums(pk, u);
+        quad_fold(u, l31, srec[a][j2][0], srec[a][j2][1]);
+        // (l31 >> 1) == 8 is is_record_lane(l31), spelled out here and below on purpose: with the call inside these conditions
+        // aconv_kernel<2> issues the K loop's barrier ahead of the step's last MFMA (profiles/rowwave_epilogue_device_code.txt)
+        if ((wave & 1) && (l31 >> 1) == 8)
+          quad_put(sRec + (((wave * CSUB + a) * 2 + j2) * 2 + half) * 4 + (l31 & 1) * 2, srec[a][j2][0], srec[a][j2][1]);
       }
     }
   if (p.stats) {
@@ -210,10 +158,7 @@ __global__ __launch_bounds__(256, 2) void aconv_kernel(const AConvParams p, cons
 #pragma unroll
         for (int j2 = 0; j2 < 2; ++j2) {
           const float* o = sRec + ((((wave + 1) * CSUB + a) * 2 + j2) * 2 + half) * 4 + (l31 & 1) * 2;
-          const int col = cbase + a * 32 + 16 * j2 + 8 * half;
-          float* d = p.stats + (rec * p.stats_ld + (col >> 2) + (l31 & 1)) * 2;
-          d[0] = srec[a][j2][0] + o[0];
-          d[1] = srec[a][j2][1] + o[1];
+          half_record_finish(quad_record(p.stats, rec, p.stats_ld, cbase + a * 32 + 16 * j2 + 8 * half, l31), srec[a][j2], o);
         }
     }
   }

@@ -6,14 +6,6 @@
 #include <stdarg.h>
 #include "../../include/mmd.h"   // the C ABI: every extern "C" definition is checked against its declaration
 
-#define MMD_F32 0
-#define MMD_BF16 1
-
-#define MMD_OK 0
-#define MMD_ERR_ARG (-1)
-#define MMD_ERR_LAUNCH (-2)
-#define MMD_ERR_UNSUPPORTED (-3)
-
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;

@@ -1,7 +1,7 @@
 // Convolutions at the API layout edge: the stem (InitialBlock, unet:680-694; fp32 [N, F, C, H, W] -> channels-last rows) and the head
 // (unet:1003-1012; rows -> fp32 [N, F, C, H, W]) in their direct, cooperative, strip, MFMA and GEMM + gather forms, and the
 // super-resolution model's bilinear-upsample + concat input (image_unet.py:704-715).
-#include "mmd_common.h"
+#include "mmd_rowwave.h"
 
 // ----------------------------------------------------------------------------- stem conv (API layout -> channels-last)
 // in : fp32 [N, F, Cin, H, W] (audio: F=1, H=1, W=L)   W packed fp32 [ntaps][Cin][Cout]   out: T [N*F*H*W, Cout]
@@ -230,25 +230,16 @@ __global__ __launch_bounds__(256, 2) void stem_conv_mfma_kernel(const EdgeConvPa
         for (int b = 0; b < NB; ++b) acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(wreg[s][b], xcur[s], acc[b], 0, 0, 0);
       }
     }
-    // acc[b][4 q + j] = channel 32 b + 8 q + 4 half + j of pixel l31: pair q = 2 j2 with q = 2 j2 + 1 across the half-waves
+    // the row-wave epilogue (mmd_rowwave.h): the lane's octets are the channels 32 b + 16 j2 + 8 half .. + 8 of pixel l31
     const int64_t m = g * 32 + l31;                      // groups walk the rows in order: 32 consecutive pixels of one image row
 #pragma unroll
     for (int b = 0; b < NB; ++b)
 #pragma unroll
       for (int j2 = 0; j2 < 2; ++j2) {
         float v[8];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[b][8 * j2 + j]), __float_as_uint(acc[b][8 * j2 + 4 + j]), false, false);
-          v[j] = __uint_as_float(sw[0]);
-          v[4 + j] = __uint_as_float(sw[1]);
-        }
+        acc_octet(acc[b], j2, v);
         const int col = b * 32 + 16 * j2 + 8 * half;
-        if (p.bias) {
-          const f32x4 b0 = *(const f32x4*)(p.bias + col), b1 = *(const f32x4*)(p.bias + col + 4);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) { v[j] += b0[j]; v[4 + j] += b1[j]; }
-        }
+        if (p.bias) octet_add(v, load_octet(p.bias + col));
         *(u32x4*)(p.y + (m * p.ldy + col) * 2) = Elt<__bf16>::pack(v);
       }
 #pragma unroll

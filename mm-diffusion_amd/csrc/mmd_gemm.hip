@@ -15,7 +15,7 @@
 // The weights are the MFMA A operand (D rows = co) so each lane owns 4 consecutive output channels;
 // the accumulators are staged through LDS in fp32 and written with 16-byte coalesced row stores with
 // bias and residual folded in.
-#include "mmd_common.h"
+#include "mmd_rowwave.h"
 
 struct ConvGemmParams {
   const char* A; int64_t lda;
@@ -252,12 +252,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(const ConvGemmParams 
 
   // XCD-aware tile order: consecutive tiles (sharing activation halos / weight panels) stay on one L2
   const int Nt = (p.Cout + BN - 1) / BN;
-  const int nwg = gridDim.x;
-  int wgid;
-  {
-    const int bid = blockIdx.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int wgid = xcd_block_id(blockIdx.x, gridDim.x);
   const int nt = wgid % Nt, mt = wgid / Nt;
   const int m0 = mt * BM, n0 = nt * BN;
 
@@ -450,12 +445,7 @@ __global__ __launch_bounds__(256, (NS > 2 ? 1 : 2)) void conv_gemm_glds_kernel(c
   if (tid < p.ntaps * 3) s_taps[tid] = p.taps[tid];
 
   const int Nt = (p.Cout + BN - 1) / BN;
-  const int nwg = gridDim.x;
-  int wgid;
-  {
-    const int bid = blockIdx.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int wgid = xcd_block_id(blockIdx.x, gridDim.x);
   const int nt = wgid % Nt, mt = wgid / Nt;
   const int m0 = mt * BM, n0 = nt * BN;
 
@@ -803,12 +793,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_halo_kernel(const ConvGemmPa
   if (tid < p.ntaps * 3) s_taps[tid] = p.taps[tid];
 
   const int Nt = (p.Cout + BN - 1) / BN;
-  const int nwg = gridDim.x;
-  int wgid;
-  {
-    const int bid = blockIdx.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int wgid = xcd_block_id(blockIdx.x, gridDim.x);
   const int nt = wgid % Nt, mt = wgid / Nt;
   const int n0 = nt * BN;
   const int TW = p.D2 / PW, tpf = TW * (p.D1 / PH);
@@ -1099,12 +1084,7 @@ __global__ __launch_bounds__(512, 2) void conv_gemm_halo16_kernel(const ConvGemm
   const int half = lane >> 5, l31 = lane & 31;
 
   const int Nt = (p.Cout + BN - 1) / BN;
-  const int nwg = gridDim.x;
-  int wgid;
-  {
-    const int bid = blockIdx.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int wgid = xcd_block_id(blockIdx.x, gridDim.x);
   const int nt = wgid % Nt, mt = wgid / Nt;
   const int n0 = nt * BN;
   const int TW = p.D2 / PW, tpf = TW * (p.D1 / PH);
@@ -1443,12 +1423,7 @@ __device__ __forceinline__ void conv1x1_strip_body(const ConvGemmParams& p, cons
   const int half = lane >> 5, l31 = lane & 31;
 
   // the nsplit blocks of one row strip get consecutive ids inside one XCD's contiguous range: they share the strip's rows in that L2
-  const int nwg = gridDim.x;
-  int wgid;
-  {
-    const int bid = blockIdx.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int wgid = xcd_block_id(blockIdx.x, gridDim.x);
   const int sp = wgid % nsplit, mt = wgid / nsplit;
   const int Cs = p.Cout / nsplit, cbase = sp * Cs, nchunk = Cs / CC;
   const int m0 = mt * BR;

@@ -14,18 +14,18 @@
 //     step straight from global memory into MFMA B-operand fragments one step ahead; h gets the fused affine + SiLU in registers
 //     (affine rows of the at most two samples of a workgroup in LDS) and is rounded to bf16 where gn_apply rounds; the step's weight
 //     slab [CS][64] goes through a two-stage LDS ring (global_load_lds, the strip kernel's swizzled image);
-//   * epilogue as in the strip kernel's two-operand instance: the skip product gets its bias and its bf16 rounding, then it is added
-//     where the residual is added; v_permlane32_swap pairs, 16-byte stores, quad statistics of the values as stored.
+//   * the row-wave epilogue (mmd_rowwave.h) in the form of the strip kernel's two-operand instance: the skip product gets its bias and
+//     its bf16 rounding, then it is added where the residual is added.
 // Within each accumulator K runs in ascending 16-channel MFMA steps, so Y is bitwise the two launches'.  The statistics records are
-// folded in the order of the out conv the layer runs today (mmd_gemm.hip: dispatch_conv1x1_strip), which has two:
-//   one fragment  (K1 >= 384, and K1 = 128 with the norm fused and samples of >= 16384 rows): halfwave_total over a wave's 32 rows, then
-//                 even wave + odd wave through LDS;
-//   two fragments (K1 = 256, K1 = 128 otherwise): a lane of that kernel holds rows r and r + 32 of a 64-row record and sums the eight
-//                 values of r, then the eight of r + 32, into one running sum BEFORE halfwave_total.  Here those rows belong to the
-//                 same lane of the even and the odd wave of a pair: the odd wave hands its stored values over through LDS (the weight
-//                 ring is free by then) and the even wave continues its running sums with them.
+// folded in the order of the out conv the layer runs today (mmd_gemm.hip: dispatch_conv1x1_strip), which has two (steps 2 and 4 of the
+// fold order in mmd_rowwave.h):
+//   one fragment  (K1 >= 384, and K1 = 128 with the norm fused and samples of >= 16384 rows): a wave folds its 32 rows, then even wave
+//                 + odd wave through LDS;
+//   two fragments (K1 = 256, K1 = 128 otherwise): rows r and r + 32 of a record are one lane's running sums in that kernel.  Here
+//                 they belong to the same lane of the even and the odd wave of a pair: the odd wave hands its stored values over
+//                 through LDS (the weight ring is free by then) and the even wave continues its running sums with them.
 // A null affine (ga == gb == nullptr) means h is already normalised: the launch then runs behind gn_apply.
-#include "mmd_common.h"
+#include "mmd_rowwave.h"
 #include <type_traits>
 
 struct RTailParams {
@@ -61,26 +61,16 @@ __global__ __launch_bounds__(256, 2) void rtail_kernel(const RTailParams p, cons
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int half = lane >> 5, l31 = lane & 31;
   // the nsplit workgroups of one row block get consecutive ids inside one XCD's contiguous range: they share the block's rows in that L2
-  const int nwg = gridDim.x;
-  int wgid;
-  {
-    const int bid = blockIdx.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int wgid = xcd_block_id(blockIdx.x, gridDim.x);
   const int sp = wgid % nsplit, mt = wgid / nsplit;
   const int cbase = sp * CS, m0 = mt * 128;
   const int n2 = p.K2 / (64 * KB), nsteps = n2 + p.K1 / (64 * KB);
 
-  typedef const __attribute__((address_space(1))) void* gptr_t;
-  typedef __attribute__((address_space(3))) void* lptr_t;
-  const int lrow = lane >> 3, pc = lane & 7;
   const char *w_ptr[GP], *w2_ptr[GP];
 #pragma unroll
   for (int ih = 0; ih < GP; ++ih) {
-    const int row = 8 * (ih * 4 + wave) + lrow;            // row of the slab this lane fetches 16 bytes of
-    const int logical = pc ^ ((row >> 1) & 7);
-    w_ptr[ih] = p.W + ((int64_t)(cbase + row) * p.K1 + logical * 8) * 2;
-    w2_ptr[ih] = p.W2 + ((int64_t)(cbase + row) * p.K2 + logical * 8) * 2;
+    w_ptr[ih] = slab_row_ptr(p.W, cbase, p.K1, ih, wave, lane);
+    w2_ptr[ih] = slab_row_ptr(p.W2, cbase, p.K2, ih, wave, lane);
   }
   auto issue_w = [&](int stage, int s) {                   // step s: channels [64 KB s, + 64 KB) of x (s < n2), then of h (from s = n2)
 #pragma unroll
@@ -88,7 +78,7 @@ __global__ __launch_bounds__(256, 2) void rtail_kernel(const RTailParams p, cons
 #pragma unroll
       for (int ih = 0; ih < GP; ++ih) {
         const char* src = s < n2 ? w2_ptr[ih] + (int64_t)(s * KB + pl) * 128 : w_ptr[ih] + (int64_t)((s - n2) * KB + pl) * 128;
-        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(sW + stage * STAGE_B + pl * PLANE_B + (ih * 4 + wave) * 1024), 16, 0, 0);
+        slab_issue(src, sW + stage * STAGE_B + pl * PLANE_B, ih, wave);
       }
   };
   // this lane's row and its sample; the workgroup's rows touch at most two samples (L >= 128); rows past M read row M - 1 once more and
@@ -116,14 +106,7 @@ __global__ __launch_bounds__(256, 2) void rtail_kernel(const RTailParams p, cons
     sBias[tid] = p.bias ? p.bias[cbase + tid] : 0.f;
     sBias2[tid] = p.bias2 ? p.bias2[cbase + tid] : 0.f;
   }
-  if constexpr (GN) {
-    const int nS = p.M / p.L;
-    for (int i = tid; i < 4 * p.K1; i += 256) {
-      const int sl = i / (2 * p.K1), ab = (i / p.K1) & 1, c = i % p.K1;
-      const int sidx = min(s0 + sl, nS - 1);
-      sAB[i] = (ab ? p.gb : p.ga)[(int64_t)sidx * p.K1 + c];
-    }
-  }
+  if constexpr (GN) load_affine_rows(sAB, p.ga, p.gb, s0, p.M / p.L, p.K1, tid);
   f32x16 acc[CSUB], acc2[CSUB];                            // out conv | skip conv
 #pragma unroll
   for (int a = 0; a < CSUB; ++a)
@@ -144,20 +127,8 @@ __global__ __launch_bounds__(256, 2) void rtail_kernel(const RTailParams p, cons
       const int ck = s - n2;
 #pragma unroll
       for (int cg = 0; cg < NCG; ++cg) {
-        float x[8];
-        Elt<__bf16>::unpack(xc[cg], x);
         const float* ap = sAB + gsel + ck * (64 * KB) + cg * 16 + half * 8;
-        const float* bp = ap + p.K1;
-#pragma unroll
-        for (int e = 0; e < 8; e += 4) {
-          const f32x4 av = *(const f32x4*)(ap + e), bv = *(const f32x4*)(bp + e);
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const float y = x[e + k] * av[k] + bv[k];
-            x[e + k] = p.act ? silu_f(y) : y;
-          }
-        }
-        xc[cg] = Elt<__bf16>::pack(x);
+        xc[cg] = affine_act_octet(xc[cg], ap, ap + p.K1, p.act);
       }
     }
     const char* bW = sW + st * STAGE_B + l31 * 128;
@@ -165,7 +136,7 @@ __global__ __launch_bounds__(256, 2) void rtail_kernel(const RTailParams p, cons
     for (int cg = 0; cg < NCG; ++cg)
 #pragma unroll
       for (int a = 0; a < CSUB; ++a) {
-        const u32x4 fw = *(const u32x4*)(bW + (cg >> 2) * PLANE_B + a * 32 * 128 + (((2 * (cg & 3) + half) ^ xsw) * 16));
+        const u32x4 fw = *(const u32x4*)(bW + (cg >> 2) * PLANE_B + a * 32 * 128 + swz_frag_off(cg & 3, half, xsw));
         ac[a] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fw), __builtin_bit_cast(bf16x8, xc[cg]), ac[a], 0, 0, 0);
       }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -177,8 +148,7 @@ __global__ __launch_bounds__(256, 2) void rtail_kernel(const RTailParams p, cons
   for (; s < n2; ++s) step(s, std::false_type{}, acc2);
   for (; s < nsteps; ++s) step(s, std::integral_constant<bool, GN>{}, acc);
 
-  // ---- epilogue: acc[a][4 q + j] = channel 32 a + 8 q + 4 half + j of row l31.  Pair q = 2 j2 (vdst) with q = 2 j2 + 1 (src): afterwards
-  //      this lane holds the 8 consecutive channels 32 a + 16 j2 + 8 half .. + 8 of its row
+  // ---- epilogue (mmd_rowwave.h): this lane's octets are the channels 32 a + 16 j2 + 8 half .. + 8 of its row
   const bool wave_ok = (int64_t)m0 + wave * 32 < p.M;      // wave-uniform (M % 64 == 0 when statistics are on: wave pairs are whole records)
   const int64_t rec = ((int64_t)m0 + wave * 32) / 64;
   u32x4* sPk = (u32x4*)sW;                                 // two-fragment fold: [2 odd waves][CSUB * 2][64 lanes] stored values (the ring is free)
@@ -188,58 +158,32 @@ __global__ __launch_bounds__(256, 2) void rtail_kernel(const RTailParams p, cons
 #pragma unroll
     for (int j2 = 0; j2 < 2; ++j2) {
       const int cb = a * 32 + 16 * j2 + 8 * half;
-      const f32x4 b0 = *(const f32x4*)(sBias + cb), b1 = *(const f32x4*)(sBias + cb + 4);
-      const f32x4 c0 = *(const f32x4*)(sBias2 + cb), c1 = *(const f32x4*)(sBias2 + cb + 4);
       float v[8], sk[8], rf[8];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[a][8 * j2 + j]), __float_as_uint(acc[a][8 * j2 + 4 + j]), false, false);
-        v[j] = __uint_as_float(sw[0]);
-        v[4 + j] = __uint_as_float(sw[1]);
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { v[j] += b0[j]; v[4 + j] += b1[j]; }
+      const Octet b = load_octet(sBias + cb), c = load_octet(sBias2 + cb);
+      acc_octet(acc[a], j2, v);
+      octet_add(v, b);
       // + float(bf16(W2 . x + bias2)): the tensor the separate launch stores, then the residual add
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc2[a][8 * j2 + j]), __float_as_uint(acc2[a][8 * j2 + 4 + j]), false, false);
-        sk[j] = __uint_as_float(sw[0]) + c0[j];
-        sk[4 + j] = __uint_as_float(sw[1]) + c1[j];
-      }
+      acc_octet(acc2[a], j2, c, sk);
       Elt<__bf16>::unpack(Elt<__bf16>::pack(sk), rf);
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] += rf[j];
       const u32x4 pk = Elt<__bf16>::pack(v);
       if (rok) *(u32x4*)(p.Y + ((int64_t)rowc * p.ldy + cbase + cb) * 2) = pk;
-      if (p.stats) {                                       // statistics of the values as STORED: the lane's 8 channels = two quads
+      if (p.stats) {
         if (p.pair && (wave & 1)) {                        // (wave-uniform) the even wave sums these values behind its own
           sPk[((wave >> 1) * (CSUB * 2) + a * 2 + j2) * 64 + lane] = pk;
           continue;
         }
         float u[4] = {0.f, 0.f, 0.f, 0.f};
-        Elt<__bf16>::unpack(pk, rf);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          u[0] += rf[j];
-          u[1] += rf[4 + j];
-          u[2] += rf[j] * rf[j];
-          u[3] += rf[4 + j] * rf[4 + j];
-        }
+        quad_sums(pk, u);
         if (p.pair) {
 #pragma unroll
           for (int k = 0; k < 4; ++k) srec[a][j2][k] = u[k];
           continue;
         }
-        // lanes 16 / 17 of each half end up with the (sum, sum of squares) of quad 0 / 1 of the lane group's 8 channels
-        const float t0 = halfwave_total(u[0]), t1 = halfwave_total(u[1]), t2 = halfwave_total(u[2]), t3 = halfwave_total(u[3]);
-        const float msum = (l31 & 1) ? t1 : t0, msq = (l31 & 1) ? t3 : t2;
-        srec[a][j2][0] = msum;
-        srec[a][j2][1] = msq;
-        if ((wave & 1) && (l31 >> 1) == 8) {               // a wave holds HALF a record (32 rows): the odd wave parks its half
-          float* d = sRec + (((wave * CSUB + a) * 2 + j2) * 2 + half) * 4 + (l31 & 1) * 2;
-          d[0] = msum;
-          d[1] = msq;
-        }
+        quad_fold(u, l31, srec[a][j2][0], srec[a][j2][1]);
+        if ((wave & 1) && is_record_lane(l31))             // a wave holds HALF a record (32 rows): the odd wave parks its half
+          quad_put(sRec + (((wave * CSUB + a) * 2 + j2) * 2 + half) * 4 + (l31 & 1) * 2, srec[a][j2][0], srec[a][j2][1]);
       }
     }
   if (p.stats) {
@@ -249,29 +193,16 @@ __global__ __launch_bounds__(256, 2) void rtail_kernel(const RTailParams p, cons
       for (int a = 0; a < CSUB; ++a)
 #pragma unroll
         for (int j2 = 0; j2 < 2; ++j2) {
-          const int col = cbase + a * 32 + 16 * j2 + 8 * half;
-          float* d = p.stats + (rec * p.stats_ld + (col >> 2) + (l31 & 1)) * 2;
+          float* d = quad_record(p.stats, rec, p.stats_ld, cbase + a * 32 + 16 * j2 + 8 * half, l31);
           if (p.pair) {                                    // own row's running sums, continued with row + 32, then the fold over the rows
-            float u[4], rf[8];
+            float u[4], m[2];
 #pragma unroll
             for (int k = 0; k < 4; ++k) u[k] = srec[a][j2][k];
-            Elt<__bf16>::unpack(sPk[((wave >> 1) * (CSUB * 2) + a * 2 + j2) * 64 + lane], rf);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              u[0] += rf[j];
-              u[1] += rf[4 + j];
-              u[2] += rf[j] * rf[j];
-              u[3] += rf[4 + j] * rf[4 + j];
-            }
-            const float t0 = halfwave_total(u[0]), t1 = halfwave_total(u[1]), t2 = halfwave_total(u[2]), t3 = halfwave_total(u[3]);
-            if ((l31 >> 1) == 8) {
-              d[0] = (l31 & 1) ? t1 : t0;
-              d[1] = (l31 & 1) ? t3 : t2;
-            }
-          } else if ((l31 >> 1) == 8) {                    // own half + partner's half
-            const float* o = sRec + ((((wave + 1) * CSUB + a) * 2 + j2) * 2 + half) * 4 + (l31 & 1) * 2;
-            d[0] = srec[a][j2][0] + o[0];
-            d[1] = srec[a][j2][1] + o[1];
+            quad_sums(sPk[((wave >> 1) * (CSUB * 2) + a * 2 + j2) * 64 + lane], u);
+            quad_fold(u, l31, m[0], m[1]);
+            if (is_record_lane(l31)) quad_put(d, m[0], m[1]);
+          } else if (is_record_lane(l31)) {                // own half + partner's half
+            half_record_finish(d, srec[a][j2], sRec + ((((wave + 1) * CSUB + a) * 2 + j2) * 2 + half) * 4 + (l31 & 1) * 2);
           }
         }
     }

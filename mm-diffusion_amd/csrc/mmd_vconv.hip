@@ -17,14 +17,14 @@
 //     the halo stages.
 //   phase 2 (temporal, K = 3 x 128): six steps (tap, 64-channel plane) of 16 MFMAs per wave, operand rows = T rows shifted by 16 per
 //     frame; weights keep streaming through the same ring.
-//   epilogue: straight from the accumulators (v_permlane32_swap pairs -> 16-byte row stores), quad statistics records folded by DPP.
+//   epilogue: straight from the accumulators - the row-wave epilogue of mmd_rowwave.h (16-byte row stores, quad statistics records).
 // Every DMA is a buffer_load ... lds through a wave-uniform descriptor; the weights are read from an image packed once per layer
 // (mmd_vconv2d1d_pack: step-major slabs, pre-swizzled) so a weight piece is a linear 1 KB copy.  Every step issues a static number
 // of DMA instructions (dummies where there is nothing to fetch), so the waits are counted s_waitcnt vmcnt(N) + one raw s_barrier.
 // K order: spatial (32-channel chunk, tap, k) - not the (64-channel chunk, tap, k) of tiles 130 / 133, so T may differ from their
 // output in the last bf16 bit of a few elements; temporal (tap, channel) like every other main loop.  The layer that runs here is
 // chosen by its geometry alone (ops.vconv_fused_ok), never by timing.
-#include "mmd_common.h"
+#include "mmd_rowwave.h"
 #include <type_traits>
 
 struct VConvParams {
@@ -92,8 +92,7 @@ __global__ __launch_bounds__(512, 2) void vconv2d1d_kernel(const VConvParams p) 
   unsigned gvalid = 0, glc = 0;
   const float* gn_src = nullptr;
   auto setup = [&](int L) {
-    const int q = total >> 3, r = total & 7, xcd = L & 7;
-    const int wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (L >> 3);
+    const int wgid = xcd_block_id(L, total);
     n = wgid / ppf;
     patch = wgid - n * ppf;
     h0 = (patch / PWc) * 4;
@@ -399,19 +398,10 @@ __global__ __launch_bounds__(512, 2) void vconv2d1d_kernel(const VConvParams p) 
       char* tb = sA + wc * VC_TPLANE_B + trow * 128;
 #pragma unroll
       for (int j2 = 0; j2 < 2; ++j2) {
-        // acc[4 q + j] = channel 8 q + 4 half + j of row l31; pair q = 2 j2 with q = 2 j2 + 1: this lane then holds the 8 consecutive
-        // channels 16 j2 + 8 half .. + 8 of its row
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[a][b][8 * j2 + j]), __float_as_uint(acc[a][b][8 * j2 + 4 + j]), false, false);
-          v[j] = __uint_as_float(sw[0]);
-          v[4 + j] = __uint_as_float(sw[1]);
-        }
+        float v[8];                                        // the lane's octet (mmd_rowwave.h)
+        acc_octet(acc[a][b], j2, v);
         const int cl = a * 32 + 16 * j2 + 8 * half;        // channel inside the plane (= inside this wave column's 64)
-        const f32x4 b0 = *(const f32x4*)(sBias + wc * 64 + cl), b1 = *(const f32x4*)(sBias + wc * 64 + cl + 4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { v[j] += b0[j]; v[4 + j] += b1[j]; }
+        octet_add(v, load_octet(sBias + wc * 64 + cl));
         *(u32x4*)(tb + ((((cl >> 3)) ^ ((trow >> 1) & 7)) * 16)) = Elt<__bf16>::pack(v);
       }
     }
@@ -496,41 +486,22 @@ __global__ __launch_bounds__(512, 2) void vconv2d1d_kernel(const VConvParams p) 
 #pragma unroll
     for (int j2 = 0; j2 < 2; ++j2) {
       const int col = wc * 64 + a * 32 + 16 * j2 + 8 * half;
-      const f32x4 b0 = *(const f32x4*)(sBias + 128 + col), b1 = *(const f32x4*)(sBias + 128 + col + 4);
-      float u[4] = {0.f, 0.f, 0.f, 0.f};
+      const Octet bt = load_octet(sBias + 128 + col);
+      float u[4] = {0.f, 0.f, 0.f, 0.f};                   // one running sum over the lane's two rows (b = 0, then b = 1)
 #pragma unroll
       for (int b = 0; b < 2; ++b) {
         float v[8];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[a][b][8 * j2 + j]), __float_as_uint(acc[a][b][8 * j2 + 4 + j]), false, false);
-          v[j] = __uint_as_float(sw[0]);
-          v[4 + j] = __uint_as_float(sw[1]);
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { v[j] += b0[j]; v[4 + j] += b1[j]; }
+        acc_octet(acc[a][b], j2, v);
+        octet_add(v, bt);
         const u32x4 pk = Elt<__bf16>::pack(v);
         const int64_t m = mbase + (int64_t)(wr * 4 + b * 2 + (l31 >> 4)) * HW;
         *(u32x4*)(p.Y + (m * p.ldy + col) * 2) = pk;
-        if (p.stats) {
-          float rf[8];
-          Elt<__bf16>::unpack(pk, rf);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            u[0] += rf[j];
-            u[1] += rf[4 + j];
-            u[2] += rf[j] * rf[j];
-            u[3] += rf[4 + j] * rf[4 + j];
-          }
-        }
+        if (p.stats) quad_sums(pk, u);
       }
-      if (p.stats) {                                       // block-uniform: lanes 16 / 17 of each half hold quad 0 / 1 of the lane group's 8 channels
-        const float t0 = halfwave_total(u[0]), t1 = halfwave_total(u[1]), t2 = halfwave_total(u[2]), t3 = halfwave_total(u[3]);
-        if ((l31 >> 1) == 8) {
-          float* d = p.stats + (rec * p.stats_ld + (col >> 2) + (l31 & 1)) * 2;
-          d[0] = (l31 & 1) ? t1 : t0;
-          d[1] = (l31 & 1) ? t3 : t2;
-        }
+      if (p.stats) {                                       // block-uniform: a wave holds whole records
+        float m[2];
+        quad_fold(u, l31, m[0], m[1]);
+        if (is_record_lane(l31)) quad_put(quad_record(p.stats, rec, p.stats_ld, col, l31), m[0], m[1]);
       }
     }
   if (!has_next) break;

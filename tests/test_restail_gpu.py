@@ -113,6 +113,32 @@ def test_streamed_tail_is_bitwise_the_two_launches(ops, case, mode):
         assert _same_bits(y2, y_ref), "Y without records"
 
 
+def test_streamed_tail_follows_the_fold_of_long_samples(ops):
+    """K1 = 128 with samples of >= 16384 rows is where the out conv's record fold depends on the norm mode: with the norm fused the
+    strip GEMM holds one row fragment per wave (half records through LDS), behind gn_apply two (one running sum over rows r, r + 32).
+    The streamed launch follows each: with the affine given it meets the norm-fused strip GEMM, with a null affine the plain one behind
+    gn_apply - Y and records bit for bit.  The smallest such launch: one sample, K2 = Cout = 64 (64-column workgroups, 64-channel K steps)."""
+    S, L, K1, K2, Cout = 1, 16384, 128, 64, 64
+    h, x, w, ws, b, bs, ga, gb, geom = _operands(S, L, K1, K2, Cout, 11)
+    M = S * L
+    rec_ref = torch.full((M // 64, Cout // 4, 2), float("nan"), device="cuda")
+    assert ops.strip_tile_ok(h, Cout, stats=rec_ref, geom=geom)
+    y_ref = _two_launches(ops, h, x, w, ws, b, bs, ga, gb, geom, stats=rec_ref)      # the norm inside the strip GEMM
+    rec = torch.full_like(rec_ref, float("nan"))
+    assert ops.res_tail_ok(h, x, Cout, geom, rec)
+    y = ops.res_tail(h, ga, gb, geom, True, w, b, x, ws, bs, stats=rec)
+    assert _same_bits(y, y_ref), "Y, affine"
+    assert _same_bits(rec, rec_ref), "records, affine"
+    hn = ops.gn_apply(h, ga, gb, geom, act=True)
+    rec_ref2 = torch.full_like(rec_ref, float("nan"))
+    y_ref2 = ops.conv_gemm(hn, w, b, residual=ops.conv_gemm(x, ws, bs), tile=131, stats=rec_ref2)
+    rec2 = torch.full_like(rec_ref, float("nan"))
+    y2 = ops.res_tail(hn, None, None, geom, True, w, b, x, ws, bs, stats=rec2)
+    assert _same_bits(y2, y_ref2), "Y, prenormalised"
+    assert _same_bits(rec2, rec_ref2), "records, prenormalised"
+    assert _same_bits(y2, y_ref), "the two norm modes store the same Y"
+
+
 def test_streamed_tail_without_biases_and_without_silu(ops):
     """Null biases and act = 0 take their own paths in the prologue and the norm."""
     S, L, K1, K2, Cout = 2, 192, 384, 640, 384

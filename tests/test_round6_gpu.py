@@ -121,7 +121,10 @@ def test_attn_pipe_kernel_repeatable_under_load(ops):
 # --------------------------------------------------------------------------- audio in_layers in one launch (mmd_aconv)
 ACONV_CASES = [   # N, L, Cin, Cout, dilation
     (2, 400, 512, 512, 2), (4, 400, 1024, 512, 1), (2, 400, 512, 512, 512), (2, 1600, 384, 384, 256), (2, 1600, 896, 384, 512),
-    (1, 6400, 256, 256, 32), (2, 6400, 128, 256, 16), (1, 25600, 128, 128, 4), (1, 256, 128, 128, 8), (3, 448, 640, 256, 64)]
+    (1, 6400, 256, 256, 32), (2, 6400, 128, 256, 16), (1, 25600, 128, 128, 4), (1, 256, 128, 128, 8), (3, 448, 640, 256, 64),
+    # every row above runs 64-column workgroups (fewer than 256 workgroups of 128 columns); this one is the smallest launch of the
+    # 128-column instance: 128 row blocks x 2 column ranges
+    (2, 8192, 64, 256, 3)]
 
 
 @pytest.mark.parametrize("N,L,Cin,Cout,dil", ACONV_CASES)
