@@ -62,95 +62,13 @@ import pytest
 import torch
 
 import errbound as eb
+from errbound_expr import C32, K_EXP, K_TANH, V, cat, where          # (the class `V` of the docstring lives in tests/errbound_expr.py)
 from helpers import rel_l2
 
 pytestmark = pytest.mark.gpu
 
 U = eb.U32
 LN2 = math.log(2.0)
-K_EXP, K_TANH = 6, 10          # 3 ulp and 5 ulp, in units of U = half an ulp
-
-
-# ------------------------------------------------------------------ value + magnitude + rounding count
-class V:
-    def __init__(self, v, m=None, n=0):
-        self.v = torch.as_tensor(v, dtype=torch.float64)
-        self.m = self.v.abs() if m is None else m
-        self.n = n
-
-    @staticmethod
-    def of(x):
-        return x if isinstance(x, V) else V(x)
-
-    def bound(self):
-        return self.n * U * self.m
-
-    def _sum(self, o, v):
-        exact = self.n == 0 and o.n == 0          # one rounding of the result of two exact operands: U |v|, not U (|a| + |b|)
-        return V(v, v.abs() if exact else self.m + o.m, self.n + o.n + 1)
-
-    def __add__(self, o):
-        o = V.of(o)
-        return self._sum(o, self.v + o.v)
-
-    __radd__ = __add__
-
-    def __sub__(self, o):
-        o = V.of(o)
-        return self._sum(o, self.v - o.v)
-
-    def __rsub__(self, o):
-        return V.of(o) - self
-
-    def __neg__(self):
-        return V(-self.v, self.m, self.n)
-
-    def __mul__(self, o):
-        o = V.of(o)
-        return V(self.v * o.v, self.m * o.m, self.n + o.n + 1)
-
-    __rmul__ = __mul__
-
-    def __truediv__(self, o):
-        o = V.of(o)
-        amp = torch.where(o.v == 0, torch.ones_like(o.m), o.m / o.v.abs())
-        return V(self.v / o.v, self.m / o.v.abs() * amp, self.n + o.n + 1)
-
-    def exact(self, c):
-        """times a power of two"""
-        return V(self.v * c, self.m * abs(c), self.n)
-
-    def sqrt(self):
-        r = self.v.sqrt()
-        return V(r, torch.where(self.v == 0, self.m, r * self.m / self.v.abs().clamp_min(1e-300)), self.n + 1)
-
-    def exp(self):
-        r = self.v.exp()
-        return V(r, r * self.m.clamp_min(1.0), self.n + K_EXP)
-
-    def tanh(self):
-        r = self.v.tanh()
-        return V(r, (1 - r * r) * self.m + r.abs(), self.n + K_TANH)
-
-    def clamp(self, lo, hi):
-        return V(self.v.clamp(lo, hi), self.m, self.n)
-
-    def expand_as(self, t):
-        return V(self.v.expand_as(t), self.m.expand_as(t), self.n)
-
-
-def C32(c):
-    """a constant the kernel holds in fp32: within one rounding of the double the oracle uses"""
-    return V(c, n=1)
-
-
-def where(mask, a, b):
-    a, b = V.of(a), V.of(b)
-    return V(torch.where(mask, a.v, b.v), torch.where(mask, a.m, b.m), max(a.n, b.n))
-
-
-def cat(a, b, dim):
-    return V(torch.cat([a.v, b.v], dim), torch.cat([a.m, b.m], dim), max(a.n, b.n))
 
 
 # ------------------------------------------------------------------ schedule, tables, inputs
