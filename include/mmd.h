@@ -401,7 +401,8 @@ int mmd_ddim_update(const float* x, const float* model_out, const float* noise, 
  *   c0 = r >> 2   r = the element's index inside its sample in API layout ([F,C,H,W] video, [C,L] audio, [C,H,W] SR image)
  *   c1 = draw     the loop index t[n] the update kernels read (SpacedDiffusion: the respaced index); 0xFFFFFFFF = x_T; the resampled
  *                 masked loop hands its draws in (mmd_ddpm_update_ctr_at, mmd_renoise_ctr): i + r T for visit r of step i, 0x80000000 + k
- *                 for the k-th forward jump
+ *                 for the k-th forward jump; the stochastic solver step (mmd_dpmpp_sde_update_ctr) draws at the evaluation number k[n], the
+ *                 table row it reads anyway (below 2^31, like the loop indices)
  *   c2 = sample id  ids[n] (device int64 [N]); the low 32 bits are used and the HOST refuses ids outside [0, 2^32) (mm_diffusion/seeded.py:
  *                 the library cannot look into device memory without a sync)
  *   c3 = tag      0 video, 1 audio, 2 SR image, 3 window shifts (host only)
@@ -488,6 +489,28 @@ int mmd_dpmpp_x0(const float* x, const float* model_out, float* x0raw, const flo
 int mmd_dpmpp_select(const float* x, void* workspace, int level0_done, int N, int64_t per_sample, float q, float* out, void* stream);
 int mmd_dpmpp_update(float* x, const float* m0, float* M1, const float* s, float max_val, const float* tab, const int64_t* k, int rows, int N,
                      int F, int C, int Cm, int HW, void* stream);
+/* One evaluation of the stochastic multistep solver in its data-prediction form (SDE-DPM-Solver++, Lu et al. 2022, "DPM++ 2M SDE" in
+ * other toolkits; orders 1 and 2): mmd_dpmpp_update with a noise term.  tab, k, rows, the kinds and the geometry are mmd_dpmpp_update's
+ * (tab fp32 [6][rows], layout unchanged); cz: fp32 [rows], the noise coefficient of each row.  With h = lambda_t - lambda_s > 0 and
+ * E = -expm1(-2 h) the host fills c0 = (sigma_t / sigma_s) e^-h, c1 + c2 = alpha_t E (second order: c1 = alpha_t E (1 + 1 / (2 r0)),
+ * c2 = -alpha_t E / (2 r0)), cz = sigma_t sqrt(E), so that c0 alpha_s + c1 + c2 = alpha_t and c0^2 sigma_s^2 + cz^2 = sigma_t^2: a
+ * perfect data prediction keeps the marginal N(alpha_t mu, sigma_t^2) at any step size.  In place, by the row's kind:
+ *   0  x = c0 x + c1 m0 + cz z (M1 is not read)     1  x = c0 x + c1 m0 + c2 M1 + cz z     2  x = m0 (no noise is read, no Philox evaluated)
+ * and M1 = m0; m0 is clamp-scaled by s[n] first when s != NULL.  The sums are mmd_lincomb's, term by term in that order (one rounded
+ * product, then one fma per further term, the noise last): bitwise mmd_clamp_scale + mmd_lincomb(x, c0, m0, c1, M1, c2) +
+ * mmd_lincomb(v, 1, z, cz).  A sample whose k is outside [0, rows) writes nothing: not x, not M1.
+ *   mmd_dpmpp_sde_update      z = noise[i], fp32 [N,F,C,HW].  x, M1 and noise must not overlap (checked).
+ *   mmd_dpmpp_sde_update_ctr  z = the counter normal above with c1 (draw) = the low 32 bits of k[n], c2 = ids[n], c3 = tag, c0 = the
+ *                             element's index inside its sample >> 2: bitwise mmd_ctr_fill(draw = k) followed by the memory form, and
+ *                             no noise buffer exists.
+ * A thread owns one quad of consecutive elements of a sample in both forms: 16-byte loads and stores where the quad is whole and its
+ * address a multiple of 16, element by element otherwise (a ragged last quad; words past the end of a sample are dropped).  No LDS, no
+ * library state. */
+int mmd_dpmpp_sde_update(float* x, const float* m0, float* M1, const float* noise, const float* s, float max_val, const float* tab,
+                         const float* cz, const int64_t* k, int rows, int N, int F, int C, int Cm, int HW, void* stream);
+int mmd_dpmpp_sde_update_ctr(float* x, const float* m0, float* M1, const uint32_t* key, const int64_t* ids, int tag, const float* s,
+                             float max_val, const float* tab, const float* cz, const int64_t* k, int rows, int N, int F, int C, int Cm,
+                             int HW, void* stream);
 /* One evaluation of the single-step DPM-Solver / DPM-Solver++ loop (multimodal_dpm_solver_plus.py:1277-1294; orders 1-3, dpm:532-887)
  * from the same kind of table (fp32 [6][rows] = cx, ce, c0, c1, c2, kind; k as above; a sample whose k is outside [0, rows) writes
  * nothing: not x, not XB, not MS).  A step of order p is p evaluations; its later stages combine the state and the model value at the

@@ -61,7 +61,7 @@ __device__ __forceinline__ R post_mean(const PostCoef<R>& q, R x0, R xv) { retur
 // with the 64-bit seed (low word first) on the counter
 //   c0 = r >> 2   r = the element's index inside its sample in API layout     c1 = draw (the loop index t[n]; 0xFFFFFFFF = x_T)
 //                 resampled loops (mmd_ddpm_update_ctr_at, mmd_renoise_ctr) hand the draw in: visit r of step i of T draws i + r T (< 2^31),
-//                 the k-th forward jump 0x80000000 + k
+//                 the k-th forward jump 0x80000000 + k; the stochastic solver step (mmd_dpmpp_sde_update_ctr) draws at its evaluation number k[n]
 //   c2 = sample id (low 32 bits of ids[n]; the host refuses ids outside [0, 2^32))   c3 = tag (0 video, 1 audio, 2 SR image, 3 shifts)
 // The four output words belong to elements 4 c0 ... 4 c0 + 3; words past the end of a sample are dropped.  Nothing in the counter
 // depends on the batch position, the batch size, the lane or the rank.  Word w -> u = ((w >> 9) + 0.5) 2^-23, exact in fp32 and inside
@@ -1184,4 +1184,134 @@ extern "C" int mmd_dpm_single_update(float* x, const float* src, int form, float
   const dim3 grid(ew_grid(total));
   if (form == 1) return mmd_launch<dpm_single_update_kernel<true>>("dpm_single_update", grid, dim3(256), 0, (hipStream_t)stream, p, t, x, XB, MS, s, max_val);
   return mmd_launch<dpm_single_update_kernel<false>>("dpm_single_update", grid, dim3(256), 0, (hipStream_t)stream, p, t, x, XB, MS, s, max_val);
+}
+
+// ----------------------------------------------------------------------------- SDE-DPM-Solver++ multistep step, graph form
+// One evaluation of the stochastic data-prediction multistep solver (Lu et al., DPM-Solver++ 2022, the "SDE-DPM-Solver++(2M)" update;
+// DPM_Solver.sample_graph_sde) from mmd_dpmpp_update's table plus cz fp32 [rows], the noise coefficient of the row:
+//   kind 0  x = c0 x + c1 m0 + cz z        1  x = c0 x + c1 m0 + c2 M1 + cz z        2  x = m0 (no noise is read or drawn)
+// and M1 = m0.  mmd_lincomb's terms in that order, so the result is bitwise mmd_clamp_scale + mmd_lincomb(x, c0, m0, c1, M1, c2) +
+// mmd_lincomb(v, 1, z, cz).  z = noise[i], or the counter normal of (element, draw = the low 32 bits of k[n], ids[n], tag): the value
+// mmd_ctr_fill(draw = k) gives the element.  A thread owns one quad of consecutive elements of a sample in both forms; the quad moves as
+// 16 bytes where it is whole and its address is a multiple of 16 (x, M1 and the noise share one offset; in the model output a quad is
+// contiguous while it stays inside one (frame, channel) row), else element by element - a sample of 6147 elements has a ragged last
+// quad and, from the second sample on, no aligned one.
+struct DpmppSdeParams {
+  float* x; float* M1; const float* s; const float* cz;
+  float max_val;
+  int vec;      // bit 0: x, M1 (and the noise) start on 16 bytes, bit 1: the model output does
+};
+struct SdeNoiseFromMemory {
+  const float* noise;
+  __device__ __forceinline__ void draw(int64_t, int64_t, int64_t i0, uint32_t, int cnt, bool vec, float* z) const {
+    if (vec) {
+      const float4 q = *reinterpret_cast<const float4*>(noise + i0);
+      z[0] = q.x; z[1] = q.y; z[2] = q.z; z[3] = q.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (j < cnt) z[j] = noise[i0 + j];
+    }
+  }
+};
+struct SdeNoiseFromCounter {
+  CtrKey k;
+  __device__ __forceinline__ void draw(int64_t n, int64_t r0, int64_t, uint32_t d, int, bool, float* z) const { ctr_normals(k, n, r0, d, z); }
+};
+__device__ __forceinline__ void quad_load(const float* p, int cnt, bool vec, float* v) {
+  if (vec) {
+    const float4 q = *reinterpret_cast<const float4*>(p);
+    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (j < cnt) v[j] = p[j];
+  }
+}
+__device__ __forceinline__ void quad_store(float* p, int cnt, bool vec, const float* v) {
+  if (vec) {
+    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (j < cnt) p[j] = v[j];
+  }
+}
+template <class Src>
+__global__ __launch_bounds__(256) void dpmpp_sde_update_kernel(const DiffusionParams p, const DpmppTab t, const DpmppSdeParams q, const Src src) {
+  const int64_t per = (int64_t)p.F * p.C * p.HW;
+  const int64_t ups = (per + 3) / 4, total = ups * p.N;
+  for (int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x; u < total; u += (int64_t)gridDim.x * 256) {
+    const int64_t n = u / ups, r0 = (u % ups) * 4;
+    const int64_t ki = t.k[n];
+    if (ki < 0 || ki >= t.rows) continue;
+    const float c0 = t.tab[2 * t.rows + ki], c1 = t.tab[3 * t.rows + ki], c2 = t.tab[4 * t.rows + ki], cz = q.cz[ki];
+    const int kind = (int)t.tab[5 * t.rows + ki];
+    const int cnt = per - r0 < 4 ? (int)(per - r0) : 4;
+    const int64_t i0 = n * per + r0;
+    const bool vx = cnt == 4 && (q.vec & 1) && !(i0 & 3);
+    float m0[4] = {}, v[4] = {}, m1[4] = {}, z[4] = {};
+    const ElemAddr a0 = elem_addr(p, n, r0);
+    if (cnt == 4 && (q.vec & 2) && !(a0.mean & 3) && (int)(r0 % p.HW) + 4 <= p.HW) {
+      quad_load(p.mo + a0.mean, 4, true, m0);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (j < cnt) m0[j] = p.mo[elem_addr(p, n, r0 + j).mean];
+    }
+    if (q.s) {
+      const float sv = q.s[n];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) m0[j] = clamp_scale_elem(m0[j], sv, q.max_val);
+    }
+    if (kind == 2) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = m0[j];
+    } else {
+      quad_load(q.x + i0, cnt, vx, v);
+      if (kind == 1) quad_load(q.M1 + i0, cnt, vx, m1);
+      src.draw(n, r0, i0, (uint32_t)ki, cnt, vx, z);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float w = lincomb_add(lincomb_first(c0, v[j]), c1, m0[j]);
+        if (kind == 1) w = lincomb_add(w, c2, m1[j]);
+        v[j] = lincomb_add(w, cz, z[j]);
+      }
+    }
+    quad_store(q.x + i0, cnt, vx, v);
+    quad_store(q.M1 + i0, cnt, vx, m0);
+  }
+}
+
+static bool on16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+static int dpmpp_sde_args(const char* what, const float* x, const float* m0, const float* M1, const float* s, float max_val, const float* tab,
+                          const float* cz, const int64_t* k, int rows, int N, int F, int C, int Cm, int HW) {
+  MMD_REQUIRE(x && m0 && M1 && tab && k, "%s: needs x, m0, M1, the table and the step numbers", what);
+  MMD_REQUIRE(cz, "%s: needs cz, the noise coefficient of every row", what);
+  MMD_REQUIRE(!s || max_val > 0.f, "%s: max_val must be positive with thresholding (s != NULL)", what);
+  return dpmpp_geom_ok(what, rows, N, F, C, Cm, HW);
+}
+extern "C" int mmd_dpmpp_sde_update(float* x, const float* m0, float* M1, const float* noise, const float* s, float max_val, const float* tab,
+                                    const float* cz, const int64_t* k, int rows, int N, int F, int C, int Cm, int HW, void* stream) {
+  if (int rc = dpmpp_sde_args("dpmpp_sde_update", x, m0, M1, s, max_val, tab, cz, k, rows, N, F, C, Cm, HW)) return rc;
+  MMD_REQUIRE(noise, "dpmpp_sde_update: needs the noise (the counter form draws it: mmd_dpmpp_sde_update_ctr)");
+  const int64_t per = (int64_t)F * C * HW, total = per * N;
+  MMD_REQUIRE(dpm_disjoint(x, M1, total) && dpm_disjoint(x, noise, total) && dpm_disjoint(M1, noise, total),
+              "dpmpp_sde_update: x, M1 and noise must not overlap (x and M1 are written in place)");
+  const DiffusionParams p{nullptr, m0, nullptr, nullptr, 0, N, F, C, HW, Cm == C ? 0 : 4};
+  const DpmppSdeParams q{x, M1, s, cz, max_val, (on16(x) && on16(M1) && on16(noise) ? 1 : 0) | (on16(m0) ? 2 : 0)};
+  return mmd_launch<dpmpp_sde_update_kernel<SdeNoiseFromMemory>>("dpmpp_sde_update", dim3(ew_grid((per + 3) / 4 * N)), dim3(256), 0, (hipStream_t)stream, p,
+                                                                 DpmppTab{tab, k, rows}, q, SdeNoiseFromMemory{noise});
+}
+extern "C" int mmd_dpmpp_sde_update_ctr(float* x, const float* m0, float* M1, const uint32_t* key, const int64_t* ids, int tag, const float* s,
+                                        float max_val, const float* tab, const float* cz, const int64_t* k, int rows, int N, int F, int C, int Cm,
+                                        int HW, void* stream) {
+  if (int rc = dpmpp_sde_args("dpmpp_sde_update_ctr", x, m0, M1, s, max_val, tab, cz, k, rows, N, F, C, Cm, HW)) return rc;
+  MMD_REQUIRE(ctr_args_ok(key, ids, tag), "dpmpp_sde_update_ctr: needs the key, the sample ids and a stream tag in [0, 3]");
+  const int64_t per = (int64_t)F * C * HW;
+  MMD_REQUIRE(dpm_disjoint(x, M1, per * N), "dpmpp_sde_update_ctr: x and M1 must not overlap (both are written in place)");
+  const DiffusionParams p{nullptr, m0, nullptr, nullptr, 0, N, F, C, HW, Cm == C ? 0 : 4};
+  const DpmppSdeParams q{x, M1, s, cz, max_val, (on16(x) && on16(M1) ? 1 : 0) | (on16(m0) ? 2 : 0)};
+  return mmd_launch<dpmpp_sde_update_kernel<SdeNoiseFromCounter>>("dpmpp_sde_update_ctr", dim3(ew_grid((per + 3) / 4 * N)), dim3(256), 0, (hipStream_t)stream,
+                                                                  p, DpmppTab{tab, k, rows}, q, SdeNoiseFromCounter{{key, ids, tag}});
 }

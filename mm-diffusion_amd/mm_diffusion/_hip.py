@@ -122,6 +122,8 @@ _PROTOS = {
     "mmd_dpmpp_select": (i32, [vp, vp, i32, i32, i64, f32, vp, vp]),
     "mmd_dpmpp_update": (i32, [vp, vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "mmd_dpm_single_update": (i32, [vp, vp, i32, vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "mmd_dpmpp_sde_update": (i32, [vp, vp, vp, vp, vp, f32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "mmd_dpmpp_sde_update_ctr": (i32, [vp, vp, vp, vp, vp, i32, vp, f32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
 }
 EXPORTS = tuple(_PROTOS)
 

@@ -18,7 +18,10 @@ one evaluation is one graph replay per lane (sampler.DpmppStepper: mmd_dpmpp_x0 
 eager loop, with batch lanes, seeded.CounterNoise and the partial masks of masked_sample_loop.  `DPM_Solver.sample_graph_singlestep`
 does the same for the single-step method of orders 1-3 (the reference sampling script's call): `singlestep_tables` has one row per network
 evaluation - a step of order p is p rows, at s, s1 and s2 - and the recorded update is mmd_dpm_single_update (sampler.DpmSingleStepper).
-The two share one driver (`_graph_loop`) and the stepper kept from the last call.
+`DPM_Solver.sample_graph_sde` is the stochastic multistep solver in its data-prediction form (SDE-DPM-Solver++, orders 1 and 2; eager:
+sample(method="multistep_sde")): `sde_tables` adds a noise coefficient per row, the recorded update mmd_dpmpp_sde_update draws or reads a
+fresh z ~ N(0, I) inside the step graph (sampler.DpmppSdeStepper).  Generation quality is not assessed: there are no trained weights.
+The three share one driver (`_graph_loop`) and the stepper kept from the last call.
 
 Reference behaviours reproduced knowingly:
   * the noise-prediction first-order update moves the AUDIO stream with the x0-form coefficients
@@ -383,6 +386,23 @@ class DPM_Solver:
             cd = -0.5 * _f(sig_t * (torch.exp(h) - 1.))
         return c0, c1 + cd * inv_r0, -cd * inv_r0
 
+    def _sde_coefs(self, t_prev_1, s, t):
+        """(c0, c1, c2, cz) of the stochastic data-prediction update s -> t (SDE-DPM-Solver++, Lu et al. 2022): x_t = c0 x_s + c1 m0 + c2 m1
+        + cz z with h = lambda_t - lambda_s, E = -expm1(-2 h): c0 = (sigma_t / sigma_s) e^-h, cm = alpha_t E, cz = sigma_t sqrt(E); first
+        order (t_prev_1 None) c1 = cm, c2 = 0; second order, r0 = (lambda_s - lambda_prev) / h: c1 = cm (1 + 1 / (2 r0)), c2 = -cm / (2 r0).
+        So c0 alpha_s + c1 + c2 = alpha_t and c0^2 sigma_s^2 + cz^2 = sigma_t^2: a perfect data prediction keeps the marginal.  Formed in
+        float64 from _sc()'s fp32 values, each coefficient rounded to fp32 once."""
+        import numpy as np
+        (lam_s, _, sig_s), (lam_t, la_t, sig_t) = (tuple(float(v.reshape(-1)[0]) for v in sc) for sc in self._sc(s, t))
+        h = lam_t - lam_s
+        E = -math.expm1(-2. * h)
+        c0, cm, cz = sig_t / sig_s * math.exp(-h), math.exp(la_t) * E, sig_t * math.sqrt(E)
+        c1, c2 = cm, 0.
+        if t_prev_1 is not None:
+            r0 = (lam_s - float(self._sc(t_prev_1)[0][0].reshape(-1)[0])) / h
+            c1, c2 = cm * (1. + 0.5 / r0), -cm * 0.5 / r0
+        return tuple(float(np.float32(v)) for v in (c0, c1, c2, cz))
+
     @staticmethod
     def _ratio(r):
         """a step ratio r1 / r2 (host tensor of sample(), or a number) as a host fp32 tensor [1]."""
@@ -568,9 +588,15 @@ class DPM_Solver:
 
     # ------------------------------------------------------------------ driver
     def sample(self, x, steps=20, t_start=None, t_end=None, order=3, skip_type="time_uniform", method="singlestep", denoise=False,
-               solver_type="dpm_solver", atol=0.0078, rtol=0.05):
+               solver_type="dpm_solver", atol=0.0078, rtol=0.05, noise_source=None):
+        """method "multistep_sde": the stochastic data-prediction multistep solver of orders 1 and 2 (_sample_sde); noise_source (that
+        method only): None = torch.randn, or a seeded.CounterNoise."""
         t_0 = 1. / self.noise_schedule.total_N if t_end is None else t_end
         t_T = self.noise_schedule.T if t_start is None else t_start
+        if method == "multistep_sde":
+            return self._sample_sde(x, steps, order, skip_type, denoise, solver_type, t_T, t_0, noise_source)
+        if noise_source is not None:
+            raise H.MMDError(f"sample: method {method!r} is deterministic and draws nothing: noise_source goes with 'multistep_sde' only")
         x = self._prep(x)
         device, B = x[self.KEYS[0]].device, self._batch(x)
         with torch.no_grad():
@@ -610,6 +636,119 @@ class DPM_Solver:
         if denoise:
             x = self.denoise_fn(x, torch.ones((B,)) * t_0)
         return x
+
+    # ------------------------------------------------------------------ stochastic multistep solver (SDE-DPM-Solver++)
+    def _sde_check(self, who, steps, order, solver_type="dpm_solver"):
+        if not self.predict_x0:
+            raise H.MMDError(f"{who}: the stochastic solver is built in its data-prediction form only (predict_x0=True): the reference's "
+                             "noise-prediction first update moves the audio stream with x0-form coefficients (dpm:576-584), and that form does "
+                             "not keep the marginal")
+        if order not in (1, 2):
+            raise H.MMDError(f"{who}: order must be 1 or 2 (no third-order stochastic update is built); got {order}")
+        if solver_type != "dpm_solver":
+            raise H.MMDError(f"{who}: solver_type must be 'dpm_solver' (the stochastic update has one form), got {solver_type!r}")
+        steps = int(steps)
+        if steps < order:
+            raise H.MMDError(f"{who}: steps ({steps}) must be at least the order ({order})")
+        return steps
+
+    def multistep_sde_update(self, x, m0, m1, coefs, z):
+        """x_t = c0 x + c1 m0 (+ c2 m1) + cz z per stream from the kernels of the deterministic updates: one mmd_lincomb for the
+        deterministic terms (m1 None: first order), then mmd_lincomb(v, 1, z, cz).  coefs = _sde_coefs' tuple, z = {stream: N(0, 1)}."""
+        c0, c1, c2, cz = coefs
+        x = self._prep(x)
+        out = {}
+        for k in self.KEYS:
+            v = _comb([(c0, x[k]), (c1, m0[k])] + ([(c2, m1[k])] if m1 is not None else []))
+            out[k] = ops.lincomb(v, 1.0, z[k].float().contiguous(), cz)
+        return out
+
+    def _sample_sde(self, x, steps, order, skip_type, denoise, solver_type, t_T, t_0, noise_source):
+        """sample(method="multistep_sde"): the multistep loop's structure with a fresh z ~ N(0, I) at every update - torch.randn, video
+        first, then audio, or noise_source.randn(shape, tag, draw=i) of a seeded.CounterNoise at evaluation i, whose window shifts then
+        come from the counter too (x is expected to be its X_T draw) - and none at the closing denoise evaluation."""
+        from .seeded import CounterNoise, TAG_AUDIO, TAG_VIDEO
+        steps = self._sde_check("sample(method='multistep_sde')", steps, order, solver_type)
+        if self.KEYS != ("video", "audio"):
+            raise H.MMDError("sample(method='multistep_sde'): the stochastic solver is built for the multimodal base model's "
+                             "{'video', 'audio'} state only")
+        ctr = noise_source
+        if ctr is not None and not isinstance(ctr, CounterNoise):
+            raise H.MMDError("sample(method='multistep_sde'): noise_source must be a seeded.CounterNoise or None")
+        tags = {"video": TAG_VIDEO, "audio": TAG_AUDIO}
+        x = self._prep(x)
+        device, B = x[self.KEYS[0]].device, self._batch(x)
+        def evaluate(fn, x, i, t):      # evaluation i: with a counter its window shifts are the counter's at draw i
+            if ctr is None:
+                return fn(x, t)
+            ctr.set_draw(i)
+            with ctr.shifting(self.raw_model):
+                return fn(x, t)
+        with torch.no_grad():
+            timesteps = self.get_time_steps(skip_type=skip_type, t_T=t_T, t_0=t_0, N=steps, device="cpu")
+            m1 = None
+            for i in range(steps):
+                m0 = evaluate(self.model_fn, x, i, timesteps[i].expand(B))
+                second = order == 2 and i > 0
+                coefs = self._sde_coefs(timesteps[i - 1:i] if second else None, timesteps[i:i + 1], timesteps[i + 1:i + 2])
+                if ctr is not None:
+                    z = {k: ctr.randn(tuple(x[k].shape), tags[k], i, device) for k in self.KEYS}
+                else:
+                    z = {k: torch.randn(tuple(x[k].shape), device=device) for k in self.KEYS}
+                x = self.multistep_sde_update(x, m0, m1 if second else None, coefs, z)
+                m1 = m0
+            if denoise:
+                x = evaluate(self.denoise_fn, x, steps, torch.ones((B,)) * t_0)
+        return x
+
+    def sde_tables(self, steps, order=2, skip_type="logSNR", denoise=False, device="cpu"):
+        """graph_tables' dictionary for sample_graph_sde, plus "cz": {stream: float32 [rows]}, the noise coefficient of each row (0 at the
+        denoise row).  Rows and kinds as in graph_tables - row 0 first order, the denoise row last - with c0, c1, c2, cz from _sde_coefs,
+        the helper the eager method calls."""
+        import numpy as np
+        steps = self._sde_check("sde_tables", steps, order)
+        key = (steps, order, skip_type, bool(denoise), str(device))
+        cache = self.__dict__.setdefault("_sde_tables", {})
+        if key not in cache:
+            cache[key] = self._build_sde_tables(np, steps, order, skip_type, denoise, device)
+        return cache[key]
+
+    def _build_sde_tables(self, np, steps, order, skip_type, denoise, device):
+        t_0, t_T = 1. / self.noise_schedule.total_N, self.noise_schedule.T
+        grid = self.get_time_steps(skip_type=skip_type, t_T=t_T, t_0=t_0, N=steps, device="cpu")
+        times = [grid[i:i + 1] for i in range(steps + 1)]
+        evals = times[:steps] + ([torch.ones((1,)) * t_0] if denoise else [])
+        rows = len(evals)
+        tab = {k: np.zeros((ops.DPMPP_TAB_ROWS, rows), dtype=np.float32) for k in self.KEYS}
+        cz = {k: np.zeros(rows, dtype=np.float32) for k in self.KEYS}
+        tab2 = np.zeros((2, rows), dtype=np.float32)
+        for i, t in enumerate(evals):
+            tab2[:, i] = self._alpha_sigma(t)
+            if i == steps:
+                c, z = (0.0, 0.0, 0.0, ops.DPMPP_KIND_DENOISE), 0.0
+            else:
+                second = order == 2 and i > 0
+                c0, c1, c2, z = self._sde_coefs(times[i - 1] if second else None, times[i], times[i + 1])
+                c = (c0, c1, c2, ops.DPMPP_KIND_SECOND if second else ops.DPMPP_KIND_FIRST)
+            for k in self.KEYS:
+                tab[k][:, i] = self._x0_coefs(t) + c
+                cz[k][i] = z
+        tm = self.model.get_model_input_time(torch.cat(evals).to(device))
+        return {"rows": rows, "timesteps": torch.cat(evals), "tab": tab, "tab2": tab2, "cz": cz, "tm": [int(v) for v in tm.cpu()]}
+
+    def sample_graph_sde(self, x_T=None, *, shape=None, steps, order=2, skip_type="logSNR", denoise=False, known=None, mask=None,
+                         noise_source=None, paste_known=True, use_graph=True, lanes=None):
+        """sample(method="multistep_sde") as one graph replay per lane and evaluation (sampler.DpmppSdeStepper, the tables of sde_tables):
+        the same x_T, window-shift stream and torch device seed give the same bits.  The update draws its noise inside the step graph:
+        with a seeded.CounterNoise in the kernel, at draw = the evaluation number (sample k of a seed is then the same at any batch and
+        lane count, on the graph and the eager path), else from full-batch buffers refilled before every update row in the eager order.
+        x_T / shape, known / mask / paste_known, use_graph and lanes as in sample_graph: the known cells are set to alpha(t) known +
+        sigma(t) eps (eps = that stream's x_T) before every evaluation, so the unknown part is re-randomised at every step around them.
+        Data prediction (predict_x0=True), orders 1 and 2; batch 1 is accepted."""
+        from .sampler import DpmppSdeStepper
+        return self._graph_loop("sample_graph_sde", DpmppSdeStepper, lambda: self._sde_check("sample_graph_sde", steps, order),
+                                lambda device: self.sde_tables(steps, order, skip_type, denoise, device=device),
+                                x_T, shape, known, mask, noise_source, paste_known, use_graph, lanes)
 
     # ------------------------------------------------------------------ graph-replayed multistep loop
     def graph_tables(self, steps, order=2, skip_type="logSNR", solver_type="dpm_solver", denoise=False, device="cpu"):

@@ -1300,6 +1300,33 @@ def dpmpp_update(x, m0, M1, tab, k, F, C, Cm, HW, s=None, max_val=1.0):
     return x
 
 
+def dpmpp_sde_update(x, m0, M1, tab, cz, k, F, C, Cm, HW, noise=None, ctr=None, s=None, max_val=1.0):
+    """dpmpp_update with the row's noise term: in place x = c0[k] x + c1[k] m0 (+ c2[k] M1) + cz[k] z by the row's kind (the denoise row
+    takes no noise), M1 = m0 (include/mmd.h: mmd_dpmpp_sde_update).  cz: fp32 [rows], one per table row.  Exactly one noise source:
+    noise = fp32 [N,F,C,HW], or ctr = (key, ids, tag): z is drawn in the kernel at draw = k[n] (mmd_dpmpp_sde_update_ctr)."""
+    if (noise is None) == (ctr is None):
+        raise H.MMDError("dpmpp_sde_update: give exactly one of noise and ctr=(key, ids, tag)")
+    key, ids, tag = ctr if ctr is not None else (None, None, 0)
+    H.require_cuda(x, m0, M1, tab, cz, k, s, noise, key, ids)
+    N = x.shape[0]
+    _dpmpp_args("dpmpp_sde_update", tab, k, N, (("x", x), ("m0", m0), ("M1", M1), ("s", s), ("cz", cz), ("noise", noise)))
+    if cz.numel() != tab.shape[1]:
+        raise H.MMDError(f"dpmpp_sde_update: cz must hold one coefficient per table row ({tab.shape[1]}), got {cz.numel()}")
+    if x.numel() != N * F * C * HW or M1.numel() != x.numel() or m0.numel() != N * F * Cm * HW or (s is not None and s.numel() != N) or \
+            (noise is not None and noise.numel() != x.numel()):
+        raise H.MMDError(f"dpmpp_sde_update: x / M1 / noise must hold N F C HW = {N * F * C * HW}, m0 N F Cm HW = {N * F * Cm * HW} elements and s "
+                         "one per sample")
+    if ctr is None:
+        _dispatch("mmd_dpmpp_sde_update", x.data_ptr(), m0.data_ptr(), M1.data_ptr(), noise.data_ptr(), H.ptr(s), float(max_val), tab.data_ptr(),
+                  cz.data_ptr(), k.data_ptr(), tab.shape[1], N, F, C, Cm, HW, meta=("dpmpp_sde_update", 0, 24 * x.numel()))
+    else:
+        _per_sample_i64("dpmpp_sde_update", "ids", ids, N)
+        _dispatch("mmd_dpmpp_sde_update_ctr", x.data_ptr(), m0.data_ptr(), M1.data_ptr(), key.data_ptr(), ids.data_ptr(), int(tag), H.ptr(s),
+                  float(max_val), tab.data_ptr(), cz.data_ptr(), k.data_ptr(), tab.shape[1], N, F, C, Cm, HW,
+                  meta=("dpmpp_sde_update_ctr", 0, 20 * x.numel()))
+    return x
+
+
 DPM1_KIND_OPEN, DPM1_KIND_STAGE, DPM1_KIND_DENOISE = 0, 1, 2      # row kinds of mmd_dpm_single_update (include/mmd.h)
 
 

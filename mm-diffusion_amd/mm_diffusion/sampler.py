@@ -10,7 +10,7 @@ the timestep_map tensor rebuild, ~16 table uploads and ~55k ATen dispatches.
 Structure: LaneStepper owns what every replayed step shares - the batch lanes and their engines, the conditioning buffers and the
 pre-plan that replaces the known cells, the per-step uploads, the lane events, and capture / launch / close over NAMED PLAN SETS
 (name -> per-lane plans behind the U-Net plan, and their per-lane graph execs once captured).  GraphStepper (DDPM / DDIM / variational
-bound) and SolverStepper (DPM-Solver / DPM-Solver++: DpmppStepper multistep, DpmSingleStepper single-step) record their update plans into
+bound) and SolverStepper (DPM-Solver / DPM-Solver++: DpmppStepper multistep, DpmSingleStepper single-step, DpmppSdeStepper stochastic multistep) record their update plans into
 sets and say, in set_step, which set the next launch replays.  A set may be `bare`: launched without the pre-plan and the U-Net plan (the
 forward jump of masked sampling with resampling, GraphStepper.jump)."""
 import ctypes
@@ -507,6 +507,7 @@ class SolverStepper(LaneStepper):
         self.retable(tabs, ctr)
         self._record_cond(cond, self._qtab)
         n, e = self.n, self.eng
+        self._prepare()
         geom = {"video": (e.F, e.Cv_in, unet.video_out_channels, e.H0 * e.W0), "audio": (1, e.Ca_in, unet.audio_out_channels, e.L0)}
         self.predict_x0 = predict_x0 = bool(solver.predict_x0)
         thresholding, max_val = bool(solver.thresholding), float(solver.max_val)
@@ -519,7 +520,7 @@ class SolverStepper(LaneStepper):
             streams = []
             for sid, k, xk, ok in ((0, "video", e.x_video, e.out_video), (1, "audio", e.x_audio, e.out_audio)):
                 buf = dict(self._history(xk), x0=th.empty_like(xk), s=th.zeros(n, dtype=th.float32, device=self.device),
-                           ws=ops.dpmpp_workspace(n, self.device))
+                           ws=ops.dpmpp_workspace(n, self.device), lane=r, stream=k)
                 self._bufs.append(buf)
                 streams.append((sid, k, xk, ok, buf))
 
@@ -546,13 +547,16 @@ class SolverStepper(LaneStepper):
                 self.final_plans.append(record(True))
         self.update_plan = self.update_plans[0]
 
+    def _prepare(self):
+        """Allocate what the recorded updates read besides the tables and the histories (before anything is recorded)."""
+
     def _history(self, xk):
         """{name: buffer}: what the update keeps of one stream between evaluations."""
         raise NotImplementedError
 
     def _update(self, x, src, x0_form, b, tab, t_idx, F, C, Cm, HW, s, max_val):
         """Record the update of one stream from m0 = the first C of src's Cm channels, clamp-scaled by s if given; x0_form (FUSED_X0
-        only): src is the model output and m0 its data prediction."""
+        only): src is the model output and m0 its data prediction.  b: the stream's buffers, with its lane (b["lane"]) and key (b["stream"])."""
         raise NotImplementedError
 
     def retable(self, tabs, ctr=None):
@@ -617,3 +621,48 @@ class DpmSingleStepper(SolverStepper):
     def _update(self, x, src, x0_form, b, tab, t_idx, F, C, Cm, HW, s, max_val):
         ops.dpm_single_update(x, src, b["xb"], b["ms"], tab, t_idx, F, C, Cm, HW, form=1 if x0_form else 0, s=s, max_val=max_val)
 
+
+
+class DpmppSdeStepper(SolverStepper):
+    """The stochastic multistep loop of the data-prediction solver (DPM_Solver.sample_graph_sde, SDE-DPM-Solver++ of orders 1 and 2): per
+    stream [mmd_dpmpp_x0 (+ the quantile selection) + mmd_dpmpp_sde_update], with the previous evaluation's data prediction m1 as the
+    history.  Next to the coefficient tables sit the cz tables (fp32 [ROWS_CAP] per stream, the noise coefficient of each row), reloaded
+    by retable.  With a seeded.CounterNoise the recorded update is mmd_dpmpp_sde_update_ctr, which draws at the evaluation number it reads
+    from t_idx, and the stepper owns no noise buffers; otherwise full-batch noise buffers (lanes read slices) are refilled by set_step at
+    every update row - video first, then audio, as the eager loop draws - and left alone at the denoise row."""
+    WHO = "sample_graph_sde"
+
+    def _prepare(self):
+        e = self.eng
+        self.noise = None
+        if self.ctr is None:
+            self.noise = {k: th.zeros((self.N,) + tuple(xk.shape[1:]), dtype=th.float32, device=self.device)
+                          for k, xk in (("video", e.x_video), ("audio", e.x_audio))}
+
+    def _history(self, xk):
+        return {"m1": th.zeros_like(xk)}
+
+    def _update(self, x, src, x0_form, b, tab, t_idx, F, C, Cm, HW, s, max_val):
+        k, sl = b["stream"], self._lane(b["lane"])
+        noise = dict(ctr=(self.key, self.ids[sl], dict(STREAMS)[k])) if self.ctr is not None else dict(noise=self.noise[k][sl])
+        ops.dpmpp_sde_update(x, src, b["m1"], tab, self.cz[k], t_idx, F, C, Cm, HW, s=s, max_val=max_val, **noise)
+
+    def retable(self, tabs, ctr=None):
+        super().retable(tabs, ctr)
+        if not hasattr(self, "cz"):
+            self.cz = {k: th.zeros(self.ROWS_CAP, dtype=th.float32, device=self.device) for k in ("video", "audio")}
+        for k in ("video", "audio"):
+            self.cz[k][:self.rows].copy_(th.from_numpy(tabs["cz"][k]))
+
+    def set_step(self, i, shifts=None, noise=None):
+        """SolverStepper.set_step, and the noise of an update row: `noise` = {"video", "audio"}, else drawn (video first, then audio)."""
+        super().set_step(i, shifts, noise)
+        if self.ctr is not None:
+            if noise is not None:
+                raise H.MMDError("this step draws its noise in the update kernels (CounterNoise): it takes no noise tensors")
+        elif self.kinds[int(i)] != ops.DPMPP_KIND_DENOISE:
+            for k in ("video", "audio"):
+                if noise is not None:
+                    self.noise[k].copy_(noise[k])
+                else:
+                    self.noise[k].normal_()
