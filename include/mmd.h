@@ -511,6 +511,22 @@ int mmd_dpmpp_sde_update(float* x, const float* m0, float* M1, const float* nois
 int mmd_dpmpp_sde_update_ctr(float* x, const float* m0, float* M1, const uint32_t* key, const int64_t* ids, int tag, const float* s,
                              float max_val, const float* tab, const float* cz, const int64_t* k, int rows, int N, int F, int C, int Cm,
                              int HW, void* stream);
+/* Spherical interpolation of two latents, row by row: a, b, out fp32 [N, per], lam fp32 [N] (device), out[n] = w_a a[n] + w_b b[n] with
+ *   dot = sum a b, na = sum a^2, nb = sum b^2      fp64 sums of the fp32 data (every product is exact in fp64)
+ *   c = clamp(dot / sqrt(na nb), -1, 1), theta = acos c, s = sin theta
+ *   w_a = sin((1 - lam) theta) / s, w_b = sin(lam theta) / s;      na nb == 0 or |c| > 0.9995: w_a = 1 - lam, w_b = lam (the chord)
+ * The weights are formed in fp64 by one thread and rounded to fp32 once; the combine is fma(w_a, a, fl(w_b b)), so the error of out is
+ * two weight roundings, one product rounding and one fused add.  lam = 0 / 1 gives weights exactly (1, 0) / (0, 1): out is bitwise a / b
+ * for finite data without negative zeros.  lam outside [0, 1] extrapolates.
+ * Two launches over a grid of (chunks of a sample, N): partial sums into ws (fp64 [N, chunks, 3], mmd_slerp_ws_bytes(N, per) bytes, host
+ * only, 0 for bad arguments), then the combine, whose every workgroup re-reduces the chunks of its sample in one fixed tree order.  No
+ * atomics, no host read, no library state: legal inside a stream capture.  The chunking depends on per alone and the order of every sum
+ * on the element index alone, so row n is bitwise the same in any batch and at any buffer address.  16-byte loads and stores where a quad
+ * of consecutive elements is whole and its address a multiple of 16 (a, b and out each by their own address), element by element
+ * otherwise.  Refused before anything is launched: a NULL pointer, N <= 0 (or > 65535), per <= 0, out overlapping a or b (a and b may
+ * overlap: slerp(a, a) = a by the chord). */
+int64_t mmd_slerp_ws_bytes(int N, int64_t per);
+int mmd_slerp(const float* a, const float* b, const float* lam, float* out, double* ws, int N, int64_t per, void* stream);
 /* One evaluation of the single-step DPM-Solver / DPM-Solver++ loop (multimodal_dpm_solver_plus.py:1277-1294; orders 1-3, dpm:532-887)
  * from the same kind of table (fp32 [6][rows] = cx, ce, c0, c1, c2, kind; k as above; a sample whose k is outside [0, rows) writes
  * nothing: not x, not XB, not MS).  A step of order p is p evaluations; its later stages combine the state and the model value at the

@@ -1315,3 +1315,119 @@ extern "C" int mmd_dpmpp_sde_update_ctr(float* x, const float* m0, float* M1, co
   return mmd_launch<dpmpp_sde_update_kernel<SdeNoiseFromCounter>>("dpmpp_sde_update_ctr", dim3(ew_grid((per + 3) / 4 * N)), dim3(256), 0, (hipStream_t)stream,
                                                                   p, DpmppTab{tab, k, rows}, q, SdeNoiseFromCounter{{key, ids, tag}});
 }
+
+// ----------------------------------------------------------------------------- spherical interpolation of two latents
+// out[n] = w_a a[n] + w_b b[n] for fp32 [N, per] rows, lam fp32 [N] (ddim_interpolate: the slerp of two encoded clips).  With
+//   dot = sum a b, na = sum a^2, nb = sum b^2 (fp64 sums of fp32 data: every product is exact in fp64),
+//   c = clamp(dot / sqrt(na nb), -1, 1), theta = acos c, s = sin theta,
+// the weights are w_a = sin((1 - lam) theta) / s, w_b = sin(lam theta) / s, or the chord's 1 - lam, lam when na nb == 0 or |c| > 0.9995
+// (sin theta < 0.032 there: the two forms differ by less than theta^2 / 8 and the quotient loses its digits).  They are formed in fp64
+// and rounded to fp32 once, so the error of out is that of the combine fma(w_a, a, fl(w_b b)).  theta is evaluated once: lam = 0 gives
+// s / s = 1 and sin(0) / s = 0, lam = 1 the mirror image, so out is bitwise a or b (finite data without negative zeros).
+// Two launches, SLERP_BLOCK threads per workgroup, grid (chunks, N): slerp_sums_kernel writes the three partial sums of its chunk to
+// ws [N, chunks, 3]; slerp_combine_kernel re-reduces the chunks of its sample - every workgroup in the same tree order - and one
+// thread forms the weights.  No atomics, no host read; the chunking depends on `per` alone (slerp_chunk), so a row's bits do not
+// depend on N.  A thread owns quads of consecutive elements of a sample: 16-byte accesses where the quad is whole and its address a
+// multiple of 16 (a, b and out each by their own address), element by element otherwise, and the order of every sum follows the element
+// index alone - a row's bits do not depend on where its buffers start either.
+#define SLERP_BLOCK 256
+#define SLERP_UNIT (SLERP_BLOCK * 4 * 2)      // two quads per thread: the smallest chunk
+#define SLERP_MAX_CHUNKS 256                  // the combine kernel reduces them with one block tree sum
+static int64_t slerp_chunk(int64_t per) {
+  const int64_t units = (per + (int64_t)SLERP_UNIT * SLERP_MAX_CHUNKS - 1) / ((int64_t)SLERP_UNIT * SLERP_MAX_CHUNKS);
+  return units * SLERP_UNIT;
+}
+static int slerp_chunks(int64_t per) { return (int)((per + slerp_chunk(per) - 1) / slerp_chunk(per)); }
+__device__ __forceinline__ bool quad_on16(const float* p, int cnt) { return cnt == 4 && ((uintptr_t)p & 15) == 0; }
+
+__global__ __launch_bounds__(SLERP_BLOCK) void slerp_sums_kernel(const float* __restrict__ a, const float* __restrict__ b, double* __restrict__ ws,
+                                                                 int64_t per, int64_t chunk) {
+  __shared__ double s_d[SLERP_BLOCK], s_a[SLERP_BLOCK], s_b[SLERP_BLOCK];
+  const int tid = threadIdx.x;
+  const int64_t n = blockIdx.y, lo = (int64_t)blockIdx.x * chunk, hi = lo + chunk < per ? lo + chunk : per;
+  const float* an = a + n * per;
+  const float* bn = b + n * per;
+  double dot = 0.0, na = 0.0, nb = 0.0;
+  for (int64_t r0 = lo + (int64_t)tid * 4; r0 < hi; r0 += SLERP_BLOCK * 4) {
+    const int cnt = hi - r0 < 4 ? (int)(hi - r0) : 4;
+    float av[4] = {}, bv[4] = {};
+    quad_load(an + r0, cnt, quad_on16(an + r0, cnt), av);
+    quad_load(bn + r0, cnt, quad_on16(bn + r0, cnt), bv);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {      // elements past the end are zeros: they add nothing
+      const double x = av[j], y = bv[j];
+      dot += x * y;
+      na += x * x;
+      nb += y * y;
+    }
+  }
+  s_d[tid] = dot;
+  s_a[tid] = na;
+  s_b[tid] = nb;
+  block_tree_sum256(tid, s_d, s_a, s_b);
+  if (tid == 0) {
+    double* w = ws + (n * gridDim.x + blockIdx.x) * 3;
+    w[0] = s_d[0];
+    w[1] = s_a[0];
+    w[2] = s_b[0];
+  }
+}
+
+__global__ __launch_bounds__(SLERP_BLOCK) void slerp_combine_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                                    const float* __restrict__ lam, float* __restrict__ out,
+                                                                    const double* __restrict__ ws, int64_t per, int64_t chunk) {
+  __shared__ double s_d[SLERP_BLOCK], s_a[SLERP_BLOCK], s_b[SLERP_BLOCK];
+  __shared__ float s_w[2];
+  const int tid = threadIdx.x;
+  const int64_t n = blockIdx.y, lo = (int64_t)blockIdx.x * chunk, hi = lo + chunk < per ? lo + chunk : per;
+  const bool have = tid < (int)gridDim.x;      // gridDim.x = the chunks of a sample <= SLERP_MAX_CHUNKS
+  const double* w = ws + (n * gridDim.x + (have ? tid : 0)) * 3;
+  s_d[tid] = have ? w[0] : 0.0;
+  s_a[tid] = have ? w[1] : 0.0;
+  s_b[tid] = have ? w[2] : 0.0;
+  block_tree_sum256(tid, s_d, s_a, s_b);
+  if (tid == 0) {
+    const double l = lam[n], den = s_a[0] * s_b[0];
+    double wa = 1.0 - l, wb = l;
+    if (den != 0.0) {
+      const double c = fmin(fmax(s_d[0] / sqrt(den), -1.0), 1.0);
+      if (!(fabs(c) > 0.9995)) {      // a NaN goes through the quotient and shows in out
+        const double theta = acos(c), s = sin(theta);
+        wa = sin((1.0 - l) * theta) / s;
+        wb = sin(l * theta) / s;
+      }
+    }
+    s_w[0] = (float)wa;
+    s_w[1] = (float)wb;
+  }
+  __syncthreads();
+  const float wa = s_w[0], wb = s_w[1];
+  const float* an = a + n * per;
+  const float* bn = b + n * per;
+  float* on = out + n * per;
+  for (int64_t r0 = lo + (int64_t)tid * 4; r0 < hi; r0 += SLERP_BLOCK * 4) {
+    const int cnt = hi - r0 < 4 ? (int)(hi - r0) : 4;
+    float av[4] = {}, bv[4] = {}, v[4];
+    quad_load(an + r0, cnt, quad_on16(an + r0, cnt), av);
+    quad_load(bn + r0, cnt, quad_on16(bn + r0, cnt), bv);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = __fmaf_rn(wa, av[j], __fmul_rn(wb, bv[j]));      // spelled out: one rounded product, one fma
+    quad_store(on + r0, cnt, quad_on16(on + r0, cnt), v);
+  }
+}
+
+extern "C" int64_t mmd_slerp_ws_bytes(int N, int64_t per) {
+  return N > 0 && per > 0 ? (int64_t)N * slerp_chunks(per) * 3 * (int64_t)sizeof(double) : 0;
+}
+
+extern "C" int mmd_slerp(const float* a, const float* b, const float* lam, float* out, double* ws, int N, int64_t per, void* stream) {
+  MMD_REQUIRE(a && b && lam && out && ws, "slerp: needs a, b, lam, out and the workspace ws (mmd_slerp_ws_bytes)");
+  MMD_REQUIRE(N > 0 && N <= 65535 && per > 0, "slerp: N must be in [1, 65535] and per positive, got N %d per %lld", N, (long long)per);
+  MMD_REQUIRE(per <= ((int64_t)1 << 40) / N, "slerp: N per = %d x %lld elements is too large", N, (long long)per);
+  MMD_REQUIRE(dpm_disjoint(out, a, per * N) && dpm_disjoint(out, b, per * N), "slerp: out must not overlap a or b (a and b may overlap)");
+  const int64_t chunk = slerp_chunk(per);
+  const dim3 grid(slerp_chunks(per), N);
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = mmd_launch<slerp_sums_kernel>("slerp_sums", grid, dim3(SLERP_BLOCK), 0, st, a, b, ws, per, chunk)) return rc;
+  return mmd_launch<slerp_combine_kernel>("slerp_combine", grid, dim3(SLERP_BLOCK), 0, st, a, b, lam, out, (const double*)ws, per, chunk);
+}

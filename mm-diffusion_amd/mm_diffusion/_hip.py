@@ -124,6 +124,8 @@ _PROTOS = {
     "mmd_dpm_single_update": (i32, [vp, vp, i32, vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "mmd_dpmpp_sde_update": (i32, [vp, vp, vp, vp, vp, f32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "mmd_dpmpp_sde_update_ctr": (i32, [vp, vp, vp, vp, vp, i32, vp, f32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "mmd_slerp_ws_bytes": (i64, [i32, i64]),
+    "mmd_slerp": (i32, [vp, vp, vp, vp, vp, i32, i64, vp]),
 }
 EXPORTS = tuple(_PROTOS)
 

@@ -231,3 +231,9 @@ class GaussianDiffusion(_Base):
         raise NotImplementedError("tensor-valued diffusion: use the multimodal class for {'video','audio'} states")
 
     conditional_p_sample_loop = multimodal_training_losses
+
+    def ddim_encode_loop(self, *a, **kw):
+        raise H.MMDError("DDIM inversion (ddim_encode_loop, ddim_decode_loop, ddim_interpolate and their progressive forms) is built for the "
+                         "multimodal {'video','audio'} process only: the tensor-valued SR stage has no inversion loop")
+
+    ddim_encode_loop_progressive = ddim_decode_loop = ddim_decode_loop_progressive = ddim_interpolate = ddim_encode_loop

@@ -22,6 +22,9 @@ MI355X-first differences:
     [q_sample + U-Net plan + both reductions] as one hipGraph per step and reads the tables back once.  The reference's
     own multimodal `calc_bpd_loop` cannot run (it calls `.device` / `th.randn_like` on the stream dict, gd:1249-1257); here
     it is the per-stream loop over the reference's working pieces, every result keyed {"video", "audio"}
+  * DDIM inversion (`ddim_encode_loop`, `ddim_decode_loop`, `ddim_interpolate`): the reverse ODE of `ddim_reverse_sample` (gd:903-953) as a
+    graph-replayed loop from the clip up to a level, the DDIM loop from a level and a state the caller holds, and the spherical
+    interpolation of two encoded clips (mmd_slerp) decoded at every weight; none of it is in the reference, whose reverse step raises
 Not built: cond_fn (the reference's condition_mean / condition_score call `.float()` / `.shape` on the stream
 dict, gd:385,403, and raise for every multimodal call); KL / RESCALED_KL in multimodal_training_losses (no terms in the
 reference either, gd:1143).
@@ -400,6 +403,211 @@ class GaussianDiffusion:
                 out = self.ddim_sample(model, x, t, clip_denoised=clip_denoised, model_kwargs=model_kwargs, eta=eta)
             yield out["sample"]
             x = out["sample"]
+
+    # ------------------------------------------------------------------ DDIM inversion: encode, decode from a level, interpolate
+    # "Level l" (0 <= l <= T-1) is the state whose signal level is alphas_cumprod[l].  A clip is read as the level-0 state (the reference's
+    # convention: ddim_reverse_sample at t = 0 reads alphas_cumprod[0]); ddim_sample_loop's x_T is the level T-1 state.  Encode step i maps
+    # level i to level i + 1 (mmd_ddim_update with flag 8 at t = i), decode step i maps level i to level i - 1 (the "ddim" update at t = i;
+    # step 0 ends at the sample).  Both evaluate the model at the level-i state, and with a seeded.CounterNoise both take the window shifts
+    # of draw i, so an encode followed by a decode sees the same windows level by level.
+    def _level(self, who, name, value, top_message=None):
+        """The checked level argument `name` of `who`: an int in [1, T-1] for an encode target, [0, T-1] for a decode start."""
+        T = self.num_timesteps
+        lo = 1 if top_message is not None else 0
+        if value is None:
+            value = T - 1
+        if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+            raise H.MMDError(f"{who}: {name} must be an integer level, got {value!r}")
+        value = int(value)
+        if top_message is not None and value == T:
+            raise H.MMDError(f"{who}: {name} = {value} = T: {top_message}")
+        if not lo <= value <= T - 1:
+            raise H.MMDError(f"{who}: {name} = {value} is outside [{lo}, {T - 1}] (T = {T} levels, level l has signal alphas_cumprod[l])")
+        return value
+
+    _NO_TOP = ("alphas_cumprod_next[T-1] is 0, so that encode step would return the model's eps prediction, and no decode loop starts "
+               "there (the top level is T-1)")
+
+    def ddim_encode_indices(self, to_level=None, who="ddim_encode_loop", name="to_level"):
+        """The steps an encode to level `to_level` (in [1, T-1], default T-1) runs, in order: i = 0 ... to_level - 1; step i reads
+        alphas_cumprod[i] and alphas_cumprod_next[i] = alphas_cumprod[i + 1], never the 0 that pads the table's end."""
+        return list(range(self._level(who, name, to_level, top_message=self._NO_TOP)))
+
+    def ddim_decode_indices(self, from_level=None, who="ddim_decode_loop", name="from_level"):
+        """The steps a decode from level `from_level` (in [0, T-1], default T-1) runs, in order: i = from_level ... 0."""
+        return list(range(self._level(who, name, from_level), -1, -1))
+
+    def _invert_state(self, who, name, model, x, device, shapes_only=False):
+        """The checked {"video", "audio"} state `name` of an inversion loop as fp32 device tensors, and its device.  Nothing is moved
+        for the caller: a CPU tensor is refused, as everywhere on this path.  shapes_only: check the layout against the model, no more."""
+        from .sampler import unwrap_unet
+        if not isinstance(x, dict) or set(x) != {"video", "audio"} or not all(th.is_tensor(v) for v in x.values()):
+            raise H.MMDError(f"{who}: {name} must be a dict of tensors {{'video': [B,F,C,H,W], 'audio': [B,C,L]}}")
+        v, a = x["video"], x["audio"]
+        if v.dim() != 5 or a.dim() != 3 or v.shape[0] != a.shape[0] or v.shape[0] < 1:
+            raise H.MMDError(f"{who}: {name} must be video [B,F,C,H,W] and audio [B,C,L] of one batch, got {tuple(v.shape)} and {tuple(a.shape)}")
+        unet = unwrap_unet(model)
+        if unet is not None and (list(v.shape[1:]) != list(unet.video_size) or list(a.shape[1:]) != list(unet.audio_size)):
+            raise H.MMDError(f"{who}: {name} has shapes {tuple(v.shape[1:])} / {tuple(a.shape[1:])} per sample, the model takes "
+                             f"{tuple(unet.video_size)} / {tuple(unet.audio_size)}")
+        if shapes_only:
+            return None
+        for k in ("video", "audio"):
+            if not x[k].is_cuda:
+                raise H.MMDError(f"{who}: {name}[{k!r}] is a CPU tensor: the loop runs on the MI355X HIP path only, there is no CPU fallback")
+        dev = v.device
+        if a.device != dev or (device is not None and th.device(device).index not in (None, dev.index)):
+            raise H.MMDError(f"{who}: {name} and device must name one GPU")
+        self._sampling_device(device if device is not None else dev)
+        return {"video": v.float().contiguous(), "audio": a.float().contiguous()}, dev
+
+    @staticmethod
+    def _refuse_hooks(who, denoised_fn, cond_fn):
+        if denoised_fn is not None:
+            raise H.MMDError(f"{who}: denoised_fn is not supported (the fused update forms the x_0 prediction inside the kernel)")
+        if cond_fn is not None:
+            raise H.MMDError(f"{who}: cond_fn is not supported (see ddim_sample)")
+
+    def _encode_step(self, model, x, i, clip_denoised, model_kwargs):
+        """The eager encode step i: ddim_reverse_sample at t = i; with a counter source the forward takes the window shifts of draw i."""
+        import contextlib
+        ctr = self._counter()
+        t = th.tensor([i] * x["video"].shape[0], device=x["video"].device)
+        if ctr is not None:
+            ctr.set_draw(i)
+        with th.no_grad(), (ctr.shifting(model) if ctr is not None else contextlib.nullcontext()):
+            return self.ddim_reverse_sample(model, x, t, clip_denoised=clip_denoised, model_kwargs=model_kwargs)["sample"]
+
+    def ddim_encode_loop(self, model, x_start, to_level=None, *, clip_denoised=False, model_kwargs=None, device=None, progress=False,
+                         use_graph=True, lanes=None, eta=0.0, denoised_fn=None, cond_fn=None):
+        """The last state of ddim_encode_loop_progressive: the level-`to_level` latent of the clip x_start."""
+        final = None
+        for sample in self.ddim_encode_loop_progressive(model, x_start, to_level, clip_denoised=clip_denoised, model_kwargs=model_kwargs,
+                                                        device=device, progress=progress, use_graph=use_graph, lanes=lanes, eta=eta,
+                                                        denoised_fn=denoised_fn, cond_fn=cond_fn):
+            final = sample
+        return final
+
+    def ddim_encode_loop_progressive(self, model, x_start, to_level=None, *, clip_denoised=False, model_kwargs=None, device=None,
+                                     progress=False, use_graph=True, lanes=None, eta=0.0, denoised_fn=None, cond_fn=None):
+        """DDIM inversion: x_start = {"video", "audio"} is read as the level-0 state and steps i = 0 ... to_level - 1 of the reverse ODE
+        (gd:903-953) carry it to level `to_level` (in [1, T-1], default T-1: where ddim_sample_loop starts); the state after every step
+        is yielded.  One graph replay per lane and step (sampler.GraphStepper, update="ddim_reverse") under the rule of the other loops,
+        else ddim_reverse_sample step by step: the same bits.  The arguments are checked here, before the first step is asked for."""
+        who = "ddim_encode_loop"
+        self._refuse_hooks(who, denoised_fn, cond_fn)
+        if eta != 0.0:
+            raise H.MMDError(f"{who}: eta = {eta}: the reverse ODE is deterministic, only eta = 0 can be inverted")
+        indices = self.ddim_encode_indices(to_level)
+        x, device = self._invert_state(who, "x_start", model, x_start, device)
+        stepper = self._graph_stepper(model, model_kwargs, use_graph, x["video"].shape[0], device, clip_denoised, update="ddim_reverse",
+                                      lanes=lanes)
+        return self._encode_steps(model, x, self._progress(indices, progress), stepper, clip_denoised, model_kwargs)
+
+    def _encode_steps(self, model, x, indices, stepper, clip_denoised, model_kwargs):
+        if stepper is not None:
+            stepper.load(x["video"], x["audio"])
+            yield from self._replay(stepper, indices)
+            return
+        for i in indices:
+            x = self._encode_step(model, x, i, clip_denoised, model_kwargs)
+            yield x
+
+    def ddim_decode_loop(self, model, latent, from_level=None, *, eta=0.0, clip_denoised=True, model_kwargs=None, device=None, progress=False,
+                         use_graph=True, lanes=None, denoised_fn=None, cond_fn=None):
+        """The last state of ddim_decode_loop_progressive: the sample the level-`from_level` state `latent` decodes to."""
+        final = None
+        for sample in self.ddim_decode_loop_progressive(model, latent, from_level, eta=eta, clip_denoised=clip_denoised,
+                                                        model_kwargs=model_kwargs, device=device, progress=progress, use_graph=use_graph,
+                                                        lanes=lanes, denoised_fn=denoised_fn, cond_fn=cond_fn):
+            final = sample
+        return final
+
+    def ddim_decode_loop_progressive(self, model, latent, from_level=None, *, eta=0.0, clip_denoised=True, model_kwargs=None, device=None,
+                                     progress=False, use_graph=True, lanes=None, denoised_fn=None, cond_fn=None):
+        """ddim_sample_loop_progressive on a state the caller holds: latent = {"video", "audio"} at level `from_level` (in [0, T-1],
+        default T-1) runs steps i = from_level ... 0 of the "ddim" stepper (or ddim_sample eagerly) and every state is yielded.  With
+        eta > 0 the noise of step i is drawn at draw i with a counter source, as in ddim_sample_loop.  From T-1 on that loop's x_T this is
+        that loop, bit for bit.  The arguments are checked here, before the first step is asked for."""
+        who = "ddim_decode_loop"
+        self._refuse_hooks(who, denoised_fn, cond_fn)
+        indices = self.ddim_decode_indices(from_level)
+        x, device = self._invert_state(who, "latent", model, latent, device)
+        stepper = self._graph_stepper(model, model_kwargs, use_graph, x["video"].shape[0], device, clip_denoised, update="ddim", eta=eta,
+                                      lanes=lanes)
+        return self._decode_steps(model, x, self._progress(indices, progress), stepper, clip_denoised, model_kwargs, eta)
+
+    def _decode_steps(self, model, x, indices, stepper, clip_denoised, model_kwargs, eta):
+        if stepper is not None:
+            stepper.load(x["video"], x["audio"])
+            yield from self._replay(stepper, indices)
+            return
+        for i in indices:
+            t = th.tensor([i] * x["video"].shape[0], device=x["video"].device)
+            with th.no_grad():
+                x = self.ddim_sample(model, x, t, clip_denoised=clip_denoised, model_kwargs=model_kwargs, eta=eta)["sample"]
+            yield x
+
+    def ddim_interpolate(self, model, a, b, weights, level=None, *, clip_denoised=False, model_kwargs=None, device=None, progress=False,
+                         use_graph=True, lanes=None, batch=None, denoised_fn=None, cond_fn=None):
+        """Latent interpolation of two batches of clips: encode a and b to `level` (default T-1), form slerp(enc a, enc b, w) per stream
+        and pair for every w in `weights` (mmd_slerp: rows that are parallel, opposite or zero take the chord), and decode each from
+        `level` at eta = 0.  Returns {"video": [B, len(weights), F, C, H, W], "audio": [B, len(weights), C, L]}: entry [n, j] is pair n at
+        weights[j]; w = 0 is decode(encode(a[n])), w = 1 decode(encode(b[n])).  clip_denoised applies to the encode and the decode alike.
+        One encode stepper serves both encodes and one decode stepper every decode; `batch` (default B, a divisor of B) is their batch
+        size, and larger inputs run through them in chunks.  Bitwise the composition ddim_encode_loop, ops.slerp, ddim_decode_loop."""
+        who = "ddim_interpolate"
+        self._refuse_hooks(who, denoised_fn, cond_fn)
+        up = self.ddim_encode_indices(level, who, "level")
+        level = len(up)
+        down = self.ddim_decode_indices(level, who, "level")
+        for name, x in (("a", a), ("b", b)):
+            self._invert_state(who, name, model, x, device, shapes_only=True)
+        try:
+            lams = [float(w) for w in weights]
+        except TypeError:
+            raise H.MMDError(f"{who}: weights must be a sequence of numbers") from None
+        if not lams or not all(math.isfinite(w) for w in lams):
+            raise H.MMDError(f"{who}: weights must be a non-empty sequence of finite numbers, got {weights!r}")
+        xa, device = self._invert_state(who, "a", model, a, device)
+        xb, _ = self._invert_state(who, "b", model, b, device)
+        B = xa["video"].shape[0]
+        if xb["video"].shape[0] != B:
+            raise H.MMDError(f"{who}: a and b must hold the same number of clips, got {B} and {xb['video'].shape[0]}")
+        nb = B if batch is None else int(batch)
+        if nb < 1 or B % nb:
+            raise H.MMDError(f"{who}: batch = {batch} must be a positive divisor of the {B} pairs")
+        enc = self._graph_stepper(model, model_kwargs, use_graph, nb, device, clip_denoised, update="ddim_reverse", lanes=lanes)
+        dec = self._graph_stepper(model, model_kwargs, use_graph, nb, device, clip_denoised, update="ddim", lanes=lanes)
+        kw = dict(clip_denoised=clip_denoised, model_kwargs=model_kwargs, use_graph=False)
+
+        def run(stepper, x, indices):
+            stepper.load(x["video"], x["audio"])
+            for i in indices:
+                stepper.step(i)
+            return stepper.current()
+
+        def encode(x):
+            return run(enc, x, up) if enc is not None else self.ddim_encode_loop(model, x, level, **kw)
+
+        def decode(x):
+            return run(dec, x, down) if dec is not None else self.ddim_decode_loop(model, x, level, **kw)
+        out = {k: th.empty((B, len(lams)) + tuple(xa[k].shape[1:]), dtype=th.float32, device=device) for k in ("video", "audio")}
+        lam_dev = [th.full((nb,), w, dtype=th.float32, device=device) for w in lams]
+        chunks = self._progress([slice(c, c + nb) for c in range(0, B, nb)], progress)
+        try:
+            for sl in chunks:
+                ea = encode({k: v[sl] for k, v in xa.items()})
+                eb = encode({k: v[sl] for k, v in xb.items()})
+                for j, lam in enumerate(lam_dev):
+                    res = decode({k: ops.slerp(ea[k], eb[k], lam) for k in ("video", "audio")})
+                    for k in ("video", "audio"):
+                        out[k][sl, j] = res[k]
+        finally:
+            for st in (enc, dec):
+                if st is not None:
+                    st.close()
+        return out
 
     # ------------------------------------------------------------------ zero-shot conditional sampling (gd:584-819)
     def _sampling_device(self, device):

@@ -1327,7 +1327,31 @@ def dpmpp_sde_update(x, m0, M1, tab, cz, k, F, C, Cm, HW, noise=None, ctr=None, 
     return x
 
 
-DPM1_KIND_OPEN, DPM1_KIND_STAGE, DPM1_KIND_DENOISE = 0, 1, 2      # row kinds of mmd_dpm_single_update (include/mmd.h)
+def slerp_workspace(N, per, device):
+    return alloc(max(H.lib().mmd_slerp_ws_bytes(int(N), int(per)) // 8, 1), dtype=torch.float64, device=device)
+
+
+def slerp(a, b, lam, out=None, ws=None):
+    """out[n] = the spherical interpolation of rows a[n] and b[n] at lam[n] (include/mmd.h: mmd_slerp; the chord where the rows are
+    zero, parallel or opposite).  a, b: fp32 contiguous [N, ...] of one shape; lam: fp32 device [N]; out like a, overlapping neither a
+    nor b; ws: slerp_workspace(N, per, device).  out and ws are allocated when not given (inside a stream capture hand both in)."""
+    H.require_cuda(a, b, lam, out, ws)
+    N = a.shape[0] if a.dim() else 0
+    per = a[0].numel() if N else 0
+    for name, v in (("a", a), ("b", b), ("out", out)):
+        if v is not None and (v.dtype != torch.float32 or not v.is_contiguous() or tuple(v.shape) != tuple(a.shape)):
+            raise H.MMDError(f"slerp: {name} must be contiguous fp32 of a's shape {tuple(a.shape)}, got {v.dtype} {tuple(v.shape)}")
+    if lam.dtype != torch.float32 or lam.numel() != N or not lam.is_contiguous():
+        raise H.MMDError(f"slerp: lam must be one contiguous fp32 weight per row ({N}), got {lam.dtype} {tuple(lam.shape)}")
+    ws = slerp_workspace(N, per, a.device) if ws is None else ws
+    if ws.dtype != torch.float64 or not ws.is_contiguous() or ws.numel() * 8 < H.lib().mmd_slerp_ws_bytes(int(N), int(per)):
+        raise H.MMDError(f"slerp: ws must be contiguous fp64 with at least {H.lib().mmd_slerp_ws_bytes(int(N), int(per))} bytes (slerp_workspace)")
+    out = alloc(a.shape, dtype=torch.float32, device=a.device) if out is None else out
+    _dispatch("mmd_slerp", a.data_ptr(), b.data_ptr(), lam.data_ptr(), out.data_ptr(), ws.data_ptr(), N, per, meta=("slerp", 0, 20 * a.numel()))
+    return out
+
+
+DPM1_KIND_OPEN, DPM1_KIND_STAGE, DPM1_KIND_DENOISE = 0, 1, 2     # row kinds of mmd_dpm_single_update (include/mmd.h)
 
 
 def dpm_single_update(x, src, XB, MS, tab, k, F, C, Cm, HW, form=0, s=None, max_val=1.0):

@@ -2,7 +2,8 @@
 hipGraph (mmd_graph_*), replayed per step.  Between replays only three small device buffers change: the
 timestep (loop index + model timestep), the window shifts and the noise.  update="vlb" replays one step of the
 variational bound instead (calc_bpd_loop): [q_sample of both streams from static x_0 buffers + U-Net plan + mmd_vlb_terms of
-both streams], whose per-sample results land in device tables at the step's column.
+both streams], whose per-sample results land in device tables at the step's column.  update="ddim_reverse" replays one step of DDIM
+inversion (ddim_encode_loop): [U-Net plan + mmd_ddim_update with flag 8 of both streams], which draws nothing.
 
 Replaces the per-step host work of the reference loop (gd:561-582 + resp:134-139): th.tensor([i]*B) H2D,
 the timestep_map tensor rebuild, ~16 table uploads and ~55k ATen dispatches.
@@ -287,8 +288,12 @@ class LaneStepper:
 
 
 class GraphStepper(LaneStepper):
-    """One denoising step of `batch` trajectories as one graph replay per lane (LaneStepper): update "ddpm" / "ddim", or one step of the
-    variational bound ("vlb").
+    """One denoising step of `batch` trajectories as one graph replay per lane (LaneStepper): update "ddpm" / "ddim", one step of the
+    variational bound ("vlb"), or one step of the DDIM reverse ODE ("ddim_reverse": level i -> level i + 1, mmd_ddim_update with flag 8).
+
+    The reverse step draws nothing, so it owns no noise buffers and has no counter form; with a seeded.CounterNoise on the diffusion its
+    set_step(i) still takes the window shifts from ctr.shifts(i, unet) - the draw decode step i uses, and both evaluate the model at the
+    level-i state.  It takes neither cond nor jump_length.
 
     With a seeded.CounterNoise as the diffusion's noise_source (update "ddpm" / "ddim") the step owns no noise buffers: the graph records
     mmd_ddpm_update_ctr / mmd_ddim_update_ctr, which draw the noise of (seed, sample id, loop index, stream, element) in the kernel - a
@@ -306,8 +311,12 @@ class GraphStepper(LaneStepper):
 
     def __init__(self, diffusion, unet, batch, device, clip_denoised=True, use_graph=True, update="ddpm", eta=0.0, lanes=None, cond=None,
                  jump_length=None):
-        if update not in ("ddpm", "ddim", "vlb"):
-            raise H.MMDError(f"unknown update {update!r} (ddpm, ddim or vlb)")
+        if update not in ("ddpm", "ddim", "ddim_reverse", "vlb"):
+            raise H.MMDError(f"unknown update {update!r} (ddpm, ddim, ddim_reverse or vlb)")
+        if update == "ddim_reverse" and jump_length is not None:
+            raise H.MMDError("jump_length: resampling jumps ride the ddpm update; the ddim_reverse update (DDIM inversion) takes none")
+        if update == "ddim_reverse" and cond:
+            raise H.MMDError("cond: masked conditioning rides the sampling steps (ddpm, ddim), not the ddim_reverse update (DDIM inversion)")
         if jump_length is not None and update != "ddpm":
             raise H.MMDError(f"resampling jumps ride the ddpm update, not {update!r}")
         if cond and update == "vlb":
@@ -321,7 +330,7 @@ class GraphStepper(LaneStepper):
         self.flags = diffusion._flags(clip_denoised)
         e, n = self.eng, self.n
         self.noise_v = self.noise_a = None
-        if ctr is None:
+        if ctr is None and update != "ddim_reverse":      # the reverse ODE step draws nothing
             self.noise_v = th.zeros((self.N,) + tuple(e.x_video.shape[1:]), dtype=th.float32, device=self.device)
             self.noise_a = th.zeros((self.N,) + tuple(e.x_audio.shape[1:]), dtype=th.float32, device=self.device)
         self._noise = {"video": self.noise_v, "audio": self.noise_a}
@@ -343,7 +352,7 @@ class GraphStepper(LaneStepper):
             self._x0 = {"video": self.x0_v, "audio": self.x0_a}
             self.res = {k: tuple(th.zeros(self.N, T, dtype=th.float32, device=self.device) for _ in range(3)) for k in ("video", "audio")}
             self._ws = [(ops.vlb_workspace(n, self.device), ops.vlb_workspace(n, self.device)) for _ in self.engs]
-        elif update == "ddim":       # ddim_sample (gd:821-901): same graph, different fused update
+        elif update in ("ddim", "ddim_reverse"):       # ddim_sample (gd:821-901) / ddim_reverse_sample (gd:903-953): same graph, different fused update
             self._tab3 = diffusion.ddim_tables(self.device)
         plans = self.update_plans = self._add_set("step", [])
         self.jump_plans = self._add_set("jump", [], bare=True) if self.jtab is not None else []
@@ -385,6 +394,9 @@ class GraphStepper(LaneStepper):
         that draw by counter, else (its slice of the stream's noise buffer,)."""
         sl = self._lane(r)
         t_idx, (F, C, HW) = self.t_idx[sl], geom
+        if self.update == "ddim_reverse":      # flag 8: x_t -> x_{t+1} by alphas_cumprod_next; no noise source in either form
+            ops.ddim_update(x, out, None, x, self.tab, self._tab3, t_idx, F, C, HW, self.flags | 8, 0.0)
+            return
         src = (self.key, self.ids[sl], tag) if self.ctr is not None else (self._noise[k][sl],)
         if self.update == "vlb":
             vb, xs, em = (a[sl] for a in self.res[k])
@@ -461,6 +473,10 @@ class GraphStepper(LaneStepper):
         elif draw is not None and int(draw) != int(i):
             raise H.MMDError("a draw other than the step's index needs a stepper built with jump_length")
         self._push_step(int(i), float(tm) * (1000.0 / self.orig_T) if self.use_f32 else int(tm), shifts)
+        if self.update == "ddim_reverse":
+            if noise is not None:
+                raise H.MMDError("the ddim_reverse step draws nothing: it takes no noise tensors")
+            return
         if self.ctr is not None:
             if noise is not None:
                 raise H.MMDError("this step draws its noise in the update kernels (CounterNoise): it takes no noise tensors")
