@@ -545,6 +545,78 @@ int mmd_dpm_single_update(float* x, const float* src, int form, float* XB, float
 /* adaptive-step error term (dpm:1088-1149): out[n] += sum(((hi - lo) / max(atol, rtol max(|lo|, |prev|)))^2), fp64, caller zeroes. */
 int mmd_dpm_err(const float* hi, const float* lo, const float* prev, float atol, float rtol, int N, int64_t per_sample, double* out,
                 void* stream);
+/* --- the adaptive DPM-Solver++ of order 2 with its step-size controller on the device (DPM_Solver.sample_graph_adaptive; the eager
+ * loop, multimodal_dpm_solver_plus.py dpm_solver_adaptive, reads one scalar back per trial step).  A trial step s -> t = lambda^-1(lambda_s
+ * + h) evaluates the network at (x, s) and at (x_s1, s1 = lambda^-1(lambda_s + h / 2)).  Data prediction only.  All four kernels are
+ * ordinary launches without atomics or library state, legal inside a stream capture; arguments are refused before anything is launched
+ * (a NULL pointer, N <= 0, overlapping buffers).  x / XB / MS / LO / PREV: fp32 [N,F,C,HW]; src fp32 [N,F,Cm,HW], Cm = C or 2C; tab: fp32
+ * [6][rows] and k: int64 [N] as in mmd_dpm_single_update (a sample whose k is outside [0, rows) writes nothing) - the stepper uses
+ * rows = N and k[n] = n, the controller's per-sample rows, and k[n] = -1 once sample n is done.  m (the model value): form 0 / form 1 and
+ * s / max_val exactly as in mmd_dpm_single_update, with tab rows 0, 1 = cx, ce.  The elementwise kernels own one quad per thread
+ * (16-byte accesses where the quad is whole and aligned, element by element otherwise) and their sums are mmd_lincomb's term by term,
+ * so they write the bits of the mmd_clamp_scale / mmd_lincomb / copy launches they replace.
+ *   mmd_dpm_adapt_open     tab rows 2-5 = a0, a1, b0, b1.  XB = x, MS = m0, LO = a0 x + a1 m0 (the first-order result at t),
+ *                          x = b0 x + b1 m0 (the first-order result at s1: the next evaluation's input).
+ *   mmd_dpm_adapt_close    tab rows 2-4 = c0, c1, c2.  x = c0 XB + c1 MS + c2 m1 (the second-order result at t, over x_s1), and in the
+ *                          same pass the element term e = (x - LO) / max(atol, rtol max(|LO|, |PREV|)) in fp32 - mmd_dpm_err's
+ *                          expression, atol and rtol read from params and rounded to fp32 - summed as e^2 in fp64 over a grid of
+ *                          (chunks of a sample, N) into partial[n][chunk], chunks = mmd_dpm_adapt_chunks(F C HW) of
+ *                          MMD_DPM_ADAPT_CHUNK elements.  A thread adds its elements in ascending order, the 256 threads fold in one
+ *                          fixed tree: row n is bitwise the same in any batch and at any address.
+ *   mmd_dpm_adapt_control  one workgroup, after both streams' close.  Per sample (batch != 0: for the whole batch, the reference's
+ *                          rule) in fp64: sum the chunks of each stream in ascending order, E = max over streams of
+ *                          (float)sqrt(sum / per); accept iff E <= 1: s = t, lambda_s = lambda(s); h = min(theta h E^(-1/2), lambda_0 -
+ *                          lambda_s); done iff |s - t_0| <= t_err.  Then everything the next trial reads: t and s1 by piecewise-linear
+ *                          interpolation in log_alpha (fp64 [T], log alpha at t_i = (i + 1) / T; sigma^2 = -expm1(2 log alpha)); the
+ *                          model timesteps of s and s1, ((float)t - 1/T) * T truncated, each operation in fp32; the fp32 rows, each
+ *                          rounded once from fp64; the row indices; the counters; status = {samples not done, fault}.  A non-finite
+ *                          sum or E sets the fault bit (kept until the next init) and the flag REJECT and changes nothing else.
+ *                          mode 1 (init): s = t_T, h = h_init, counters 0, flag IDLE, the first trial's rows; reads no partial sums.
+ *                          state  fp64 [N][MMD_ADAPT_STATE_WORDS] (MMD_ADAPT_S_*)      cnt  int32 [N][4] (MMD_ADAPT_C_*)
+ *                          itab   int64 [3][N] = k (n, or -1 when done), model timestep of s, of s1
+ *                          ftab   fp32 [16][N]: rows 0-5 the open table (cx, ce at s; a0, a1, b0, b1), 6-11 the close table (cx, ce at
+ *                                 s1; c0, c1, c2; 0), 12-13 alpha, sigma at s, 14-15 alpha, sigma at s1 (mmd_cond_replace's tables)
+ *                          params fp64 [MMD_ADAPT_PARAMS] (MMD_ADAPT_P_*): the tolerances live in device memory, not in the launch
+ *   mmd_dpm_adapt_commit   per sample by cnt's flag: ACCEPT PREV = LO; REJECT x = XB; IDLE nothing.
+ *   mmd_dpm_adapt_time     dst[n] = src[n], int64 [N]: a row of model timesteps into the network's timestep buffer, which both
+ *                          evaluations of a trial share (8 N bytes need not be the 16-byte rows mmd_copy2d moves). */
+#define MMD_DPM_ADAPT_CHUNK 4096
+#define MMD_ADAPT_PARAMS 8
+#define MMD_ADAPT_P_ATOL 0
+#define MMD_ADAPT_P_RTOL 1
+#define MMD_ADAPT_P_THETA 2
+#define MMD_ADAPT_P_TERR 3
+#define MMD_ADAPT_P_HINIT 4
+#define MMD_ADAPT_P_TT 5
+#define MMD_ADAPT_P_T0 6
+#define MMD_ADAPT_STATE_WORDS 8
+#define MMD_ADAPT_S_S 0
+#define MMD_ADAPT_S_H 1
+#define MMD_ADAPT_S_LAM 2
+#define MMD_ADAPT_S_T 3
+#define MMD_ADAPT_S_S1 4
+#define MMD_ADAPT_S_E 5
+#define MMD_ADAPT_S_LAM0 6
+#define MMD_ADAPT_S_SPARE 7
+#define MMD_ADAPT_C_ATTEMPTS 0
+#define MMD_ADAPT_C_ACCEPTED 1
+#define MMD_ADAPT_C_FLAG 2
+#define MMD_ADAPT_C_DONE 3
+#define MMD_ADAPT_FLAG_REJECT 0
+#define MMD_ADAPT_FLAG_ACCEPT 1
+#define MMD_ADAPT_FLAG_IDLE 2
+int64_t mmd_dpm_adapt_chunks(int64_t per_sample);
+int mmd_dpm_adapt_open(float* x, const float* src, int form, float* XB, float* MS, float* LO, const float* s, float max_val,
+                       const float* tab, const int64_t* k, int rows, int N, int F, int C, int Cm, int HW, void* stream);
+int mmd_dpm_adapt_close(float* x, const float* src, int form, const float* XB, const float* MS, const float* LO, const float* PREV,
+                        const float* s, float max_val, const float* tab, const int64_t* k, int rows, const double* params, double* partial,
+                        int N, int F, int C, int Cm, int HW, void* stream);
+int mmd_dpm_adapt_control(int mode, int batch, const double* params, const double* log_alpha, int T, const double* partial_v, int chunks_v,
+                          int64_t per_v, const double* partial_a, int chunks_a, int64_t per_a, double* state, int64_t* itab, int32_t* cnt,
+                          float* ftab, int32_t* status, int N, void* stream);
+int mmd_dpm_adapt_commit(float* x, const float* XB, float* PREV, const float* LO, const int32_t* cnt, int N, int64_t per_sample,
+                         void* stream);
+int mmd_dpm_adapt_time(const int64_t* src, int64_t* dst, int N, void* stream);
 /* SR model input (image_unet.py:704-715): out [N,2C,H,W] = concat(x [N,C,H,W], bilinear(low [N,C,h,w] -> H x W)), fp32. */
 int mmd_bilinear_concat(const float* x, const float* low, float* out, int N, int C, int H, int W, int h, int w, void* stream);
 /* The same tensor as channels-last rows [(n, y, x), Cpad] in `dtype` (channels 2C..Cpad zero): feeds the SR stem as an implicit GEMM. */

@@ -2,6 +2,7 @@
 // get_variance + 453-470 p_sample) and its backward, the DDIM step, q_sample, the coefficient combinations, the training-loss and
 // variational-bound reductions with their gradients, and the DPM-Solver helpers.
 #include "mmd_common.h"
+#include "mmd_dpm_elem.h"
 
 // ----------------------------------------------------------------------------- the element core
 // What every kernel of the process shares, written once.  tables: fp32 [7][T], rows = sqrt_recip_ac, sqrt_recipm1_ac, post_c1, post_c2,
@@ -472,11 +473,7 @@ extern "C" int mmd_lincomb_t(const float* a, const float* b, float* out, const f
 }
 
 // out = ca a + cb b + cc c with host scalars (b, c nullable): the DPM-Solver update combinations (dpm:520-1100).
-// The terms of such a combination, shared with the graph step's kernels (dpmpp_x0_kernel, dpmpp_update_kernel) so that both write the
-// same bits: lincomb_kernel has always compiled to a rounded ca a and one fused multiply-add per further term, and that form is spelled
-// out here (its device code is unchanged by it).  A term that is absent is not added: -0 + 0 * c is +0.
-__device__ __forceinline__ float lincomb_first(float ca, float a) { return ca * a; }
-__device__ __forceinline__ float lincomb_add(float v, float c, float t) { return fmaf(c, t, v); }
+// Its terms are lincomb_first / lincomb_add (mmd_dpm_elem.h), shared with the graph step's kernels so that all write the same bits.
 __global__ __launch_bounds__(256) void lincomb_kernel(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ c,
                                                       float* __restrict__ out, float ca, float cb, float cc, int64_t total) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
@@ -849,11 +846,7 @@ extern "C" int mmd_abs_quantile(const float* x, int N, int64_t per_sample, float
 }
 
 // x[n, :] = clamp(x, -s_n, s_n) / (s_n / max_val),  s_n = max(s[n], 1)        (in place)
-// one element of it, shared with dpmpp_update_kernel
-__device__ __forceinline__ float clamp_scale_elem(float v, float s, float max_val) {
-  const float sn = fmaxf(s, 1.f);
-  return fminf(fmaxf(v, -sn), sn) / (sn / max_val);
-}
+// one element of it: clamp_scale_elem (mmd_dpm_elem.h), shared with the update kernels
 __global__ __launch_bounds__(256) void clamp_scale_kernel(float* __restrict__ x, const float* __restrict__ s, float max_val, int64_t per,
                                                           int64_t total) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
@@ -1163,12 +1156,6 @@ __global__ __launch_bounds__(256) void dpm_single_update_kernel(const DiffusionP
   }
 }
 
-// [a, a + n) and [b, b + n) floats share no byte
-static bool dpm_disjoint(const float* a, const float* b, int64_t n) {
-  const uintptr_t ua = (uintptr_t)a, ub = (uintptr_t)b, len = (uintptr_t)n * sizeof(float);
-  return ua + len <= ub || ub + len <= ua;
-}
-
 extern "C" int mmd_dpm_single_update(float* x, const float* src, int form, float* XB, float* MS, const float* s, float max_val, const float* tab,
                                      const int64_t* k, int rows, int N, int F, int C, int Cm, int HW, void* stream) {
   MMD_REQUIRE(x && src && XB && MS && tab && k, "dpm_single_update: needs x, the source of m0, XB, MS, the table and the step numbers");
@@ -1218,25 +1205,6 @@ struct SdeNoiseFromCounter {
   CtrKey k;
   __device__ __forceinline__ void draw(int64_t n, int64_t r0, int64_t, uint32_t d, int, bool, float* z) const { ctr_normals(k, n, r0, d, z); }
 };
-__device__ __forceinline__ void quad_load(const float* p, int cnt, bool vec, float* v) {
-  if (vec) {
-    const float4 q = *reinterpret_cast<const float4*>(p);
-    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (j < cnt) v[j] = p[j];
-  }
-}
-__device__ __forceinline__ void quad_store(float* p, int cnt, bool vec, const float* v) {
-  if (vec) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (j < cnt) p[j] = v[j];
-  }
-}
 template <class Src>
 __global__ __launch_bounds__(256) void dpmpp_sde_update_kernel(const DiffusionParams p, const DpmppTab t, const DpmppSdeParams q, const Src src) {
   const int64_t per = (int64_t)p.F * p.C * p.HW;
@@ -1283,7 +1251,6 @@ __global__ __launch_bounds__(256) void dpmpp_sde_update_kernel(const DiffusionPa
   }
 }
 
-static bool on16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 static int dpmpp_sde_args(const char* what, const float* x, const float* m0, const float* M1, const float* s, float max_val, const float* tab,
                           const float* cz, const int64_t* k, int rows, int N, int F, int C, int Cm, int HW) {
   MMD_REQUIRE(x && m0 && M1 && tab && k, "%s: needs x, m0, M1, the table and the step numbers", what);
@@ -1338,7 +1305,6 @@ static int64_t slerp_chunk(int64_t per) {
   return units * SLERP_UNIT;
 }
 static int slerp_chunks(int64_t per) { return (int)((per + slerp_chunk(per) - 1) / slerp_chunk(per)); }
-__device__ __forceinline__ bool quad_on16(const float* p, int cnt) { return cnt == 4 && ((uintptr_t)p & 15) == 0; }
 
 __global__ __launch_bounds__(SLERP_BLOCK) void slerp_sums_kernel(const float* __restrict__ a, const float* __restrict__ b, double* __restrict__ ws,
                                                                  int64_t per, int64_t chunk) {

@@ -126,6 +126,12 @@ _PROTOS = {
     "mmd_dpmpp_sde_update_ctr": (i32, [vp, vp, vp, vp, vp, i32, vp, f32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "mmd_slerp_ws_bytes": (i64, [i32, i64]),
     "mmd_slerp": (i32, [vp, vp, vp, vp, vp, i32, i64, vp]),
+    "mmd_dpm_adapt_chunks": (i64, [i64]),
+    "mmd_dpm_adapt_open": (i32, [vp, vp, i32, vp, vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "mmd_dpm_adapt_close": (i32, [vp, vp, i32, vp, vp, vp, vp, vp, f32, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "mmd_dpm_adapt_control": (i32, [i32, i32, vp, vp, i32, vp, i32, i64, vp, i32, i64, vp, vp, vp, vp, vp, i32, vp]),
+    "mmd_dpm_adapt_commit": (i32, [vp, vp, vp, vp, vp, i32, i64, vp]),
+    "mmd_dpm_adapt_time": (i32, [vp, vp, i32, vp]),
 }
 EXPORTS = tuple(_PROTOS)
 

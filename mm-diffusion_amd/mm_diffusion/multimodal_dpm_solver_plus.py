@@ -21,7 +21,10 @@ evaluation - a step of order p is p rows, at s, s1 and s2 - and the recorded upd
 `DPM_Solver.sample_graph_sde` is the stochastic multistep solver in its data-prediction form (SDE-DPM-Solver++, orders 1 and 2; eager:
 sample(method="multistep_sde")): `sde_tables` adds a noise coefficient per row, the recorded update mmd_dpmpp_sde_update draws or reads a
 fresh z ~ N(0, I) inside the step graph (sampler.DpmppSdeStepper).  Generation quality is not assessed: there are no trained weights.
-The three share one driver (`_graph_loop`) and the stepper kept from the last call.
+`DPM_Solver.sample_graph_adaptive` is the adaptive solver of order 2 (data prediction) with its step-size controller on the device: the
+error norm, the accept test, the next step size and every coefficient derived from it stay in device memory (mmd_dpm_adapt_*,
+sampler.DpmAdaptiveStepper), a trial step is two graph replays per lane and the host reads a status word every `poll` trial steps.
+All share one driver (`_graph_loop`) and the stepper kept from the last call.
 
 Reference behaviours reproduced knowingly:
   * the noise-prediction first-order update moves the AUDIO stream with the x0-form coefficients
@@ -812,14 +815,18 @@ class DPM_Solver:
         from .sampler import DpmppStepper
         if method != "multistep":
             raise H.MMDError(f"sample_graph: only method 'multistep' is recorded here, got {method!r}: the single-step solver has "
-                             "sample_graph_singlestep, the adaptive solver chooses its evaluations on the host - use sample()")
+                             "sample_graph_singlestep, the adaptive solver sample_graph_adaptive")
         return self._graph_loop("sample_graph", DpmppStepper, lambda: self._graph_check(steps, order, solver_type),
                                 lambda device: self.graph_tables(steps, order, skip_type, solver_type, denoise, device=device),
                                 x_T, shape, known, mask, noise_source, paste_known, use_graph, lanes)
 
-    def _graph_loop(self, who, stepper_cls, check, tables, x_T, shape, known, mask, noise_source, paste_known, use_graph, lanes):
+    def _graph_loop(self, who, stepper_cls, check, tables, x_T, shape, known, mask, noise_source, paste_known, use_graph, lanes, drive=None,
+                    stepper_kw=None):
         """What the graph-replayed loops share: the argument checks (check() has the method's own), the drawing of x_T, the conditioning,
-        the kept stepper of class stepper_cls with the tables of tables(device), and one stepper.step per table row."""
+        the kept stepper of class stepper_cls with the tables of tables(device), and one stepper.step per table row - or drive(stepper),
+        the loop of a method whose evaluations no table lists (its return value is handed back next to the samples).  stepper_kw: further
+        constructor arguments of the stepper; they are part of the kept stepper's key."""
+        stepper_kw = dict(stepper_kw or {})
         from . import masking, sampler
         from .sampler import unwrap_unet
         from .seeded import CounterNoise, TAG_AUDIO, TAG_VIDEO, X_T
@@ -860,7 +867,7 @@ class DPM_Solver:
         B = shape["video"][0]
         key = (stepper_cls.__name__, B, sampler.default_lanes(B) if lanes is None else int(lanes), bool(use_graph), ctr is not None,
                sampler.DPMPP_SELECT, tuple((k, c.mask is not None) for k, c in sorted(cond.items())), bool(self.predict_x0),
-               bool(self.thresholding), float(self.max_val), str(device), id(unet))
+               bool(self.thresholding), float(self.max_val), str(device), id(unet), tuple(sorted(stepper_kw.items())))
         kept = getattr(self, "_stepper", None)
         self._stepper = None
         with torch.no_grad():
@@ -870,14 +877,18 @@ class DPM_Solver:
             else:
                 if kept is not None:
                     kept[1].close()
-                stepper = stepper_cls(self, unet, B, device, tabs, use_graph=use_graph, lanes=lanes, cond=cond, ctr=ctr)
+                stepper = stepper_cls(self, unet, B, device, tabs, use_graph=use_graph, lanes=lanes, cond=cond, ctr=ctr, **stepper_kw)
             try:
                 stepper.load(x_T["video"], x_T["audio"])
                 if cond:
                     stepper.load_cond(cond, x_T)
-                for i in range(tabs["rows"]):
-                    stepper.step(i)
-                    self.nfe += 1
+                extra = None
+                if drive is not None:
+                    extra = drive(stepper)
+                else:
+                    for i in range(tabs["rows"]):
+                        stepper.step(i)
+                        self.nfe += 1
                 if cond and paste_known:
                     stepper.paste_known()
                 out = stepper.current()
@@ -885,14 +896,14 @@ class DPM_Solver:
                 stepper.close()
                 raise
             self._stepper = (key, stepper)
-            return out
+            return out if drive is None else (out, extra)
 
     # ------------------------------------------------------------------ graph-replayed single-step loop
     def _single_check(self, steps, order, method, solver_type):
         who = "sample_graph_singlestep"
         if method not in ("singlestep", "singlestep_fixed"):
             raise H.MMDError(f"{who}: method must be 'singlestep' or 'singlestep_fixed', got {method!r}: the multistep method has sample_graph, "
-                             "the adaptive solver chooses its evaluations on the host - use sample()")
+                             "the adaptive solver sample_graph_adaptive")
         if order not in (1, 2, 3):
             raise H.MMDError(f"{who}: order must be 1, 2 or 3; got {order}")
         if solver_type not in ("dpm_solver", "taylor"):
@@ -964,6 +975,77 @@ class DPM_Solver:
         return self._graph_loop("sample_graph_singlestep", DpmSingleStepper, lambda: self._single_check(steps, order, method, solver_type),
                                 lambda device: self.singlestep_tables(steps, order, skip_type, method, solver_type, denoise, device=device),
                                 x_T, shape, known, mask, noise_source, paste_known, use_graph, lanes)
+
+    # ------------------------------------------------------------------ graph-replayed adaptive loop: the controller on the device
+    def _adaptive_check(self, order, solver_type, control, lanes, poll, max_attempts):
+        who = "sample_graph_adaptive"
+        if self.KEYS != ("video", "audio"):
+            raise H.MMDError(f"{who}: built for the multimodal base model's {{'video', 'audio'}} state only, not for the SR stage's tensor solver")
+        if not self.predict_x0:
+            raise H.MMDError(f"{who}: predict_x0=False is not built: the reference's noise-prediction first update moves the audio stream with "
+                             "x0-form coefficients (dpm:576-584) - use sample(method='adaptive')")
+        if order != 2:
+            raise H.MMDError(f"{who}: order must be 2 (the embedded pair of orders 1 and 2), got order {order}")
+        if solver_type != "dpm_solver":
+            raise H.MMDError(f"{who}: solver_type must be 'dpm_solver', got solver_type {solver_type!r}")
+        if control not in ("sample", "batch"):
+            raise H.MMDError(f"{who}: control must be 'sample' or 'batch', got control {control!r}")
+        if control == "batch" and lanes is not None and int(lanes) != 1:
+            raise H.MMDError(f"{who}: control='batch' takes the maximum over the whole batch, which must sit in one lane: lanes must be 1, got lanes {lanes}")
+        if int(poll) < 1:
+            raise H.MMDError(f"{who}: poll must be at least 1 trial step between two status reads, got poll {poll}")
+        if int(max_attempts) < 1:
+            raise H.MMDError(f"{who}: max_attempts must be at least 1, got max_attempts {max_attempts}")
+
+    def adaptive_tables(self, h_init=0.05, atol=0.0078, rtol=0.05, theta=0.9, t_err=1e-5, t_start=None, t_end=None):
+        """What the device controller of sample_graph_adaptive reads: {"params": the parameter block's values, "log_alpha": the discrete
+        schedule's knots as float64 (log alpha at t_i = (i + 1) / N - the table the eager solver interpolates in its own dtype)}."""
+        ns = self.noise_schedule
+        t_0 = 1. / ns.total_N if t_end is None else t_end
+        t_T = ns.T if t_start is None else t_start
+        return {"params": dict(atol=atol, rtol=rtol, theta=theta, t_err=t_err, h_init=h_init, t_T=t_T, t_0=t_0),
+                "log_alpha": ns.log_alpha_array.reshape(-1).double().cpu().numpy()}
+
+    def sample_graph_adaptive(self, x_T=None, *, shape=None, order=2, h_init=0.05, atol=0.0078, rtol=0.05, theta=0.9, t_err=1e-5,
+                              control="sample", poll=4, max_attempts=1000, known=None, mask=None, noise_source=None, paste_known=True,
+                              use_graph=True, lanes=None, return_stats=False, solver_type="dpm_solver"):
+        """sample(method="adaptive") of order 2 in its data-prediction form with the step-size controller on the device
+        (sampler.DpmAdaptiveStepper; include/mmd.h: mmd_dpm_adapt_*): a trial step is two graph replays per lane, and the error norm, the
+        accept test, the next step size, the next times and every coefficient derived from them stay in device memory.  The host replays
+        `poll` trial steps, then reads one status word per lane (samples not done, fault bit); a trial step replayed after a sample is
+        done is an exact no-op for it, so samples and statistics are bitwise the same for every poll.  A model with a host shift_source
+        draws the shifts of up to poll - 1 trial steps (2 (poll - 1) evaluations) more than the loop needed.
+        control="sample": every sample has its own s, h, error and decision - sample k of a seed is the same at any batch and lane count;
+        control="batch": the reference's rule, E = the maximum over all samples and streams and one s, h for the batch (one lane), the form
+        to hold against sample(method="adaptive"), whose coefficients are fp32 where the controller's are fp64 rounded once.
+        More than max_attempts trial steps, or a non-finite error sum (the fault bit; that sample's state is left as it was), raise MMDError
+        at the poll that sees them.  x_T / shape, known / mask / paste_known, noise_source, use_graph and lanes as in sample_graph; the
+        known cells are set before both evaluations at the levels of s and s1.  return_stats: also {"attempts", "accepted", "nfe"} per
+        sample and "trials", "host_reads" of the call.  self.nfe grows by 2 x the trial steps replayed.  The tolerances live in a device
+        parameter block: another call with other values replays the kept stepper's graph execs."""
+        from .sampler import DpmAdaptiveStepper
+        who = "sample_graph_adaptive"
+        self._adaptive_check(order, solver_type, control, lanes, poll, max_attempts)      # first: the SR stage's solver gets no further
+        if control == "batch" and lanes is None:
+            lanes = 1
+
+        def drive(stepper):
+            stepper.start()
+            while True:
+                for _ in range(min(int(poll), int(max_attempts) - stepper.trials)):
+                    stepper.trial()
+                    self.nfe += 2
+                active, fault = stepper.poll()
+                if fault:
+                    raise H.MMDError(f"{who}: a non-finite error sum after {stepper.trials} trial steps (the sample's state was left as it was)")
+                if not active:
+                    break
+                if stepper.trials >= int(max_attempts):
+                    raise H.MMDError(f"{who}: {active} sample(s) not done after max_attempts = {stepper.trials} trial steps")
+            return dict(stepper.stats(), trials=stepper.trials, host_reads=stepper.host_reads)
+        out, stats = self._graph_loop(who, DpmAdaptiveStepper, lambda: None, lambda device: self.adaptive_tables(h_init, atol, rtol, theta, t_err), x_T, shape, known, mask, noise_source,
+                                      paste_known, use_graph, lanes, drive=drive, stepper_kw=dict(control=control))
+        return (out, stats) if return_stats else out
 
 
 def expand_dims(v, dims):

@@ -1380,6 +1380,131 @@ def dpm_err(hi, lo, prev, atol, rtol, out):
     return out
 
 
+# ----------------------------------------------------------------------------- adaptive DPM-Solver++, controller on the device
+DPM_ADAPT_CHUNK = 4096          # include/mmd.h: MMD_DPM_ADAPT_CHUNK, the elements of a sample behind one partial error sum
+ADAPT_PARAMS = 8                # fp64 words of the parameter block, and where each parameter sits (MMD_ADAPT_P_*)
+ADAPT_P = {"atol": 0, "rtol": 1, "theta": 2, "t_err": 3, "h_init": 4, "t_T": 5, "t_0": 6}
+ADAPT_STATE_WORDS = 8           # fp64 words per sample of the controller's state (MMD_ADAPT_S_*)
+ADAPT_S = {"s": 0, "h": 1, "lam_s": 2, "t": 3, "s1": 4, "E": 5, "lam_0": 6}
+ADAPT_C = {"attempts": 0, "accepted": 1, "flag": 2, "done": 3}      # int32 words per sample of the counters (MMD_ADAPT_C_*)
+ADAPT_FLAG_REJECT, ADAPT_FLAG_ACCEPT, ADAPT_FLAG_IDLE = 0, 1, 2
+
+
+def dpm_adapt_chunks(per):
+    """Partial error sums per sample of `per` elements: the chunking depends on the sample size alone."""
+    return -(-int(per) // DPM_ADAPT_CHUNK)
+
+
+def dpm_adapt_params(device, out=None, **values):
+    """The controller's parameter block (fp64 [ADAPT_PARAMS], device memory) from atol, rtol, theta, t_err, h_init, t_T, t_0; `out`: an
+    existing block to refill - the recorded launches read the block, so other tolerances need no new capture."""
+    if set(values) != set(ADAPT_P):
+        raise H.MMDError(f"dpm_adapt_params: needs exactly {sorted(ADAPT_P)}, got {sorted(values)}")
+    host = torch.zeros(ADAPT_PARAMS, dtype=torch.float64)
+    for name, v in values.items():
+        host[ADAPT_P[name]] = float(v)
+    if out is None:
+        return host.to(device)
+    out.copy_(host)
+    return out
+
+
+class AdaptBlock:
+    """The device memory mmd_dpm_adapt_control keeps for N samples (include/mmd.h), and its views: k (row indices), tm_s / tm_s1 (the
+    model timesteps), tab_open / tab_close (fp32 [6, N], mmd_dpmpp_x0's layout), q_s / q_s1 (fp32 [2, N], mmd_cond_replace's)."""
+
+    def __init__(self, N, device):
+        self.N = N = int(N)
+        self.state = torch.zeros(N, ADAPT_STATE_WORDS, dtype=torch.float64, device=device)
+        self.itab = torch.zeros(3, N, dtype=torch.int64, device=device)
+        self.cnt = torch.zeros(N, 4, dtype=torch.int32, device=device)
+        self.ftab = torch.zeros(16, N, dtype=torch.float32, device=device)
+        self.status = torch.zeros(2, dtype=torch.int32, device=device)
+        self.k, self.tm_s, self.tm_s1 = self.itab[0], self.itab[1], self.itab[2]
+        self.tab_open, self.tab_close, self.q_s, self.q_s1 = self.ftab[0:6], self.ftab[6:12], self.ftab[12:14], self.ftab[14:16]
+
+
+def _adapt_args(name, x, src, others, tab, k, F, C, Cm, HW, form, s):
+    N = x.shape[0]
+    _dpmpp_args(name, tab, k, N, (("x", x), ("src", src), ("s", s)) + tuple(others))
+    if form not in (0, 1) or (s is not None and form != 0):
+        raise H.MMDError(f"{name}: form is 0 or 1, and s goes with form 0 only")
+    if x.numel() != N * F * C * HW or any(v.numel() != x.numel() for _, v in others) or src.numel() != N * F * Cm * HW or \
+            (s is not None and s.numel() != N):
+        raise H.MMDError(f"{name}: x and {' / '.join(w for w, _ in others)} must hold N F C HW = {N * F * C * HW}, src N F Cm HW = "
+                         f"{N * F * Cm * HW} elements and s one per sample")
+    return N
+
+
+def dpm_adapt_open(x, src, XB, MS, LO, tab, k, F, C, Cm, HW, form=0, s=None, max_val=1.0):
+    """The first evaluation of an adaptive trial step, in place (include/mmd.h: mmd_dpm_adapt_open): XB = x, MS = m0, LO = a0[k] x + a1[k] m0,
+    x = b0[k] x + b1[k] m0; tab rows = cx, ce, a0, a1, b0, b1; m0 as in dpm_single_update (form, s, max_val)."""
+    H.require_cuda(x, src, XB, MS, LO, tab, k, s)
+    N = _adapt_args("dpm_adapt_open", x, src, (("XB", XB), ("MS", MS), ("LO", LO)), tab, k, F, C, Cm, HW, form, s)
+    _dispatch("mmd_dpm_adapt_open", x.data_ptr(), src.data_ptr(), int(form), XB.data_ptr(), MS.data_ptr(), LO.data_ptr(), H.ptr(s), float(max_val),
+              tab.data_ptr(), k.data_ptr(), tab.shape[1], N, F, C, Cm, HW, meta=("dpm_adapt_open", 0, 24 * x.numel()))
+    return x
+
+
+def dpm_adapt_close(x, src, XB, MS, LO, PREV, tab, k, params, partial, F, C, Cm, HW, form=0, s=None, max_val=1.0):
+    """The second evaluation of an adaptive trial step (mmd_dpm_adapt_close): x = c0[k] XB + c1[k] MS + c2[k] m1 over x_s1, and
+    partial[n, chunk] = the fp64 sum of ((x - LO) / max(atol, rtol max(|LO|, |PREV|)))^2 over that chunk; tab rows = cx, ce, c0, c1, c2;
+    params: dpm_adapt_params' block; partial: fp64 [N, dpm_adapt_chunks(F C HW)]."""
+    H.require_cuda(x, src, XB, MS, LO, PREV, tab, k, s, params, partial)
+    N = _adapt_args("dpm_adapt_close", x, src, (("XB", XB), ("MS", MS), ("LO", LO), ("PREV", PREV)), tab, k, F, C, Cm, HW, form, s)
+    if params.dtype != torch.float64 or params.numel() != ADAPT_PARAMS or not params.is_contiguous():
+        raise H.MMDError(f"dpm_adapt_close: params must be the contiguous fp64 [{ADAPT_PARAMS}] parameter block")
+    if partial.dtype != torch.float64 or not partial.is_contiguous() or partial.numel() != N * dpm_adapt_chunks(F * C * HW):
+        raise H.MMDError(f"dpm_adapt_close: partial must be contiguous fp64 [N, {dpm_adapt_chunks(F * C * HW)}]")
+    _dispatch("mmd_dpm_adapt_close", x.data_ptr(), src.data_ptr(), int(form), XB.data_ptr(), MS.data_ptr(), LO.data_ptr(), PREV.data_ptr(), H.ptr(s),
+              float(max_val), tab.data_ptr(), k.data_ptr(), tab.shape[1], params.data_ptr(), partial.data_ptr(), N, F, C, Cm, HW,
+              meta=("dpm_adapt_close", 0, 28 * x.numel()))
+    return x
+
+
+def dpm_adapt_control(blk, params, log_alpha, partials=(), batch=False, init=False):
+    """The controller (mmd_dpm_adapt_control) on an AdaptBlock: init writes the start state and the first trial's rows; otherwise
+    partials = ((partial fp64 [N, chunks], per), ...) of one or two streams ends a trial.  log_alpha: fp64 [T], device."""
+    H.require_cuda(blk.state, params, log_alpha, *(p for p, _ in partials))
+    if params.dtype != torch.float64 or params.numel() != ADAPT_PARAMS or not params.is_contiguous():
+        raise H.MMDError(f"dpm_adapt_control: params must be the contiguous fp64 [{ADAPT_PARAMS}] parameter block")
+    if log_alpha.dtype != torch.float64 or log_alpha.dim() != 1 or not log_alpha.is_contiguous():
+        raise H.MMDError("dpm_adapt_control: log_alpha must be a contiguous fp64 vector")
+    if init != (len(partials) == 0) or len(partials) > 2:
+        raise H.MMDError("dpm_adapt_control: init takes no partial sums, a trial's end those of one or two streams")
+    args = []
+    for p, per in tuple(partials) + ((None, 0),) * (2 - len(partials)):
+        if p is not None and (p.dtype != torch.float64 or not p.is_contiguous() or p.numel() != blk.N * dpm_adapt_chunks(per)):
+            raise H.MMDError(f"dpm_adapt_control: partial sums must be contiguous fp64 [N, {dpm_adapt_chunks(per)}]")
+        args += [H.ptr(p), dpm_adapt_chunks(per) if p is not None else 0, int(per)]
+    _dispatch("mmd_dpm_adapt_control", 1 if init else 0, 1 if batch else 0, params.data_ptr(), log_alpha.data_ptr(), log_alpha.numel(), *args,
+              blk.state.data_ptr(), blk.itab.data_ptr(), blk.cnt.data_ptr(), blk.ftab.data_ptr(), blk.status.data_ptr(), blk.N,
+              meta=("dpm_adapt_control", 0, 0))
+
+
+def dpm_adapt_commit(x, XB, PREV, LO, cnt):
+    """Per sample by the controller's flag (mmd_dpm_adapt_commit): accept PREV = LO, reject x = XB, idle nothing."""
+    H.require_cuda(x, XB, PREV, LO, cnt)
+    N = x.shape[0]
+    for name, v in (("x", x), ("XB", XB), ("PREV", PREV), ("LO", LO)):
+        if v.dtype != torch.float32 or not v.is_contiguous() or v.numel() != x.numel():
+            raise H.MMDError(f"dpm_adapt_commit: {name} must be contiguous fp32 with the {x.numel()} elements of x")
+    if cnt.dtype != torch.int32 or not cnt.is_contiguous() or cnt.numel() != 4 * N:
+        raise H.MMDError("dpm_adapt_commit: cnt must be the contiguous int32 [N, 4] counters")
+    _dispatch("mmd_dpm_adapt_commit", x.data_ptr(), XB.data_ptr(), PREV.data_ptr(), LO.data_ptr(), cnt.data_ptr(), N, x[0].numel(),
+              meta=("dpm_adapt_commit", 0, 8 * x.numel()))
+    return x
+
+
+def dpm_adapt_time(src, dst):
+    """dst = src for int64 [N] model timesteps (mmd_dpm_adapt_time): a row of the controller's itab into the network's timestep buffer."""
+    H.require_cuda(src, dst)
+    if src.dtype != torch.int64 or dst.dtype != torch.int64 or src.numel() != dst.numel() or not src.is_contiguous() or not dst.is_contiguous():
+        raise H.MMDError("dpm_adapt_time: src and dst must be contiguous int64 of one size")
+    _dispatch("mmd_dpm_adapt_time", src.data_ptr(), dst.data_ptr(), src.numel(), meta=("dpm_adapt_time", 0, 16 * src.numel()))
+    return dst
+
+
 def ddpm_update_bwd(x, model_out, dsample, dx, dmo, tables, t, flags):
     H.require_cuda(x, model_out, dsample, tables, t)
     _dispatch("mmd_ddpm_update_bwd", x.data_ptr(), model_out.data_ptr(), dsample.data_ptr(), H.ptr(dx), H.ptr(dmo), tables.data_ptr(),

@@ -13,7 +13,8 @@ pre-plan that replaces the known cells, the per-step uploads, the lane events, a
 (name -> per-lane plans behind the U-Net plan, and their per-lane graph execs once captured).  GraphStepper (DDPM / DDIM / variational
 bound) and SolverStepper (DPM-Solver / DPM-Solver++: DpmppStepper multistep, DpmSingleStepper single-step, DpmppSdeStepper stochastic multistep) record their update plans into
 sets and say, in set_step, which set the next launch replays.  A set may be `bare`: launched without the pre-plan and the U-Net plan (the
-forward jump of masked sampling with resampling, GraphStepper.jump)."""
+forward jump of masked sampling with resampling, GraphStepper.jump).  DpmAdaptiveStepper (the adaptive DPM-Solver++ with its step-size
+controller on the device) has two sets per trial step, each with a pre-plan of its own, and no table rows: the controller writes them."""
 import ctypes
 import os
 
@@ -119,6 +120,18 @@ class LaneStepper:
         whole stream) and, without a counter source, the fixed conditioning noise (= that stream's x_T); load_cond fills them.  Every
         lane's pre-plan then starts the step with one mmd_cond_replace per conditioned stream, which sets the known cells of the state
         to q_sample(known, t, noise) by the [2, T] table qtab and leaves the others alone.  cond=None records nothing."""
+        self._alloc_cond(cond)
+        for r in range(self.lanes if self.cond else 0):
+            pre = []
+            with ops.recording(pre):       # on the origin stream: the known cells at this step's noise level
+                for k, tag in STREAMS:
+                    if k in self.cond:
+                        self._cond_replace(r, k, tag, qtab, self.t_idx[self._lane(r)], None)
+            self.pre_plans.append(pre)
+
+    def _alloc_cond(self, cond):
+        """The conditioning buffers of _record_cond, without a recorded pre-plan (a stepper whose levels are not indexed by t_idx records
+        its own mmd_cond_replace launches with _cond_replace)."""
         e = self.eng
         for k, c in (cond or {}).items():
             xk = e.x_video if k == "video" else e.x_audio
@@ -127,13 +140,6 @@ class LaneStepper:
             self.cond[k] = {"known": th.zeros(**like),
                             "mask": None if c.mask is None else th.zeros(self.N, cells, dtype=th.uint8, device=self.device),
                             "noise": None if self.ctr is not None else th.zeros(**like)}
-        for r in range(self.lanes if self.cond else 0):
-            pre = []
-            with ops.recording(pre):       # on the origin stream: the known cells at this step's noise level
-                for k, tag in STREAMS:
-                    if k in self.cond:
-                        self._cond_replace(r, k, tag, qtab, self.t_idx[self._lane(r)], None)
-            self.pre_plans.append(pre)
 
     def _cond_replace(self, r, k, tag, tab2, t, coef):
         """ops.cond_replace of stream k on lane r's state and its slices of the conditioning buffers; coef = (ca, cb) draws no noise."""
@@ -682,3 +688,191 @@ class DpmppSdeStepper(SolverStepper):
                     self.noise[k].copy_(noise[k])
                 else:
                     self.noise[k].normal_()
+
+
+class DpmAdaptiveStepper(LaneStepper):
+    """The adaptive DPM-Solver++ of order 2 (DPM_Solver.sample_graph_adaptive) with the step-size controller on the device.  A trial
+    step s -> t is two graph replays per lane, and no host scalar enters either:
+      "open"   [model timesteps of s -> the network's timestep buffer + mmd_cond_replace at alpha(s), sigma(s)] + U-Net plan + per stream
+               [the data prediction (+ the quantile selection) + mmd_dpm_adapt_open]
+      "stage"  the same at s1, with mmd_dpm_adapt_close per stream, then the join, mmd_dpm_adapt_control and one mmd_dpm_adapt_commit
+               per stream.
+    The controller (one ops.AdaptBlock per lane) writes the times, the model timesteps, the coefficient rows and the conditioning
+    levels of the next trial into device memory that the recorded launches read: rows = the lane's samples, row index n for sample n,
+    -1 once it is done - the kernels then write nothing for it, so further trial steps are exact no-ops for a finished sample.
+    control="sample": every sample has its own s, h, E and decision; control="batch": the reference's rule, one E (the maximum) and one
+    s, h for the batch, which needs the whole batch in one lane.  atol, rtol, theta, t_err, h_init, t_T and t_0 sit in a device
+    parameter block (retable refills it), so a kept stepper serves other tolerances with the graph execs it has.
+
+    The first launch of a set is its capture's warm-up run; launch() keeps the state, PREV and the controller's block intact around it
+    (the warm-up of "stage" would otherwise count as a trial)."""
+    WHO = "sample_graph_adaptive"
+
+    def __init__(self, solver, unet, batch, device, tabs, use_graph=True, lanes=None, cond=None, ctr=None, select=None, control="sample"):
+        select = DPMPP_SELECT if select is None else select
+        if select not in ("multi", "block"):
+            raise H.MMDError(f"unknown selection {select!r} (multi or block)")
+        if control not in ("sample", "batch"):
+            raise H.MMDError(f"{self.WHO}: control must be 'sample' or 'batch', got {control!r}")
+        if control == "batch":
+            lanes = 1 if lanes is None else lanes
+            if int(lanes) != 1:
+                raise H.MMDError(f"{self.WHO}: control='batch' takes the maximum over the whole batch, which must sit in one lane: lanes must be 1, got {lanes}")
+        if not solver.predict_x0:
+            raise H.MMDError(f"{self.WHO}: the adaptive stepper is built in its data-prediction form only (predict_x0=True)")
+        super().__init__(unet, batch, device, lanes, use_graph, ctr=ctr, own_ids=True)
+        self.diff, self.control = None, control
+        self.params = th.zeros(ops.ADAPT_PARAMS, dtype=th.float64, device=self.device)
+        self.log_alpha = th.zeros(len(tabs["log_alpha"]), dtype=th.float64, device=self.device)
+        self.blk = [ops.AdaptBlock(self.n, self.device) for _ in self.engs]
+        self._status = th.zeros(self.lanes, 2, dtype=th.int32).pin_memory()
+        self.retable(tabs, ctr)
+        self._alloc_cond(cond)
+        n, e = self.n, self.eng
+        geom = {"video": (e.F, e.Cv_in, unet.video_out_channels, e.H0 * e.W0), "audio": (1, e.Ca_in, unet.audio_out_channels, e.L0)}
+        thresholding, max_val = bool(solver.thresholding), float(solver.max_val)
+        self._bufs = []
+        sets = {"open": ([], []), "stage": ([], [])}
+        for r, e in enumerate(self.engs):
+            blk, streams = self.blk[r], []
+            for sid, k, xk, ok in ((0, "video", e.x_video, e.out_video), (1, "audio", e.x_audio, e.out_audio)):
+                per = xk[0].numel()
+                buf = dict(xb=th.zeros_like(xk), ms=th.zeros_like(xk), lo=th.zeros_like(xk), prev=th.zeros_like(xk), x0=th.zeros_like(xk),
+                           s=th.zeros(n, dtype=th.float32, device=self.device), ws=ops.dpmpp_workspace(n, self.device),
+                           partial=th.zeros(n, ops.dpm_adapt_chunks(per), dtype=th.float64, device=self.device), per=per, lane=r, stream=k, x=xk)
+                self._bufs.append(buf)
+                streams.append((sid, k, xk, ok, buf))
+            for name, (pres, plans) in sets.items():
+                opening = name == "open"
+                tab, qtab, tm = (blk.tab_open, blk.q_s, blk.tm_s) if opening else (blk.tab_close, blk.q_s1, blk.tm_s1)
+                pre, plan = [], []
+                with ops.recording(pre):       # on the origin stream: this evaluation's model timesteps, and the known cells at its level
+                    ops.dpm_adapt_time(tm, e.t_i64)
+                    for k, tag in STREAMS:
+                        if k in self.cond:
+                            self._cond_replace(r, k, tag, qtab, blk.k, None)
+                with ops.recording(plan):
+                    for sid, k, xk, ok, b in streams:
+                        Fk, C, Cm, HWk = geom[k]
+                        with ops.on_stream(sid):
+                            src, form, s = ok, 1, None
+                            if thresholding:
+                                multi = select == "multi"
+                                ops.dpmpp_x0(xk, ok, b["x0"], tab, blk.k, Fk, C, Cm, HWk, hist=b["ws"] if multi else None)
+                                if multi:
+                                    ops.dpmpp_select(b["x0"], 0.995, b["s"], b["ws"], level0_done=True)      # p of the Imagen paper
+                                else:
+                                    ops.abs_quantile(b["x0"], 0.995, out=b["s"])
+                                src, form, s, Cm = b["x0"], 0, b["s"], C
+                            if opening:
+                                ops.dpm_adapt_open(xk, src, b["xb"], b["ms"], b["lo"], tab, blk.k, Fk, C, Cm, HWk, form=form, s=s, max_val=max_val)
+                            else:
+                                ops.dpm_adapt_close(xk, src, b["xb"], b["ms"], b["lo"], b["prev"], tab, blk.k, self.params, b["partial"], Fk, C, Cm,
+                                                    HWk, form=form, s=s, max_val=max_val)
+                    ops.record_sync(1, 0)
+                    if not opening:      # behind the join, on the origin stream: the decision, then what it means for x and PREV
+                        ops.dpm_adapt_control(blk, self.params, self.log_alpha, [(b["partial"], b["per"]) for *_, b in streams],
+                                              batch=control == "batch")
+                        for _, _, xk, _, b in streams:
+                            ops.dpm_adapt_commit(xk, b["xb"], b["prev"], b["lo"], blk.cnt)
+                pres.append(pre)
+                plans.append(plan)
+        for name, (pres, plans) in sets.items():
+            self._add_set(name, plans)
+            self._sets[name].pre = pres
+        self.update_plans = self._sets["open"].plans
+        self.trials = self.evals = self.host_reads = 0
+
+    @property
+    def graphs(self):
+        return self._sets["open"].graphs
+
+    def retable(self, tabs, ctr=None):
+        """Load the parameter block, the schedule and (with a counter source) the key and sample ids: what another call may change."""
+        if (ctr is None) != (self.ctr is None):
+            raise H.MMDError("the noise source's kind is fixed when the stepper is built")
+        if len(tabs["log_alpha"]) != self.log_alpha.numel():
+            raise H.MMDError(f"{self.WHO}: the schedule's length is fixed when the stepper is built")
+        ops.dpm_adapt_params(self.device, out=self.params, **tabs["params"])
+        self.log_alpha.copy_(th.as_tensor(tabs["log_alpha"], dtype=th.float64))
+        self.ctr = ctr
+        if ctr is not None:
+            self.key.copy_(ctr.key(self.device))
+            self.ids.copy_(ctr.ids(self.N, self.device))
+
+    usable = SolverStepper.usable
+
+    # ------------------------------------------------------------------ launch: the sets carry their own pre-plans
+    def _lane_launch(self, ps, r, stream):
+        e = self.engs[r]
+        aux = e.aux.cuda_stream
+        ops.run_plan(ps.pre[r], stream, aux)
+        ops.run_plan(e.plan, stream, aux)
+        ops.run_plan(ps.plans[r], stream, aux)
+
+    def _mutable(self):
+        """Every buffer a set's warm-up run may change and its first replay does not rewrite from scratch."""
+        out = [b[name] for b in self._bufs for name in ("x", "prev")]
+        for blk in self.blk:
+            out += [blk.state, blk.itab, blk.cnt, blk.ftab, blk.status]
+        return out + [e.t_i64 for e in self.engs]
+
+    def launch(self):
+        ps = self._sets[self._set]
+        if self.use_graph and ps.graphs is None:
+            keep = [(t, t.clone()) for t in self._mutable()]
+            self._capture(ps)
+            for t, v in keep:
+                t.copy_(v)
+        if self.use_graph:
+            self._fan(_replay, ps)
+        else:
+            if self.lanes == 1:
+                self.eng.aux.wait_stream(th.cuda.current_stream(self.device))
+            self._fan(self._lane_launch, ps)
+
+    # ------------------------------------------------------------------ the loop's pieces
+    def start(self):
+        """After load() (and load_cond()): PREV = x_T, and the controller's init - s = t_T, h = h_init, the first trial's rows."""
+        for b in self._bufs:
+            b["prev"].copy_(b["x"])
+        for blk in self.blk:
+            ops.dpm_adapt_control(blk, self.params, self.log_alpha, batch=self.control == "batch", init=True)
+        self.trials = self.evals = self.host_reads = 0
+
+    def _push_shifts(self, i, shifts=None):
+        """The window shifts of evaluation i: one draw per block for the whole batch, from the counter with a CounterNoise."""
+        if shifts is None:
+            own = self.ctr is not None and self.unet.shift_source is None
+            shifts = self.ctr.shifts(i, self.unet) if own else self.unet.draw_shifts()
+        for e in self.engs:
+            e.set_shifts(shifts)
+
+    def trial(self):
+        """One trial step of every lane: the open and the stage replay, two network evaluations."""
+        for name in ("open", "stage"):
+            self._set = name
+            self._push_shifts(self.evals)
+            self.launch()
+            self.evals += 1
+        self.trials += 1
+
+    def poll(self):
+        """(samples not done, fault) from the lanes' status words: one small read through a pinned buffer, and the only host wait."""
+        for r, blk in enumerate(self.blk):
+            self._status[r].copy_(blk.status, non_blocking=True)
+        th.cuda.current_stream(self.device).synchronize()
+        self.host_reads += 1
+        return int(self._status[:, 0].sum()), bool(self._status[:, 1].any())
+
+    def stats(self):
+        """Per-sample {"attempts", "accepted", "nfe"} (int64 host tensors [N]) of the loop so far."""
+        cnt = th.cat([blk.cnt for blk in self.blk]).cpu().to(th.int64)
+        a = cnt[:, ops.ADAPT_C["attempts"]]
+        return {"attempts": a, "accepted": cnt[:, ops.ADAPT_C["accepted"]], "nfe": 2 * a}
+
+    def trace(self):
+        """The controller's block of every sample as host tensors (a device read: for tests and tools, one call per trial step with
+        poll=1): "state" fp64 [N, 8], "cnt" int32 [N, 4], "ftab" fp32 [16, N], "itab" int64 [3, N]."""
+        return {"state": th.cat([b.state for b in self.blk]).cpu(), "cnt": th.cat([b.cnt for b in self.blk]).cpu(),
+                "ftab": th.cat([b.ftab for b in self.blk], dim=1).cpu(), "itab": th.cat([b.itab for b in self.blk], dim=1).cpu()}
