@@ -18,6 +18,27 @@
  *     mmd_env_set of mmd_common.h) - MMD_VCONV_RING at every call; once per process, at first use: MMD_GN_BLOCKS, MMD_STRIP_BLOCKS, MMD_STRIP_K128_RF1, MMD_GEMM_DESC, MMD_TCONV_BLOCKS, MMD_STEM_MFMA, MMD_ATTN_DMA,
  *     MMD_ATTN_PIPE, MMD_ATTN_PIPE_LDSPAD, MMD_WGRAD_TR, MMD_WGRAD_TILE64, MMD_WGRAD_BLOCKS
  *   - return 0 on success, <0 on error (MMD_ERR_*); mmd_last_error() gives the message (thread local)
+ *
+ * Size limits.  Row counts are int (M < 2^31); what can grow past 32 bits is the BYTE range of a strided operand, (rows - 1) * ld * ES +
+ * C * ES - a bf16 ds1 tensor of the base model passes 2 GiB at batch 43 and 4 GiB at batch 86.  Kernels address rows as int64 row * ld
+ * unless listed here (tests/bigaddr.py holds the same table as data; tests/test_bigaddr_gpu.py runs both sides of every limit):
+ *   - mmd_conv_gemm* / mmd_gn_conv1x1* tiles 129 and 132: a 32-bit buffer descriptor over A while (M * lda + Cin) * ES < 2 GiB, the
+ *     64-bit pointer instantiation of the same loop beyond - same results, nothing refused
+ *   - tile 133 (also through mmd_gn_conv_gemm): a descriptor per FRAME of A; a frame whose rows span 2 GiB or more is refused by name
+ *     (tile 130 takes it and is bitwise equal: ops.halo_tile_code)
+ *   - tile 131: Y and R by 32-bit byte offsets from the launch's base.  Rows whose offsets would pass 4 GiB are run as several launches
+ *     of the same kernel, cut at multiples of 256 rows, of the GroupNorm slice and of the (D0, D1, D2) sample of a conv with taps, so
+ *     the results - statistics records included - do not depend on it; only when ONE such unit of Y or R spans 4 GiB (row strides
+ *     of megabytes) is the launch refused by name (ops.strip_tile_ok knows)
+ *   - mmd_gn_conv1x1_skip: M * ldy * 2 < 4 GiB, refused by name beyond (ops.skip_fusable knows; the two launches it replaces run instead)
+ *   - mmd_attn_fwd impl 4 / 5 (and 0 at head width 64): a descriptor over the K/V rows of the batches of one launch; batches are cut into
+ *     launches of less than 2 GiB of K/V; ONE batch of 2 GiB or more is refused for impl 4 / 5 and runs the per-128-query kernel (bitwise
+ *     equal) for impl 0.  Q and O are 64-bit
+ *   - mmd_vconv2d1d: one SAMPLE's rows of X below 2 GiB (a descriptor re-based per sample), refused by name beyond (ops.vconv_shape_ok)
+ *   - mmd_conv_wgrad: the transposing 9-tap kernel while M * ld * 2 < 2 GiB on both operands, the 128-tile kernel beyond
+ *   No other entry has a limit on a strided activation: they form int64 row * ld (the buffer descriptors in mmd_tconv, mmd_tattn_block and
+ *   mmd_vconv2d1d's second one cover the packed weight image only), and every strided entry is run at ranges past 2 and 4 GiB by
+ *   tests/test_bigaddr_gpu.py - also with the extent carried by a Geom's outer_stride or tstride alone.
  */
 #ifndef MMD_H
 #define MMD_H

@@ -1997,14 +1997,57 @@ static int launch_conv1x1_strip(const ConvGemmParams& p, hipStream_t st) {
 
 // tile 131: bf16 convs whose whole K = ntaps * Cin is 128 / 256 (two row fragments per wave) or 384 / 512 (one fragment): the 1x1
 // convs at 128-512 channels and the k=3 temporal / audio convs at 128 channels.  Cin % 64 == 0; fused GroupNorm only with one tap
+static int dispatch_conv1x1_strip_rows(const ConvGemmParams& p, hipStream_t st);
+
+static int64_t lcm64(int64_t a, int64_t b) {
+  int64_t x = a, y = b;
+  while (y) { const int64_t t = x % y; x = y; y = t; }
+  return a / x * b;
+}
+
 static int dispatch_conv1x1_strip(const ConvGemmParams& p, hipStream_t st) {
   const int K = p.Cin * p.ntaps;
   const int rf = K <= 256 ? 2 : 1, cc = K <= 256 ? 64 : 32;
   if ((K != 128 && K != 256 && K != 384 && K != 512) || p.Cin % 64 != 0 || p.Cout % cc != 0 ||
-      (int64_t)p.M * p.ldy * 2 >= 0xffffffffLL || (p.R && (int64_t)p.M * p.ldr * 2 >= 0xffffffffLL) || (p.gn_a && (p.ntaps != 1 || p.gn_rows < 128 * rf)) ||
+      (p.gn_a && (p.ntaps != 1 || p.gn_rows < 128 * rf)) ||
       (p.ntaps == 1 && (p.taps[0] || p.taps[1] || p.taps[2])))
     return mmd_set_error(MMD_ERR_UNSUPPORTED, "conv_gemm tile 131 (strip): needs ntaps * Cin in {128, 256, 384, 512}, Cin %% 64 == 0, Cout %% %d == 0, "
                          "fused GroupNorm only for 1x1 convs with slices of >= %d rows (got Cin=%d ntaps=%d Cout=%d)", cc, 128 * rf, p.Cin, p.ntaps, p.Cout);
+  // The kernel addresses Y and R by 32-bit byte offsets from the launch's base pointers: a launch covers rows whose offsets stay below
+  // 4 GB.  A longer row range is cut into several launches of the SAME instance (the kernel family of a layer - and with it the last
+  // bit of its statistics records - must not depend on the batch size; mmd_attn_fwd cuts its batches the same way).  The cuts are
+  // multiples of 256 rows (whole row blocks of either instance, whole 64-row records), of the GroupNorm slice and of the sample a conv
+  // with taps stays inside: every row meets the operands, the wave position and the record it meets in one launch.
+  const int64_t row_bytes = 2 * (p.R && p.ldr > p.ldy ? p.ldr : p.ldy);
+  if ((int64_t)p.M * row_bytes < 0xffffffffLL) return dispatch_conv1x1_strip_rows(p, st);
+  int64_t unit = 256;
+  if (p.gn_a) unit = lcm64(unit, p.gn_rows);
+  if (p.ntaps > 1) unit = lcm64(unit, (int64_t)p.D0 * p.D1 * p.D2);
+  const int64_t per = (0xffffffffLL - 1) / row_bytes / unit * unit;
+  if (per <= 0)
+    return mmd_set_error(MMD_ERR_UNSUPPORTED, "conv_gemm tile 131 (strip): %ld rows (whole row blocks, GroupNorm slices and samples) of Y or R span 4 GB "
+                         "or more (row strides %ld / %ld elements): the launch cannot be cut into ranges below 4 GB", (long)unit, (long)p.ldy, (long)(p.R ? p.ldr : 0));
+  for (int64_t r0 = 0; r0 < p.M; r0 += per) {
+    ConvGemmParams c = p;
+    c.M = (int)(p.M - r0 < per ? p.M - r0 : per);
+    c.A = p.A + r0 * p.lda * 2;
+    c.Y = p.Y + r0 * p.ldy * 2;
+    if (p.R) c.R = p.R + r0 * p.ldr * 2;
+    if (p.stats) c.stats = p.stats + (r0 / 64) * p.stats_ld * 2;
+    if (p.gn_a) {
+      const int64_t s0 = r0 / p.gn_rows;
+      c.gn_a = p.gn_a + s0 * p.Cin;
+      c.gn_b = p.gn_b + s0 * p.Cin;
+      c.gn_S = (int)(c.M / p.gn_rows);
+    }
+    const int rc = dispatch_conv1x1_strip_rows(c, st);
+    if (rc != MMD_OK) return rc;
+  }
+  return MMD_OK;
+}
+
+static int dispatch_conv1x1_strip_rows(const ConvGemmParams& p, hipStream_t st) {
+  const int K = p.Cin * p.ntaps;
   if (K == 128) {
     // round 6: the ResBlock out conv of the ds1 levels (norm + SiLU + 1x1 + skip, 65536 / 25600 rows per sample) on 128-row blocks, four
     // per CU, instead of 256-row blocks, three per CU - 1024 blocks on 768 slots ran 1.33 rounds.  Chosen by the layer's rows per

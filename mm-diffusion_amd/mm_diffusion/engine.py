@@ -253,7 +253,7 @@ class UNetEngine:
         C = x.shape[1]
         Cout = self.params[wkey].shape[0]
         will_emit = True if (out is not None and self._rec_slice(out)[0] is not None) else None    # the launch below emits out's statistics
-        if not ops.gn_fusable(geom, C, Cout, x, will_emit, act):
+        if not ops.gn_fusable(geom, C, Cout, x, will_emit, act, out=out, residual=residual):
             # wide outputs (qkv, deep levels) outside the row-strip kernel's shapes: every column tile would redo the normalisation
             # in its loader (measured 2x slower than materialising once), so normalise once and run the plain GEMM; likewise a strip
             # GEMM whose few rows force a deep column split (ops.gn_fusable)

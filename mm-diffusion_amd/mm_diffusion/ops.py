@@ -4,6 +4,7 @@ say which kernel a launch may run on.  Every MMD_* switch read here is listed in
 Activations are 2-D torch tensors [rows, C] with stride(1) == 1 and any row stride (a column slice of a wider buffer is fine); torch
 is used for device memory and the current stream only - every arithmetic op runs in libmmd."""
 import contextlib
+import math
 import os
 
 import torch
@@ -367,9 +368,11 @@ _HALO16 = _flag("MMD_HALO16")
 def halo_tile_code(x, taps, dims):
     """130 or 133 for a launch tile 130 accepts.  Measured (tools/halo_bench.py, MI355X): the one-block-per-CU tile 133 wins from four
     channel chunks on (ds1 256->128: 193 -> 164 us, ds2 640->256: 200 -> 166 us); with two chunks its prologue and epilogue have no
-    co-resident block to hide behind (ds1 128->128: 103 vs 110 us)."""
+    co-resident block to hide behind (ds1 128->128: 103 vs 110 us).  Tile 133 stages a frame through a 32-bit buffer descriptor: a frame
+    whose rows span 2 GB or more (row strides of megabytes) stays on tile 130, which is bitwise its equal (include/mmd.h: size limits)."""
     return 133 if (_HALO16 and x.dtype == torch.bfloat16 and len(taps) == 9 and dims[1] % 16 == 0 and dims[2] % 16 == 0
-                   and x.shape[1] >= 256 and tuple(tuple(t) for t in taps) == tuple(TAPS_SPATIAL)) else 130
+                   and x.shape[1] >= 256 and tuple(tuple(t) for t in taps) == tuple(TAPS_SPATIAL)
+                   and ((dims[1] * dims[2] - 1) * x.stride(0) + x.shape[1]) * 2 < 0x7fffffff) else 130
 
 
 def _stats_args(stats, M, Cout):
@@ -407,13 +410,29 @@ def halo_tile_pinned(x, taps, dims):
 _STRIP_MODE = os.environ.get("MMD_GEMM_STRIP", "pin")
 
 
-def strip_tile_ok(x, Cout, taps=TAPS_1, stats=None, geom=None, base=False):
+def strip_cut_rows(taps=TAPS_1, dims=(1, 1, 1), geom=None):
+    """The row unit at which the library cuts a tile-131 launch whose Y / R offsets would pass 4 GB into several launches of the same
+    kernel (mmd_gemm.hip: dispatch_conv1x1_strip): whole 256-row blocks, whole GroupNorm slices, whole samples of a conv with taps."""
+    unit = 256
+    if geom is not None:
+        unit = math.lcm(unit, geom.Tn)
+    if len(taps) > 1:
+        unit = math.lcm(unit, int(dims[0]) * int(dims[1]) * int(dims[2]))
+    return unit
+
+
+def strip_tile_ok(x, Cout, taps=TAPS_1, stats=None, geom=None, base=False, dims=(1, 1, 1), out=None, residual=None):
     """Launches conv_gemm tile 131 accepts: bf16, K = ntaps * Cin in {128, 256} (two row fragments per wave, 64-channel chunks) or
     {384, 512} (one fragment, 32-channel chunks), Cin a multiple of 64; output statistics need M % 64 == 0; fused GroupNorm (1x1 convs
-    only) needs contiguous slices of at least one block of rows (256 / 128)."""
+    only) needs contiguous slices of at least one block of rows (256 / 128).  No term in the size of the launch: rows whose Y / R byte
+    offsets pass 4 GB are run as several launches of the same kernel (so a layer keeps its kernel at every batch size); only when ONE
+    cut unit (strip_cut_rows) of `out` / `residual` spans 4 GB - row strides of 8 M elements - is the launch refused."""
     M, Cin = x.shape
     K = len(taps) * Cin
     if x.dtype != torch.bfloat16 or K not in (128, 256, 384, 512) or Cin % 64:
+        return False
+    ldmax = max([t.stride(0) for t in (out, residual) if t is not None], default=0)
+    if M * ldmax * 2 >= 0xffffffff and 0xfffffffe // (ldmax * 2) < strip_cut_rows(taps, dims, geom):
         return False
     if len(taps) == 1 and tuple(taps[0]) != (0, 0, 0):
         return False
@@ -427,10 +446,10 @@ def strip_tile_ok(x, Cout, taps=TAPS_1, stats=None, geom=None, base=False):
     return True
 
 
-def strip_tile_pinned(x, Cout, taps=TAPS_1, stats=None, geom=None):
+def strip_tile_pinned(x, Cout, taps=TAPS_1, stats=None, geom=None, dims=(1, 1, 1), out=None, residual=None):
     if _STRIP_MODE == "0":
         return False
-    return strip_tile_ok(x, Cout, taps, stats, geom, base=_STRIP_MODE == "base")
+    return strip_tile_ok(x, Cout, taps, stats, geom, base=_STRIP_MODE == "base", dims=dims, out=out, residual=residual)
 
 
 def _tile_name(tile):
@@ -479,7 +498,7 @@ def conv_gemm(x, w, bias, taps=TAPS_1, dims=(1, 1, 1), residual=None, out=None, 
             int(dims[0]), int(dims[1]), int(dims[2]))
     if tile == 0 and stats is None and halo_tile_pinned(x, taps, dims):
         tile = halo_tile_code(x, taps, dims)
-    if tile == 0 and strip_tile_pinned(x, Cout, taps, stats):
+    if tile == 0 and strip_tile_pinned(x, Cout, taps, stats, dims=dims, out=out, residual=residual):
         tile = 131
     if tile == 0:
         # statistics-emitting launches stay inside the 128-row tile family: the per-record sums are folded in an order that depends on
@@ -524,7 +543,7 @@ def gn_tiled_ok(geom: Geom, Cin, Cout):
     return geom.contiguous and geom.Tn >= 128 and Cin <= 256 and (Cout + 127) // 128 <= 2
 
 
-def gn_fusable(geom: Geom, Cin, Cout, x=None, stats=None, act=False):
+def gn_fusable(geom: Geom, Cin, Cout, x=None, stats=None, act=False, out=None, residual=None):
     """Whether GroupNorm can ride in the 1x1 GEMM: in the tiled loader (contiguous slices of >= 128 rows, narrow K and N: every
     column tile redoes the normalisation) or, given the input x (and whether the launch will emit output statistics), in the
     row-strip kernel (normalises once per strip: any N).
@@ -533,8 +552,8 @@ def gn_fusable(geom: Geom, Cin, Cout, x=None, stats=None, act=False):
     what may depend on M is only whether the normalisation is FUSED: every block of a strip's column split redoes it, and with SiLU
     that is ~12 VALU instructions per element, so when few rows force a deep split (M = 4096 at 512 channels: 16 ranges, 34 us fused
     against 5 + 17 us) gn_apply + the plain strip GEMM is the faster of two bitwise-equal paths (tests/test_strip_gpu.py)."""
-    if x is not None and strip_tile_pinned(x, Cout, stats=stats):
-        if not strip_tile_pinned(x, Cout, stats=stats, geom=geom):
+    if x is not None and strip_tile_pinned(x, Cout, stats=stats, out=out, residual=residual):
+        if not strip_tile_pinned(x, Cout, stats=stats, geom=geom, out=out, residual=residual):
             return False                                   # slices the strip cannot fuse: gn_apply + strip GEMM
         return not (act and strip_column_split(x.shape[0], Cin, Cout) > 2)
     return gn_tiled_ok(geom, Cin, Cout)
@@ -551,13 +570,13 @@ def gn_conv1x1(x, a, b, geom: Geom, act, w, bias, residual=None, out=None, tile=
     es = x.element_size()
     # capability, not preference: an explicit tile is checked against what THAT main loop can do (gn_fusable is the caller's cost rule)
     tiled_ok = gn_tiled_ok(geom, Cin, Cout)
-    strip_ok = strip_tile_ok(x, Cout, stats=stats, geom=geom)
+    strip_ok = strip_tile_ok(x, Cout, stats=stats, geom=geom, out=out, residual=residual)
     if not ((tile == 131 and strip_ok) or (tile in (64, 128) and tiled_ok) or (tile == 0 and (tiled_ok or strip_ok))):
         raise H.MMDError("gn_conv1x1: needs contiguous slices of >= 128 rows, Cin <= 256 (use gn_apply + conv_gemm otherwise)")
     base = (H.dt_of(x), x.data_ptr(), x.stride(0), a.data_ptr(), b.data_ptr(), 1 if act else 0, geom.S, geom.Tn,
             w.data_ptr(), H.ptr(bias), H.ptr(residual),
             0 if residual is None else residual.stride(0), out.data_ptr(), out.stride(0), M, Cout, Cin)
-    if tile == 0 and strip_tile_pinned(x, Cout, stats=stats, geom=geom):
+    if tile == 0 and strip_tile_pinned(x, Cout, stats=stats, geom=geom, out=out, residual=residual):
         tile = 131                                         # (callers that follow gn_fusable only get here when the fusion pays)
     if tile == 0 and not tiled_ok:
         raise H.MMDError("gn_conv1x1: the row-strip kernel is switched off (MMD_GEMM_STRIP) and the tiled loader cannot take this launch")
