@@ -7,182 +7,9 @@
 //   mmd_dpm_adapt_close    x = c0 XB + c1 MS + c2 m1, and the fp64 chunk sums of the squared error terms
 //   mmd_dpm_adapt_control  E, the decision, the next s / h / t / s1, and every coefficient row the next trial reads
 //   mmd_dpm_adapt_commit   accept: PREV = LO; reject: x = XB
-// The elementwise kernels use mmd_lincomb's terms (mmd_dpm_elem.h) in its order: they write the bits of the launches they replace.
-#include "mmd_dpm_elem.h"
+// open, close and commit are step kernels and live with the other solvers' in mmd_dpm.hip; here: controller, schedule, mmd_dpm_adapt_time.
+#include "mmd_common.h"
 #include <math.h>
-
-#define ADAPT_TAB_ROWS 6
-#define ADAPT_MAX_PER ((int64_t)1 << 31)
-
-struct AdaptGeom { int N, F, C, Cm, HW; };
-// element r = (f, c, hw) of sample n in the source [N, F, Cm, HW]: its first C channels are read
-__device__ __forceinline__ int64_t adapt_src_addr(const AdaptGeom& g, int64_t n, int64_t r) {
-  const int hw = (int)(r % g.HW), c = (int)((r / g.HW) % g.C);
-  const int64_t f = r / ((int64_t)g.HW * g.C);
-  return ((n * g.F + f) * g.Cm + c) * (int64_t)g.HW + hw;
-}
-
-// The model value of a quad: X0FORM m = cx x + ce eps (mmd_dpmpp_x0's value), else the source itself, clamp-scaled by s[n] when given
-template <bool X0FORM>
-__device__ __forceinline__ void adapt_model_quad(const AdaptGeom& g, const float* __restrict__ src, bool vsrc, int64_t n, int64_t r0, int cnt,
-                                                 const float* xv, float cx, float ce, const float* __restrict__ s, float max_val, float* m) {
-  const int64_t a0 = adapt_src_addr(g, n, r0);
-  if (cnt == 4 && vsrc && !(a0 & 3) && (int)(r0 % g.HW) + 4 <= g.HW) {
-    quad_load(src + a0, 4, true, m);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (j < cnt) m[j] = src[adapt_src_addr(g, n, r0 + j)];
-  }
-  if (X0FORM) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) m[j] = lincomb_add(lincomb_first(cx, xv[j]), ce, m[j]);
-  } else if (s) {
-    const float sv = s[n];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) m[j] = clamp_scale_elem(m[j], sv, max_val);
-  }
-}
-
-struct AdaptTab { const float* tab; const int64_t* k; int rows; };
-
-// ----------------------------------------------------------------------------- open
-struct AdaptOpen {
-  float* x; const float* src; float* XB; float* MS; float* LO; const float* s;
-  float max_val;
-  int vec;      // bit 0: x, XB, MS and LO start on 16 bytes, bit 1: the source does
-};
-template <bool X0FORM>
-__global__ __launch_bounds__(256) void dpm_adapt_open_kernel(const AdaptGeom g, const AdaptTab t, const AdaptOpen q) {
-  const int64_t per = (int64_t)g.F * g.C * g.HW;
-  const int64_t ups = (per + 3) / 4, total = ups * g.N;
-  for (int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x; u < total; u += (int64_t)gridDim.x * 256) {
-    const int64_t n = u / ups, r0 = (u % ups) * 4;
-    const int64_t ki = t.k[n];
-    if (ki < 0 || ki >= t.rows) continue;
-    const float cx = t.tab[ki], ce = t.tab[t.rows + ki];
-    const float a0 = t.tab[2 * t.rows + ki], a1 = t.tab[3 * t.rows + ki], b0 = t.tab[4 * t.rows + ki], b1 = t.tab[5 * t.rows + ki];
-    const int cnt = per - r0 < 4 ? (int)(per - r0) : 4;
-    const int64_t i0 = n * per + r0;
-    const bool vx = cnt == 4 && (q.vec & 1) && !(i0 & 3);
-    float xv[4] = {}, m0[4] = {}, lo[4], nx[4];
-    quad_load(q.x + i0, cnt, vx, xv);
-    adapt_model_quad<X0FORM>(g, q.src, (q.vec & 2) != 0, n, r0, cnt, xv, cx, ce, q.s, q.max_val, m0);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      lo[j] = lincomb_add(lincomb_first(a0, xv[j]), a1, m0[j]);
-      nx[j] = lincomb_add(lincomb_first(b0, xv[j]), b1, m0[j]);
-    }
-    quad_store(q.XB + i0, cnt, vx, xv);
-    quad_store(q.MS + i0, cnt, vx, m0);
-    quad_store(q.LO + i0, cnt, vx, lo);
-    quad_store(q.x + i0, cnt, vx, nx);
-  }
-}
-
-static int adapt_geom_ok(const char* what, int rows, int N, int F, int C, int Cm, int HW) {
-  MMD_REQUIRE(rows > 0 && N > 0 && N <= 65535 && F > 0 && C > 0 && HW > 0, "%s: rows, N (<= 65535), F, C, HW must be positive", what);
-  MMD_REQUIRE(Cm == C || Cm == 2 * C, "%s: the model output has C = %d or 2C channels; got %d", what, C, Cm);
-  MMD_REQUIRE((int64_t)F * C * HW <= ADAPT_MAX_PER, "%s: sample too large", what);
-  return MMD_OK;
-}
-static int adapt_form_ok(const char* what, int form, const float* s, float max_val) {
-  MMD_REQUIRE(form == 0 || form == 1, "%s: form is 0 (the model value = the source) or 1 (= cx x + ce eps); got %d", what, form);
-  MMD_REQUIRE(!s || form == 0, "%s: thresholding (s != NULL) goes with form 0 only: the quantile is taken of the stored x0raw", what);
-  MMD_REQUIRE(!s || max_val > 0.f, "%s: max_val must be positive with thresholding (s != NULL)", what);
-  return MMD_OK;
-}
-// no two of the n buffers of `total` floats share a byte
-static bool adapt_all_disjoint(const float* const* b, int n, int64_t total) {
-  for (int i = 0; i < n; ++i)
-    for (int j = i + 1; j < n; ++j)
-      if (!dpm_disjoint(b[i], b[j], total)) return false;
-  return true;
-}
-
-extern "C" int mmd_dpm_adapt_open(float* x, const float* src, int form, float* XB, float* MS, float* LO, const float* s, float max_val,
-                                  const float* tab, const int64_t* k, int rows, int N, int F, int C, int Cm, int HW, void* stream) {
-  MMD_REQUIRE(x && src && XB && MS && LO && tab && k, "dpm_adapt_open: needs x, the source of m0, XB, MS, LO, the table and the row indices");
-  if (int rc = adapt_form_ok("dpm_adapt_open", form, s, max_val)) return rc;
-  if (int rc = adapt_geom_ok("dpm_adapt_open", rows, N, F, C, Cm, HW)) return rc;
-  const int64_t per = (int64_t)F * C * HW, total = per * N;
-  const float* bufs[4] = {x, XB, MS, LO};
-  MMD_REQUIRE(adapt_all_disjoint(bufs, 4, total), "dpm_adapt_open: x, XB, MS and LO must not overlap (all four are written)");
-  const AdaptGeom g{N, F, C, Cm, HW};
-  const AdaptOpen q{x, src, XB, MS, LO, s, max_val, (on16(x) && on16(XB) && on16(MS) && on16(LO) ? 1 : 0) | (on16(src) ? 2 : 0)};
-  const dim3 grid(ew_grid((per + 3) / 4 * N));
-  if (form == 1) return mmd_launch<dpm_adapt_open_kernel<true>>("dpm_adapt_open", grid, dim3(256), 0, (hipStream_t)stream, g, AdaptTab{tab, k, rows}, q);
-  return mmd_launch<dpm_adapt_open_kernel<false>>("dpm_adapt_open", grid, dim3(256), 0, (hipStream_t)stream, g, AdaptTab{tab, k, rows}, q);
-}
-
-// ----------------------------------------------------------------------------- close
-// params: the controller's fp64 parameter block (MMD_ADAPT_P_*); the close kernel reads atol and rtol from it, rounded to fp32 - the
-// values mmd_dpm_err takes as arguments.  The error term is dpm_err_kernel's expression, element for element.
-struct AdaptClose {
-  float* x; const float* src; const float* XB; const float* MS; const float* LO; const float* PREV; const float* s;
-  float max_val;
-  int vec;      // bit 0: x, XB, MS, LO and PREV start on 16 bytes, bit 1: the source does
-  const double* params; double* partial;
-};
-template <bool X0FORM>
-__global__ __launch_bounds__(256) void dpm_adapt_close_kernel(const AdaptGeom g, const AdaptTab t, const AdaptClose q) {
-  __shared__ double red[256];
-  const int tid = threadIdx.x;
-  const int64_t n = blockIdx.y;
-  const int64_t ki = t.k[n];
-  if (ki < 0 || ki >= t.rows) return;          // uniform over the workgroup: a finished sample writes neither x nor its partial sums
-  const int64_t per = (int64_t)g.F * g.C * g.HW;
-  const float cx = t.tab[ki], ce = t.tab[t.rows + ki];
-  const float c0 = t.tab[2 * t.rows + ki], c1 = t.tab[3 * t.rows + ki], c2 = t.tab[4 * t.rows + ki];
-  const float atol = (float)q.params[MMD_ADAPT_P_ATOL], rtol = (float)q.params[MMD_ADAPT_P_RTOL];
-  const int64_t lo_r = (int64_t)blockIdx.x * MMD_DPM_ADAPT_CHUNK, hi_r = lo_r + MMD_DPM_ADAPT_CHUNK < per ? lo_r + MMD_DPM_ADAPT_CHUNK : per;
-  double acc = 0.0;
-  for (int64_t r0 = lo_r + (int64_t)tid * 4; r0 < hi_r; r0 += 256 * 4) {
-    const int cnt = hi_r - r0 < 4 ? (int)(hi_r - r0) : 4;
-    const int64_t i0 = n * per + r0;
-    const bool vx = cnt == 4 && (q.vec & 1) && !(i0 & 3);
-    float xv[4] = {}, xb[4] = {}, ms[4] = {}, lo[4] = {}, pv[4] = {}, m1[4] = {}, v[4];
-    if (X0FORM) quad_load(q.x + i0, cnt, vx, xv);
-    quad_load(q.XB + i0, cnt, vx, xb);
-    quad_load(q.MS + i0, cnt, vx, ms);
-    quad_load(q.LO + i0, cnt, vx, lo);
-    quad_load(q.PREV + i0, cnt, vx, pv);
-    adapt_model_quad<X0FORM>(g, q.src, (q.vec & 2) != 0, n, r0, cnt, xv, cx, ce, q.s, q.max_val, m1);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      v[j] = lincomb_add(lincomb_add(lincomb_first(c0, xb[j]), c1, ms[j]), c2, m1[j]);
-      if (j < cnt) {      // ascending element order inside the thread
-        const float delta = fmaxf(atol, rtol * fmaxf(fabsf(lo[j]), fabsf(pv[j])));
-        const float e = (v[j] - lo[j]) / delta;
-        acc += (double)e * (double)e;
-      }
-    }
-    quad_store(q.x + i0, cnt, vx, v);
-  }
-  red[tid] = acc;
-  block_tree_sum256(tid, red);
-  if (tid == 0) q.partial[n * gridDim.x + blockIdx.x] = red[0];
-}
-
-extern "C" int64_t mmd_dpm_adapt_chunks(int64_t per_sample) { return per_sample > 0 ? (per_sample + MMD_DPM_ADAPT_CHUNK - 1) / MMD_DPM_ADAPT_CHUNK : 0; }
-
-extern "C" int mmd_dpm_adapt_close(float* x, const float* src, int form, const float* XB, const float* MS, const float* LO, const float* PREV,
-                                   const float* s, float max_val, const float* tab, const int64_t* k, int rows, const double* params,
-                                   double* partial, int N, int F, int C, int Cm, int HW, void* stream) {
-  MMD_REQUIRE(x && src && XB && MS && LO && PREV && tab && k, "dpm_adapt_close: needs x, the source of m1, XB, MS, LO, PREV, the table and the row indices");
-  MMD_REQUIRE(params && partial, "dpm_adapt_close: needs the parameter block and the partial sums [N, chunks]");
-  if (int rc = adapt_form_ok("dpm_adapt_close", form, s, max_val)) return rc;
-  if (int rc = adapt_geom_ok("dpm_adapt_close", rows, N, F, C, Cm, HW)) return rc;
-  const int64_t per = (int64_t)F * C * HW, total = per * N;
-  const float* bufs[5] = {x, XB, MS, LO, PREV};
-  MMD_REQUIRE(adapt_all_disjoint(bufs, 5, total), "dpm_adapt_close: x, XB, MS, LO and PREV must not overlap (x is written while the others are read)");
-  const AdaptGeom g{N, F, C, Cm, HW};
-  const AdaptClose q{x, src, XB, MS, LO, PREV, s, max_val, (on16(x) && on16(XB) && on16(MS) && on16(LO) && on16(PREV) ? 1 : 0) | (on16(src) ? 2 : 0),
-                     params, partial};
-  const dim3 grid((unsigned)mmd_dpm_adapt_chunks(per), N);
-  if (form == 1) return mmd_launch<dpm_adapt_close_kernel<true>>("dpm_adapt_close", grid, dim3(256), 0, (hipStream_t)stream, g, AdaptTab{tab, k, rows}, q);
-  return mmd_launch<dpm_adapt_close_kernel<false>>("dpm_adapt_close", grid, dim3(256), 0, (hipStream_t)stream, g, AdaptTab{tab, k, rows}, q);
-}
 
 // ----------------------------------------------------------------------------- the controller
 // The discrete VP schedule in fp64 (NoiseScheduleVP's 'discrete' family): log alpha is known at t_i = (i + 1) / T and linear in between,
@@ -390,37 +217,4 @@ extern "C" int mmd_dpm_adapt_time(const int64_t* src, int64_t* dst, int N, void*
   MMD_REQUIRE(src && dst && N > 0 && N <= 65535, "dpm_adapt_time: needs src, dst and N in [1, 65535]");
   MMD_REQUIRE((uintptr_t)src + (uintptr_t)N * 8 <= (uintptr_t)dst || (uintptr_t)dst + (uintptr_t)N * 8 <= (uintptr_t)src, "dpm_adapt_time: src and dst overlap");
   return mmd_launch<dpm_adapt_time_kernel>("dpm_adapt_time", dim3(cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, src, dst, N);
-}
-
-// ----------------------------------------------------------------------------- commit
-__global__ __launch_bounds__(256) void dpm_adapt_commit_kernel(float* x, const float* __restrict__ XB, float* PREV, const float* __restrict__ LO,
-                                                               const int32_t* __restrict__ cnt, int N, int64_t per, int vec) {
-  const int64_t ups = (per + 3) / 4, total = ups * N;
-  for (int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x; u < total; u += (int64_t)gridDim.x * 256) {
-    const int64_t n = u / ups, r0 = (u % ups) * 4;
-    const int flag = cnt[4 * n + MMD_ADAPT_C_FLAG];
-    if (flag != MMD_ADAPT_FLAG_ACCEPT && flag != MMD_ADAPT_FLAG_REJECT) continue;
-    const int cnt4 = per - r0 < 4 ? (int)(per - r0) : 4;
-    const int64_t i0 = n * per + r0;
-    const bool vx = cnt4 == 4 && vec && !(i0 & 3);
-    float v[4] = {};
-    if (flag == MMD_ADAPT_FLAG_ACCEPT) {
-      quad_load(LO + i0, cnt4, vx, v);
-      quad_store(PREV + i0, cnt4, vx, v);
-    } else {
-      quad_load(XB + i0, cnt4, vx, v);
-      quad_store(x + i0, cnt4, vx, v);
-    }
-  }
-}
-
-extern "C" int mmd_dpm_adapt_commit(float* x, const float* XB, float* PREV, const float* LO, const int32_t* cnt, int N, int64_t per_sample,
-                                    void* stream) {
-  MMD_REQUIRE(x && XB && PREV && LO && cnt, "dpm_adapt_commit: needs x, XB, PREV, LO and the counters");
-  MMD_REQUIRE(N > 0 && N <= 65535 && per_sample > 0 && per_sample <= ADAPT_MAX_PER, "dpm_adapt_commit: N in [1, 65535], per_sample in [1, 2^31]");
-  const float* bufs[4] = {x, XB, PREV, LO};
-  MMD_REQUIRE(adapt_all_disjoint(bufs, 4, per_sample * N), "dpm_adapt_commit: x, XB, PREV and LO must not overlap");
-  const int vec = on16(x) && on16(XB) && on16(PREV) && on16(LO) ? 1 : 0;
-  return mmd_launch<dpm_adapt_commit_kernel>("dpm_adapt_commit", dim3(ew_grid((per_sample + 3) / 4 * N)), dim3(256), 0, (hipStream_t)stream, x, XB,
-                                             PREV, LO, cnt, N, per_sample, vec);
 }

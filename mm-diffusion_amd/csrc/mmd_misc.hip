@@ -1,7 +1,8 @@
 // Small kernels around the U-Net that belong to neither a convolution nor the diffusion process:
 //   timestep embedding + MLP (nn.py:192-210, multimodal_unet.py:791-795,1075), batched emb_layers Linear (unet:366-372),
 //   avg-pool / nearest resampling (unet:133-208) with and without GroupNorm statistics, skip-concat copies (unet:1093-1094) and the
-//   gradient payload cast.  The layout-edge convolutions are in mmd_edge.hip, the diffusion process in mmd_diffusion.hip.
+//   gradient payload cast.  The layout-edge convolutions are in mmd_edge.hip, the diffusion process in mmd_diffusion.hip,
+//   the DPM-Solver kernels in mmd_dpm.hip.
 #include "mmd_common.h"
 
 // ----------------------------------------------------------------------------- timestep embedding + MLP

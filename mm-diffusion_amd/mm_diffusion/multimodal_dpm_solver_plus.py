@@ -720,24 +720,12 @@ class DPM_Solver:
         t_0, t_T = 1. / self.noise_schedule.total_N, self.noise_schedule.T
         grid = self.get_time_steps(skip_type=skip_type, t_T=t_T, t_0=t_0, N=steps, device="cpu")
         times = [grid[i:i + 1] for i in range(steps + 1)]
-        evals = times[:steps] + ([torch.ones((1,)) * t_0] if denoise else [])
-        rows = len(evals)
-        tab = {k: np.zeros((ops.DPMPP_TAB_ROWS, rows), dtype=np.float32) for k in self.KEYS}
-        cz = {k: np.zeros(rows, dtype=np.float32) for k in self.KEYS}
-        tab2 = np.zeros((2, rows), dtype=np.float32)
-        for i, t in enumerate(evals):
-            tab2[:, i] = self._alpha_sigma(t)
-            if i == steps:
-                c, z = (0.0, 0.0, 0.0, ops.DPMPP_KIND_DENOISE), 0.0
-            else:
-                second = order == 2 and i > 0
-                c0, c1, c2, z = self._sde_coefs(times[i - 1] if second else None, times[i], times[i + 1])
-                c = (c0, c1, c2, ops.DPMPP_KIND_SECOND if second else ops.DPMPP_KIND_FIRST)
-            for k in self.KEYS:
-                tab[k][:, i] = self._x0_coefs(t) + c
-                cz[k][i] = z
-        tm = self.model.get_model_input_time(torch.cat(evals).to(device))
-        return {"rows": rows, "timesteps": torch.cat(evals), "tab": tab, "tab2": tab2, "cz": cz, "tm": [int(v) for v in tm.cpu()]}
+        evals, cz = [], np.zeros(steps + (1 if denoise else 0), dtype=np.float32)
+        for i in range(steps):
+            second = order == 2 and i > 0
+            c0, c1, c2, cz[i] = self._sde_coefs(times[i - 1] if second else None, times[i], times[i + 1])
+            evals.append((times[i], self._same((c0, c1, c2, ops.DPMPP_KIND_SECOND if second else ops.DPMPP_KIND_FIRST))))
+        return self._eval_tables(np, evals, denoise, device, cz=cz)
 
     def sample_graph_sde(self, x_T=None, *, shape=None, steps, order=2, skip_type="logSNR", denoise=False, known=None, mask=None,
                          noise_source=None, paste_known=True, use_graph=True, lanes=None):
@@ -773,23 +761,39 @@ class DPM_Solver:
         t_0, t_T = 1. / self.noise_schedule.total_N, self.noise_schedule.T
         grid = self.get_time_steps(skip_type=skip_type, t_T=t_T, t_0=t_0, N=steps, device="cpu")
         times = [grid[i:i + 1] for i in range(steps + 1)]
-        evals = times[:steps] + ([torch.ones((1,)) * t_0] if denoise else [])
+        evals = []
+        for i in range(steps):
+            if i == 0 or order == 1:      # per stream: the noise-prediction form moves the audio stream with other coefficients (_first_coefs)
+                c = {k: v + (0.0, ops.DPMPP_KIND_FIRST) for k, v in self._first_coefs(times[i], times[i + 1]).items()}
+            else:
+                c = self._same(self._second_coefs(times[i - 1], times[i], times[i + 1], solver_type) + (ops.DPMPP_KIND_SECOND,))
+            evals.append((times[i], c))
+        return self._eval_tables(np, evals, denoise, device)
+
+    def _same(self, c):
+        return {k: c for k in self.KEYS}
+
+    def _eval_tables(self, np, evals, denoise, device, cz=None):
+        """The tables dictionary of graph_tables from evals = [(time [1], {stream: (c0, c1, c2, kind)})], one entry per network evaluation
+        in the loop's order; denoise: one more row at t_0, the final data prediction.  Slots 0, 1 of a row are the data prediction's
+        (cx, ce) where the row's model value is one (predict_x0, and the denoise row of either form), else zeros.  cz: float32 [rows], the
+        rows' noise coefficients (sde_tables), the same for every stream."""
+        if denoise:
+            evals = evals + [(torch.ones((1,)) * (1. / self.noise_schedule.total_N), self._same((0.0, 0.0, 0.0, ops.DPMPP_KIND_DENOISE)))]
         rows = len(evals)
         tab = {k: np.zeros((ops.DPMPP_TAB_ROWS, rows), dtype=np.float32) for k in self.KEYS}
         tab2 = np.zeros((2, rows), dtype=np.float32)
-        for i, t in enumerate(evals):
-            tab2[:, i] = self._alpha_sigma(t)
-            cx, ce = self._x0_coefs(t) if (self.predict_x0 or i == steps) else (0.0, 0.0)
-            if i == steps:
-                c = {k: (0.0, 0.0, 0.0, ops.DPMPP_KIND_DENOISE) for k in self.KEYS}
-            elif i == 0 or order == 1:
-                c = {k: v + (0.0, ops.DPMPP_KIND_FIRST) for k, v in self._first_coefs(times[i], times[i + 1]).items()}
-            else:
-                c = {k: self._second_coefs(times[i - 1], times[i], times[i + 1], solver_type) + (ops.DPMPP_KIND_SECOND,) for k in self.KEYS}
+        for j, (tau, c) in enumerate(evals):
+            tab2[:, j] = self._alpha_sigma(tau)
+            cx, ce = self._x0_coefs(tau) if (self.predict_x0 or c[self.KEYS[0]][3] == ops.DPMPP_KIND_DENOISE) else (0.0, 0.0)
             for k in self.KEYS:
-                tab[k][:, i] = (cx, ce) + tuple(c[k])
-        tm = self.model.get_model_input_time(torch.cat(evals).to(device))
-        return {"rows": rows, "timesteps": torch.cat(evals), "tab": tab, "tab2": tab2, "tm": [int(v) for v in tm.cpu()]}
+                tab[k][:, j] = (cx, ce) + tuple(c[k])
+        times = torch.cat([tau.reshape(-1)[:1] for tau, _ in evals])
+        tm = self.model.get_model_input_time(times.to(device))
+        out = {"rows": rows, "timesteps": times, "tab": tab, "tab2": tab2, "tm": [int(v) for v in tm.cpu()]}
+        if cz is not None:
+            out["cz"] = {k: cz.copy() for k in self.KEYS}
+        return out
 
     def _graph_check(self, steps, order, solver_type):
         if order not in (1, 2):
@@ -935,7 +939,7 @@ class DPM_Solver:
     def _build_single_tables(self, np, steps, order, skip_type, method, solver_type, denoise, device):
         t_0, t_T = 1. / self.noise_schedule.total_N, self.noise_schedule.T
         orders, grid = self._single_grid(steps, order, skip_type, method, t_T, t_0)
-        OPEN, STAGE, same = ops.DPM1_KIND_OPEN, ops.DPM1_KIND_STAGE, lambda c: {k: c for k in self.KEYS}      # noqa: E731
+        OPEN, STAGE, same = ops.DPM1_KIND_OPEN, ops.DPM1_KIND_STAGE, self._same
         evals = []          # (time [1], {stream: (c0, c1, c2, kind)})
         i = 0
         for p in orders:
@@ -950,19 +954,7 @@ class DPM_Solver:
                 s1, s2, first, mid, last = self._single_third_coefs(s, t, r1, r2, solver_type)
                 evals += [(s, same(first + (0.0, OPEN))), (s1, same(mid + (STAGE,))), (s2, same(last + (STAGE,)))]
             i += p
-        if denoise:
-            evals.append((torch.ones((1,)) * t_0, same((0.0, 0.0, 0.0, ops.DPM1_KIND_DENOISE))))
-        rows = len(evals)
-        tab = {k: np.zeros((ops.DPMPP_TAB_ROWS, rows), dtype=np.float32) for k in self.KEYS}
-        tab2 = np.zeros((2, rows), dtype=np.float32)
-        for j, (tau, c) in enumerate(evals):
-            tab2[:, j] = self._alpha_sigma(tau)
-            cx, ce = self._x0_coefs(tau) if (self.predict_x0 or c[self.KEYS[0]][3] == ops.DPM1_KIND_DENOISE) else (0.0, 0.0)
-            for k in self.KEYS:
-                tab[k][:, j] = (cx, ce) + tuple(c[k])
-        times = torch.cat([tau.reshape(-1)[:1] for tau, _ in evals])
-        tm = self.model.get_model_input_time(times.to(device))
-        return {"rows": rows, "timesteps": times, "tab": tab, "tab2": tab2, "tm": [int(v) for v in tm.cpu()]}
+        return self._eval_tables(np, evals, denoise, device)
 
     def sample_graph_singlestep(self, x_T=None, *, shape=None, steps, order=3, skip_type="logSNR", method="singlestep", solver_type="dpm_solver",
                                 denoise=False, known=None, mask=None, noise_source=None, paste_known=True, use_graph=True, lanes=None):

@@ -1270,6 +1270,20 @@ def _dpmpp_args(name, tab, k, N, fp32):
             raise H.MMDError(f"{name}: {what} must be contiguous fp32")
 
 
+def _step_args(name, state, src, tab, k, F, C, Cm, HW, form=0, s=None, src_name="src", what=None, extra=()):
+    """The argument check of the step kernels: state = ((name, tensor or None), ...), the [N,F,C,HW] buffers, x first; src [N,F,Cm,HW],
+    the source of the model value (form, s: dpm_single_update); extra: fp32 tensors of other sizes; what: the message's name of the state."""
+    state = tuple((w, v) for w, v in state if v is not None)
+    N = state[0][1].shape[0]
+    _dpmpp_args(name, tab, k, N, state[:1] + ((src_name, src),) + state[1:] + (("s", s),) + tuple(extra))
+    if form not in (0, 1) or (s is not None and form != 0):
+        raise H.MMDError(f"{name}: form is 0 or 1, and s goes with form 0 only")
+    if any(v.numel() != N * F * C * HW for _, v in state) or src.numel() != N * F * Cm * HW or (s is not None and s.numel() != N):
+        raise H.MMDError(f"{name}: {what or ' / '.join(w for w, _ in state)} must hold N F C HW = {N * F * C * HW}, {src_name} N F Cm HW = "
+                         f"{N * F * Cm * HW} elements and s one per sample")
+    return N
+
+
 def dpmpp_x0(x, model_out, x0raw, tab, k, F, C, Cm, HW, hist=None):
     """x0raw = cx[k] x + ce[k] eps (eps = the first C of the model output's Cm channels); hist = a dpmpp_workspace: the same pass adds
     level 0 of the selection to it."""
@@ -1310,10 +1324,7 @@ def dpmpp_update(x, m0, M1, tab, k, F, C, Cm, HW, s=None, max_val=1.0):
     """In place x = c0[k] x + c1[k] m0 + c2[k] M1 by the row's kind (include/mmd.h), M1 = m0; m0 [N,F,Cm,HW] is clamp-scaled by s [N] first
     when s is given."""
     H.require_cuda(x, m0, M1, tab, k, s)
-    N = x.shape[0]
-    _dpmpp_args("dpmpp_update", tab, k, N, (("x", x), ("m0", m0), ("M1", M1), ("s", s)))
-    if x.numel() != N * F * C * HW or M1.numel() != x.numel() or m0.numel() != N * F * Cm * HW or (s is not None and s.numel() != N):
-        raise H.MMDError(f"dpmpp_update: x / M1 must hold N F C HW = {N * F * C * HW}, m0 N F Cm HW = {N * F * Cm * HW} elements and s one per sample")
+    N = _step_args("dpmpp_update", (("x", x), ("M1", M1)), m0, tab, k, F, C, Cm, HW, s=s, src_name="m0")
     _dispatch("mmd_dpmpp_update", x.data_ptr(), m0.data_ptr(), M1.data_ptr(), H.ptr(s), float(max_val), tab.data_ptr(), k.data_ptr(), tab.shape[1],
               N, F, C, Cm, HW, meta=("dpmpp_update", 0, 20 * x.numel()))
     return x
@@ -1327,14 +1338,10 @@ def dpmpp_sde_update(x, m0, M1, tab, cz, k, F, C, Cm, HW, noise=None, ctr=None, 
         raise H.MMDError("dpmpp_sde_update: give exactly one of noise and ctr=(key, ids, tag)")
     key, ids, tag = ctr if ctr is not None else (None, None, 0)
     H.require_cuda(x, m0, M1, tab, cz, k, s, noise, key, ids)
-    N = x.shape[0]
-    _dpmpp_args("dpmpp_sde_update", tab, k, N, (("x", x), ("m0", m0), ("M1", M1), ("s", s), ("cz", cz), ("noise", noise)))
+    N = _step_args("dpmpp_sde_update", (("x", x), ("M1", M1), ("noise", noise)), m0, tab, k, F, C, Cm, HW, s=s, src_name="m0",
+                   what="x / M1 / noise", extra=(("cz", cz),))
     if cz.numel() != tab.shape[1]:
         raise H.MMDError(f"dpmpp_sde_update: cz must hold one coefficient per table row ({tab.shape[1]}), got {cz.numel()}")
-    if x.numel() != N * F * C * HW or M1.numel() != x.numel() or m0.numel() != N * F * Cm * HW or (s is not None and s.numel() != N) or \
-            (noise is not None and noise.numel() != x.numel()):
-        raise H.MMDError(f"dpmpp_sde_update: x / M1 / noise must hold N F C HW = {N * F * C * HW}, m0 N F Cm HW = {N * F * Cm * HW} elements and s "
-                         "one per sample")
     if ctr is None:
         _dispatch("mmd_dpmpp_sde_update", x.data_ptr(), m0.data_ptr(), M1.data_ptr(), noise.data_ptr(), H.ptr(s), float(max_val), tab.data_ptr(),
                   cz.data_ptr(), k.data_ptr(), tab.shape[1], N, F, C, Cm, HW, meta=("dpmpp_sde_update", 0, 24 * x.numel()))
@@ -1371,6 +1378,7 @@ def slerp(a, b, lam, out=None, ws=None):
 
 
 DPM1_KIND_OPEN, DPM1_KIND_STAGE, DPM1_KIND_DENOISE = 0, 1, 2     # row kinds of mmd_dpm_single_update (include/mmd.h)
+assert DPM1_KIND_DENOISE == DPMPP_KIND_DENOISE                    # one table builder marks the denoise row of both (_eval_tables)
 
 
 def dpm_single_update(x, src, XB, MS, tab, k, F, C, Cm, HW, form=0, s=None, max_val=1.0):
@@ -1378,14 +1386,7 @@ def dpm_single_update(x, src, XB, MS, tab, k, F, C, Cm, HW, form=0, s=None, max_
     stage x = c0[k] XB + c1[k] MS + c2[k] m0; denoise x = m0.  form 0: m0 = the first C of src's Cm channels [N,F,Cm,HW], clamp-scaled by
     s [N] when s is given; form 1: m0 = cx[k] x + ce[k] eps with eps = those channels (no s)."""
     H.require_cuda(x, src, XB, MS, tab, k, s)
-    N = x.shape[0]
-    _dpmpp_args("dpm_single_update", tab, k, N, (("x", x), ("src", src), ("XB", XB), ("MS", MS), ("s", s)))
-    if form not in (0, 1) or (s is not None and form != 0):
-        raise H.MMDError("dpm_single_update: form is 0 or 1, and s goes with form 0 only")
-    if x.numel() != N * F * C * HW or XB.numel() != x.numel() or MS.numel() != x.numel() or src.numel() != N * F * Cm * HW or \
-            (s is not None and s.numel() != N):
-        raise H.MMDError(f"dpm_single_update: x / XB / MS must hold N F C HW = {N * F * C * HW}, src N F Cm HW = {N * F * Cm * HW} elements and s "
-                         "one per sample")
+    N = _step_args("dpm_single_update", (("x", x), ("XB", XB), ("MS", MS)), src, tab, k, F, C, Cm, HW, form, s)
     _dispatch("mmd_dpm_single_update", x.data_ptr(), src.data_ptr(), int(form), XB.data_ptr(), MS.data_ptr(), H.ptr(s), float(max_val),
               tab.data_ptr(), k.data_ptr(), tab.shape[1], N, F, C, Cm, HW, meta=("dpm_single_update", 0, 24 * x.numel()))
     return x
@@ -1443,23 +1444,11 @@ class AdaptBlock:
         self.tab_open, self.tab_close, self.q_s, self.q_s1 = self.ftab[0:6], self.ftab[6:12], self.ftab[12:14], self.ftab[14:16]
 
 
-def _adapt_args(name, x, src, others, tab, k, F, C, Cm, HW, form, s):
-    N = x.shape[0]
-    _dpmpp_args(name, tab, k, N, (("x", x), ("src", src), ("s", s)) + tuple(others))
-    if form not in (0, 1) or (s is not None and form != 0):
-        raise H.MMDError(f"{name}: form is 0 or 1, and s goes with form 0 only")
-    if x.numel() != N * F * C * HW or any(v.numel() != x.numel() for _, v in others) or src.numel() != N * F * Cm * HW or \
-            (s is not None and s.numel() != N):
-        raise H.MMDError(f"{name}: x and {' / '.join(w for w, _ in others)} must hold N F C HW = {N * F * C * HW}, src N F Cm HW = "
-                         f"{N * F * Cm * HW} elements and s one per sample")
-    return N
-
-
 def dpm_adapt_open(x, src, XB, MS, LO, tab, k, F, C, Cm, HW, form=0, s=None, max_val=1.0):
     """The first evaluation of an adaptive trial step, in place (include/mmd.h: mmd_dpm_adapt_open): XB = x, MS = m0, LO = a0[k] x + a1[k] m0,
     x = b0[k] x + b1[k] m0; tab rows = cx, ce, a0, a1, b0, b1; m0 as in dpm_single_update (form, s, max_val)."""
     H.require_cuda(x, src, XB, MS, LO, tab, k, s)
-    N = _adapt_args("dpm_adapt_open", x, src, (("XB", XB), ("MS", MS), ("LO", LO)), tab, k, F, C, Cm, HW, form, s)
+    N = _step_args("dpm_adapt_open", (("x", x), ("XB", XB), ("MS", MS), ("LO", LO)), src, tab, k, F, C, Cm, HW, form, s, what="x and XB / MS / LO")
     _dispatch("mmd_dpm_adapt_open", x.data_ptr(), src.data_ptr(), int(form), XB.data_ptr(), MS.data_ptr(), LO.data_ptr(), H.ptr(s), float(max_val),
               tab.data_ptr(), k.data_ptr(), tab.shape[1], N, F, C, Cm, HW, meta=("dpm_adapt_open", 0, 24 * x.numel()))
     return x
@@ -1470,7 +1459,8 @@ def dpm_adapt_close(x, src, XB, MS, LO, PREV, tab, k, params, partial, F, C, Cm,
     partial[n, chunk] = the fp64 sum of ((x - LO) / max(atol, rtol max(|LO|, |PREV|)))^2 over that chunk; tab rows = cx, ce, c0, c1, c2;
     params: dpm_adapt_params' block; partial: fp64 [N, dpm_adapt_chunks(F C HW)]."""
     H.require_cuda(x, src, XB, MS, LO, PREV, tab, k, s, params, partial)
-    N = _adapt_args("dpm_adapt_close", x, src, (("XB", XB), ("MS", MS), ("LO", LO), ("PREV", PREV)), tab, k, F, C, Cm, HW, form, s)
+    N = _step_args("dpm_adapt_close", (("x", x), ("XB", XB), ("MS", MS), ("LO", LO), ("PREV", PREV)), src, tab, k, F, C, Cm, HW, form, s,
+                   what="x and XB / MS / LO / PREV")
     if params.dtype != torch.float64 or params.numel() != ADAPT_PARAMS or not params.is_contiguous():
         raise H.MMDError(f"dpm_adapt_close: params must be the contiguous fp64 [{ADAPT_PARAMS}] parameter block")
     if partial.dtype != torch.float64 or not partial.is_contiguous() or partial.numel() != N * dpm_adapt_chunks(F * C * HW):

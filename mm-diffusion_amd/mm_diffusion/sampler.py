@@ -501,7 +501,52 @@ class GraphStepper(LaneStepper):
 DPMPP_SELECT = "multi"
 
 
-class SolverStepper(LaneStepper):
+class SolverLanes(LaneStepper):
+    """What the replayed DPM-Solver steppers share besides the lanes: geometry, the model-value recorder, the counter source's refresh."""
+
+    def __init__(self, unet, batch, device, lanes, use_graph, ctr, select):
+        self.select = DPMPP_SELECT if select is None else select
+        if self.select not in ("multi", "block"):
+            raise H.MMDError(f"unknown selection {select!r} (multi or block)")
+        super().__init__(unet, batch, device, lanes, use_graph, ctr=ctr, own_ids=True)      # own ids: retable() refills them
+        self.diff = None
+
+    def _geom(self):
+        e, unet = self.eng, self.unet          # {stream: (F, C, Cm, HW)}: the state is [n, F, C, HW], the model output [n, F, Cm, HW]
+        return {"video": (e.F, e.Cv_in, unet.video_out_channels, e.H0 * e.W0), "audio": (1, e.Ca_in, unet.audio_out_channels, e.L0)}
+
+    def _record_model_value(self, xk, ok, b, tab, rows, geom, data_form, thresholding, fused):
+        """Record what runs before one stream's update and return (src, form, s, Cm), the update's source of the model value: the model
+        output ok - form 1 where a fused update forms the data prediction itself (include/mmd.h: mmd_dpm_single_update) - or, where
+        the prediction is stored (thresholding; an update that is not fused), b["x0"] of mmd_dpmpp_x0 with the selected scale b["s"]."""
+        F, C, Cm, HW = geom
+        if not data_form or (fused and not thresholding):
+            return ok, 1 if data_form else 0, None, Cm
+        multi = thresholding and self.select == "multi"
+        ops.dpmpp_x0(xk, ok, b["x0"], tab, rows, F, C, Cm, HW, hist=b["ws"] if multi else None)
+        if multi:
+            ops.dpmpp_select(b["x0"], 0.995, b["s"], b["ws"], level0_done=True)      # p of the Imagen paper
+        elif thresholding:
+            ops.abs_quantile(b["x0"], 0.995, out=b["s"])
+        return b["x0"], 0, b["s"] if thresholding else None, C
+
+    def _load_ctr(self, ctr):
+        if (ctr is None) != (self.ctr is None):
+            raise H.MMDError("the noise source's kind is fixed when the stepper is built")
+        self.ctr = ctr
+        if ctr is not None:
+            self.key.copy_(ctr.key(self.device))
+            self.ids.copy_(ctr.ids(self.N, self.device))
+
+    def usable(self):
+        """False once the model has rebuilt its engines (new weights, another dtype): the recorded plans then point at retired buffers."""
+        try:
+            return all(self.unet.engine(self.n, self.device, replica=r) is e for r, e in enumerate(self.engs))
+        except Exception:
+            return False
+
+
+class SolverStepper(SolverLanes):
     """One evaluation of a fixed-grid DPM-Solver / DPM-Solver++ loop as one graph replay per lane: [mmd_cond_replace of each conditioned
     stream] + U-Net plan + per stream on its own stream [the model value m0 + the solver's update] + join.  Every coefficient sits in
     device tables (fp32 [6, rows] per stream, include/mmd.h), indexed by the evaluation number in t_idx, so the graph of one evaluation
@@ -519,18 +564,13 @@ class SolverStepper(LaneStepper):
     WHO = "sample_graph"
 
     def __init__(self, solver, unet, batch, device, tabs, use_graph=True, lanes=None, cond=None, ctr=None, select=None):
-        select = DPMPP_SELECT if select is None else select
-        if select not in ("multi", "block"):
-            raise H.MMDError(f"unknown selection {select!r} (multi or block)")
-        super().__init__(unet, batch, device, lanes, use_graph, ctr=ctr, own_ids=True)      # own ids: retable() refills them
-        self.diff = None
+        super().__init__(unet, batch, device, lanes, use_graph, ctr, select)
         self.tab = {k: th.zeros(ops.DPMPP_TAB_ROWS, self.ROWS_CAP, dtype=th.float32, device=self.device) for k in ("video", "audio")}
         self._qtab = th.zeros(2, self.ROWS_CAP, dtype=th.float32, device=self.device)
         self.retable(tabs, ctr)
         self._record_cond(cond, self._qtab)
-        n, e = self.n, self.eng
+        n, geom = self.n, self._geom()
         self._prepare()
-        geom = {"video": (e.F, e.Cv_in, unet.video_out_channels, e.H0 * e.W0), "audio": (1, e.Ca_in, unet.audio_out_channels, e.L0)}
         self.predict_x0 = predict_x0 = bool(solver.predict_x0)
         thresholding, max_val = bool(solver.thresholding), float(solver.max_val)
         self.has_final = not predict_x0      # the noise-prediction solver's denoise row needs the data-prediction plan
@@ -550,18 +590,10 @@ class SolverStepper(LaneStepper):
                 plan = []
                 with ops.recording(plan):
                     for sid, k, xk, ok, b in streams:
-                        Fk, C, Cm, HWk = geom[k]
+                        Fk, C, _, HWk = geom[k]
                         with ops.on_stream(sid):
-                            if data_form and (thresholding or not self.FUSED_X0):
-                                multi = thresholding and select == "multi"
-                                ops.dpmpp_x0(xk, ok, b["x0"], self.tab[k], t_idx, Fk, C, Cm, HWk, hist=b["ws"] if multi else None)
-                                if multi:
-                                    ops.dpmpp_select(b["x0"], 0.995, b["s"], b["ws"], level0_done=True)      # p of the Imagen paper
-                                elif thresholding:
-                                    ops.abs_quantile(b["x0"], 0.995, out=b["s"])
-                                self._update(xk, b["x0"], False, b, self.tab[k], t_idx, Fk, C, C, HWk, b["s"] if thresholding else None, max_val)
-                            else:
-                                self._update(xk, ok, data_form, b, self.tab[k], t_idx, Fk, C, Cm, HWk, None, max_val)
+                            src, form, s, Cm = self._record_model_value(xk, ok, b, self.tab[k], t_idx, geom[k], data_form, thresholding, self.FUSED_X0)
+                            self._update(xk, src, form == 1, b, self.tab[k], t_idx, Fk, C, Cm, HWk, s, max_val)
                     ops.record_sync(1, 0)
                 return plan
             self.update_plans.append(record(predict_x0))
@@ -586,24 +618,12 @@ class SolverStepper(LaneStepper):
         recorded plans read."""
         if tabs["rows"] > self.ROWS_CAP:
             raise H.MMDError(f"{self.WHO}: {tabs['rows']} evaluations exceed the table capacity of {self.ROWS_CAP} rows")
-        if (ctr is None) != (self.ctr is None):
-            raise H.MMDError("the noise source's kind is fixed when the stepper is built")
+        self._load_ctr(ctr)
         self.rows, self.tm = tabs["rows"], tabs["tm"]
         for k in ("video", "audio"):
             self.tab[k][:, :self.rows].copy_(th.from_numpy(tabs["tab"][k]))
         self._qtab[:, :self.rows].copy_(th.from_numpy(tabs["tab2"]))
         self.kinds = [int(v) for v in tabs["tab"]["video"][5]]
-        self.ctr = ctr
-        if ctr is not None:
-            self.key.copy_(ctr.key(self.device))
-            self.ids.copy_(ctr.ids(self.N, self.device))
-
-    def usable(self):
-        """False once the model has rebuilt its engines (new weights, another dtype): the recorded plans then point at retired buffers."""
-        try:
-            return all(self.unet.engine(self.n, self.device, replica=r) is e for r, e in enumerate(self.engs))
-        except Exception:
-            return False
 
     def set_step(self, i, shifts=None, noise=None):
         """Refresh the per-evaluation device state: the step number, the model timestep and the window shifts (one draw per
@@ -690,7 +710,7 @@ class DpmppSdeStepper(SolverStepper):
                     self.noise[k].normal_()
 
 
-class DpmAdaptiveStepper(LaneStepper):
+class DpmAdaptiveStepper(SolverLanes):
     """The adaptive DPM-Solver++ of order 2 (DPM_Solver.sample_graph_adaptive) with the step-size controller on the device.  A trial
     step s -> t is two graph replays per lane, and no host scalar enters either:
       "open"   [model timesteps of s -> the network's timestep buffer + mmd_cond_replace at alpha(s), sigma(s)] + U-Net plan + per stream
@@ -709,9 +729,6 @@ class DpmAdaptiveStepper(LaneStepper):
     WHO = "sample_graph_adaptive"
 
     def __init__(self, solver, unet, batch, device, tabs, use_graph=True, lanes=None, cond=None, ctr=None, select=None, control="sample"):
-        select = DPMPP_SELECT if select is None else select
-        if select not in ("multi", "block"):
-            raise H.MMDError(f"unknown selection {select!r} (multi or block)")
         if control not in ("sample", "batch"):
             raise H.MMDError(f"{self.WHO}: control must be 'sample' or 'batch', got {control!r}")
         if control == "batch":
@@ -720,16 +737,15 @@ class DpmAdaptiveStepper(LaneStepper):
                 raise H.MMDError(f"{self.WHO}: control='batch' takes the maximum over the whole batch, which must sit in one lane: lanes must be 1, got {lanes}")
         if not solver.predict_x0:
             raise H.MMDError(f"{self.WHO}: the adaptive stepper is built in its data-prediction form only (predict_x0=True)")
-        super().__init__(unet, batch, device, lanes, use_graph, ctr=ctr, own_ids=True)
-        self.diff, self.control = None, control
+        super().__init__(unet, batch, device, lanes, use_graph, ctr, select)
+        self.control = control
         self.params = th.zeros(ops.ADAPT_PARAMS, dtype=th.float64, device=self.device)
         self.log_alpha = th.zeros(len(tabs["log_alpha"]), dtype=th.float64, device=self.device)
         self.blk = [ops.AdaptBlock(self.n, self.device) for _ in self.engs]
         self._status = th.zeros(self.lanes, 2, dtype=th.int32).pin_memory()
         self.retable(tabs, ctr)
         self._alloc_cond(cond)
-        n, e = self.n, self.eng
-        geom = {"video": (e.F, e.Cv_in, unet.video_out_channels, e.H0 * e.W0), "audio": (1, e.Ca_in, unet.audio_out_channels, e.L0)}
+        n, geom = self.n, self._geom()
         thresholding, max_val = bool(solver.thresholding), float(solver.max_val)
         self._bufs = []
         sets = {"open": ([], []), "stage": ([], [])}
@@ -753,17 +769,9 @@ class DpmAdaptiveStepper(LaneStepper):
                             self._cond_replace(r, k, tag, qtab, blk.k, None)
                 with ops.recording(plan):
                     for sid, k, xk, ok, b in streams:
-                        Fk, C, Cm, HWk = geom[k]
+                        Fk, C, _, HWk = geom[k]
                         with ops.on_stream(sid):
-                            src, form, s = ok, 1, None
-                            if thresholding:
-                                multi = select == "multi"
-                                ops.dpmpp_x0(xk, ok, b["x0"], tab, blk.k, Fk, C, Cm, HWk, hist=b["ws"] if multi else None)
-                                if multi:
-                                    ops.dpmpp_select(b["x0"], 0.995, b["s"], b["ws"], level0_done=True)      # p of the Imagen paper
-                                else:
-                                    ops.abs_quantile(b["x0"], 0.995, out=b["s"])
-                                src, form, s, Cm = b["x0"], 0, b["s"], C
+                            src, form, s, Cm = self._record_model_value(xk, ok, b, tab, blk.k, geom[k], True, thresholding, True)
                             if opening:
                                 ops.dpm_adapt_open(xk, src, b["xb"], b["ms"], b["lo"], tab, blk.k, Fk, C, Cm, HWk, form=form, s=s, max_val=max_val)
                             else:
@@ -789,18 +797,11 @@ class DpmAdaptiveStepper(LaneStepper):
 
     def retable(self, tabs, ctr=None):
         """Load the parameter block, the schedule and (with a counter source) the key and sample ids: what another call may change."""
-        if (ctr is None) != (self.ctr is None):
-            raise H.MMDError("the noise source's kind is fixed when the stepper is built")
         if len(tabs["log_alpha"]) != self.log_alpha.numel():
             raise H.MMDError(f"{self.WHO}: the schedule's length is fixed when the stepper is built")
+        self._load_ctr(ctr)
         ops.dpm_adapt_params(self.device, out=self.params, **tabs["params"])
         self.log_alpha.copy_(th.as_tensor(tabs["log_alpha"], dtype=th.float64))
-        self.ctr = ctr
-        if ctr is not None:
-            self.key.copy_(ctr.key(self.device))
-            self.ids.copy_(ctr.ids(self.N, self.device))
-
-    usable = SolverStepper.usable
 
     # ------------------------------------------------------------------ launch: the sets carry their own pre-plans
     def _lane_launch(self, ps, r, stream):

@@ -34,7 +34,7 @@ Weight pack / gradient unpack: pure data movement, `torch.equal` with permute + 
 and lanes (pack_ci_tile, the lane split tstep = 64 / nci, pack_find's count over the table) so that a defect lands where the kernel's
 would.
 
-Solver helpers (mmd_diffusion.hip): lincomb (ca a, then one fma per present term: product and sum counted apart), lincomb_t
+Solver helpers (mmd_diffusion.hip: lincomb, lincomb_t; mmd_dpm.hip: clamp_scale, dpm_err): lincomb (ca a, then one fma per present term: product and sum counted apart), lincomb_t
 (ca[t] a + cb[t] b) cs[t], clamp_scale clamp(x, -sn, sn) / (sn / max_val) with sn = max(s, 1) (the comparisons are on exact inputs),
 dpm_err: e = (hi - lo) / max(atol, rtol max(|lo|, |prev|)) in V (max is 1-Lipschitz: V.max needs no branch), e^2 is exact in double,
 the double sum of `per` terms costs per 2^-53 of it: bound = sum (2 |e| b_e + b_e^2) + per 2^-53 sum e^2.

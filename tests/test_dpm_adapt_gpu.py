@@ -1,7 +1,8 @@
 """The graph-replayed adaptive DPM-Solver++ on the GPU: mmd_dpm_adapt_open / close / commit bitwise against the launches they replace
 (mmd_clamp_scale, mmd_lincomb, copies), the error sums of mmd_dpm_adapt_close against their restated order and a float64 sum,
 mmd_dpm_adapt_control against the float64 restatement (tests/dpm_adapt_ref.py), and DPM_Solver.sample_graph_adaptive against a host loop
-composed from existing ops, against itself under every execution choice, and against the reference's fixture.
+composed from existing ops, against itself under every execution choice, and against the reference's fixture.  The quad kernels of the
+step family (these three and mmd_dpmpp_sde_update / _ctr) on buffers one float off a 16-byte boundary against the aligned run, bit for bit.
 
 Bounds.  Everything compared with existing kernels or with another execution of the same loop is compared bit for bit.  The partial sums
 are the restated order's bits, and their fold lies within (elements + chunks) 2^-53 relative of numpy's float64 sum of the same fp32 terms
@@ -124,6 +125,80 @@ def test_open_close_commit_are_bitwise_the_launches_they_replace(shape, Cm_facto
     for n, (wx, wp) in enumerate((("x", "lo"), ("x", "prev"), ("xb", "prev"))):
         got = (g["x"][1][n].cpu().numpy(), g["prev"][1][n].cpu().numpy())
         assert R.compare_commit(got, (t[wx][n].cpu().numpy(), t[wp][n].cpu().numpy())) == [], n
+
+
+# The quad kernels of the step family take their 16-byte path by the alignment bits of their buffers (one helper computes them for every
+# entry point).  Bits must not depend on them: the shape of tests/dpm_sde_ref.py, 6147 elements a sample (ragged last quad, quads that
+# straddle a (frame, channel) row, samples 1 and 2 off a quad), with every state buffer one float into its allocation, and with the source
+# of the model value alone there, against the run on aligned buffers.
+ALIGN_ENTRIES = ["sde_update", "sde_update_ctr", "open_form0", "open_form1", "close_form0", "close_form1", "commit"]
+
+
+@pytest.mark.parametrize("entry", ALIGN_ENTRIES)
+def test_buffers_one_float_off_16_bytes_give_the_aligned_bits(entry):
+    import dpm_sde_ref as S
+    from mm_diffusion import ops
+    N, F, C, HW = shape = (S.N, S.F, S.C, S.HW)
+    params = ops.dpm_adapt_params("cuda", **PARAMS)
+    key = torch.from_numpy(np.array([S.SEED & 0xFFFFFFFF, S.SEED >> 32], dtype=np.uint32).view(np.int32)).cuda()
+    ids = torch.tensor(list(S.IDS), dtype=torch.int64, device="cuda")
+    s_all = torch.from_numpy(S.S_VALUES).cuda()
+    for cmf in (1, 2):
+        t, src, tab, _ = _case(shape, cmf, seed=5)
+        sde = S.make_case(cmf, True)
+        sde_tab, cz = torch.from_numpy(sde["tab"]).cuda(), torch.from_numpy(sde["cz"]).cuda()
+        geom = (F, C, C * cmf, HW)
+        k = torch.tensor([2, 0, 1], dtype=torch.int64, device="cuda")
+        form, s = (1, None) if entry.endswith("form1") else (0, s_all)
+        # entry -> (the state buffers, the runs' launches: each takes the views v and the source's view, and returns its other outputs)
+        if entry.startswith("sde"):
+            ctr = entry == "sde_update_ctr"
+            names = ("x", "ms") if ctr else ("x", "ms", "lo")          # x, M1 and, in the memory form, the noise
+
+            def launch(v, sv):
+                for rows in S.K_CASES[4:]:          # rows of every kind, over two launches
+                    noise = dict(ctr=(key, ids, 1)) if ctr else dict(noise=v["lo"])
+                    ops.dpmpp_sde_update(v["x"], sv, v["ms"], sde_tab, cz, torch.tensor(rows, dtype=torch.int64, device="cuda"), *geom, s=s_all,
+                                         max_val=S.MAX_VAL, **noise)
+                return {}
+        elif entry.startswith("open"):
+            names = ("x", "xb", "ms", "lo")
+
+            def launch(v, sv):
+                ops.dpm_adapt_open(v["x"], sv, v["xb"], v["ms"], v["lo"], tab, k, *geom, form=form, s=s, max_val=S.MAX_VAL)
+                return {}
+        elif entry.startswith("close"):
+            names = ("x", "xb", "ms", "lo", "prev")
+
+            def launch(v, sv):
+                partial = torch.full((N, ops.dpm_adapt_chunks(F * C * HW)), -7.0, dtype=torch.float64, device="cuda")
+                ops.dpm_adapt_close(v["x"], sv, v["xb"], v["ms"], v["lo"], v["prev"], tab, k, params, partial, *geom, form=form, s=s, max_val=S.MAX_VAL)
+                return {"partial": partial}
+        else:
+            names = ("x", "xb", "prev", "lo")
+
+            def launch(v, sv):
+                cnt = torch.zeros(N, 4, dtype=torch.int32, device="cuda")
+                for flags in ((ops.ADAPT_FLAG_ACCEPT, ops.ADAPT_FLAG_IDLE, ops.ADAPT_FLAG_REJECT), (ops.ADAPT_FLAG_REJECT, ops.ADAPT_FLAG_ACCEPT, ops.ADAPT_FLAG_ACCEPT)):
+                    cnt[:, ops.ADAPT_C["flag"]] = torch.tensor(flags, dtype=torch.int32)
+                    ops.dpm_adapt_commit(v["x"], v["xb"], v["prev"], v["lo"], cnt)
+                return {}
+
+        def run(off, off_src):
+            g = {name: _guarded(t[name], off) for name in names}
+            gs = _guarded(src, off_src)
+            assert all(v.data_ptr() % 16 == 4 * off for _, v in g.values()) and gs[1].data_ptr() % 16 == 4 * off_src
+            out = launch({name: v for name, (_, v) in g.items()}, gs[1])
+            torch.cuda.synchronize()
+            assert all(_guards_intact(b, t[name], off) for name, (b, _) in g.items()), (entry, cmf, off, off_src, "a float outside a view was written")
+            assert _guards_intact(gs[0], src, off_src) and same(gs[1], src), (entry, cmf, off, off_src, "the source was written")
+            return dict({name: v.clone() for name, (_, v) in g.items()}, **out)
+        want = run(0, 0)
+        assert any(not same(want[name], t[name]) for name in names), "the aligned run wrote something"
+        for off, off_src in ((1, 1), (0, 1)) if entry != "commit" else ((1, 0),):          # commit has no source
+            got = run(off, off_src)
+            for name in want:
+                assert same(got[name], want[name]), (entry, cmf, off, off_src, name)
 
 
 def test_refused_arguments_write_nothing():

@@ -5,7 +5,8 @@ tests/test_errbound_small_cpu.py: the bounds proven on the CPU and on seeded def
     mmd_misc.hip        mmd_timestep_embedding, mmd_temb_fwd, mmd_linear_fwd (forward and the backward use with W^T), mmd_cast
     mmd_bwd.hip         mmd_silu (forward and `dy` form), mmd_dropout, mmd_mse_grad, mmd_adamw_step, mmd_adamw_step_guarded (behind
                         mmd_sumsq_chunks + mmd_step_control), mmd_pack_conv_weights, mmd_unpack_conv_grads, mmd_pack_blocks
-    mmd_diffusion.hip   mmd_lincomb, mmd_lincomb_t, mmd_clamp_scale, mmd_dpm_err
+    mmd_diffusion.hip   mmd_lincomb, mmd_lincomb_t
+    mmd_dpm.hip         mmd_clamp_scale, mmd_dpm_err
 
 Every case calls the kernel through mm_diffusion.ops (H.call for the pack pair, as optim.WeightPacker does) with NaN-prefilled outputs,
 builds the reference with torch double ops - never with a libmmd kernel - and admits ZERO elements outside the per-element bound.
