@@ -82,13 +82,6 @@ __device__ __forceinline__ u32x4 q_frag(const char* qp, int s, int half, bool qo
   if (qok) v = *(const u32x4*)(qp + (s * 16 + half * 8) * 2);
   return v;
 }
-template <int DT>
-__device__ __forceinline__ void zero_acc(f32x16 (&o)[DT]) {
-#pragma unroll
-  for (int t = 0; t < DT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[t][r] = 0.f;
-}
 
 // A fragment (8 k-slots) of a transposed, key-permuted [D][64] tile for MFMA step (kt, st): slots j<4 -> cols 32kt+16st+4half+j, j>=4 -> +8
 __device__ __forceinline__ u32x4 tr_frag(const char* tr, int row, int kt, int st, int half) {

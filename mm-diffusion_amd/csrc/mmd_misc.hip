@@ -1,7 +1,7 @@
 // Small kernels around the U-Net that belong to neither a convolution nor the diffusion process:
 //   timestep embedding + MLP (nn.py:192-210, multimodal_unet.py:791-795,1075), batched emb_layers Linear (unet:366-372),
 //   avg-pool / nearest resampling (unet:133-208) with and without GroupNorm statistics, skip-concat copies (unet:1093-1094) and the
-//   gradient payload cast.  The layout-edge convolutions are in mmd_edge.hip, the diffusion process in mmd_diffusion.hip,
+//   gradient payload cast; SiLU, dropout and the MSE gradient of the training step.  The layout-edge convolutions are in mmd_edge.hip, the diffusion process in mmd_diffusion.hip,
 //   the DPM-Solver kernels in mmd_dpm.hip.
 #include "mmd_common.h"
 
@@ -285,4 +285,70 @@ extern "C" int mmd_cast(const void* x, int src_dtype, void* y, int dst_dtype, fl
   MMD_REQUIRE(x && y && n > 0, "cast: bad argument");
   MMD_REQUIRE((src_dtype == MMD_F32 || src_dtype == MMD_BF16) && (dst_dtype == MMD_F32 || dst_dtype == MMD_BF16), "cast: bad dtype");
   return mmd_launch<cast_kernel>("cast", dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, x, y, src_dtype == MMD_BF16, dst_dtype == MMD_BF16, scale, n);
+}
+
+// ----------------------------------------------------------------------------- element-wise pieces of the training step
+// out = silu(x) or dy * silu'(x).  The product is (dy sg) (1 + x (1 - sg)): dsilu_f(x) would round sg (1 + ...) first.
+template <typename T>
+__global__ __launch_bounds__(256) void silu_kernel(const char* __restrict__ x, const char* __restrict__ dy, char* __restrict__ out, int64_t nvec) {
+  constexpr int EPV = Elt<T>::EPV;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256) {
+    float f[EPV], d[EPV];
+    Elt<T>::unpack(((const u32x4*)x)[i], f);
+    if (dy) Elt<T>::unpack(((const u32x4*)dy)[i], d);
+#pragma unroll
+    for (int e = 0; e < EPV; ++e) {
+      const float sg = __builtin_amdgcn_rcpf(1.f + __expf(-f[e]));
+      f[e] = dy ? d[e] * sg * (1.f + f[e] * (1.f - sg)) : f[e] * sg;
+    }
+    ((u32x4*)out)[i] = Elt<T>::pack(f);
+  }
+}
+
+// inverted dropout: out = x * mask * scale (mask bytes 0/1, drawn by the caller); the backward is the same kernel on dy
+template <typename T>
+__global__ __launch_bounds__(256) void dropout_kernel(const char* __restrict__ x, const uint8_t* __restrict__ mask, float scale,
+                                                      char* __restrict__ out, int64_t nvec) {
+  constexpr int EPV = Elt<T>::EPV;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256) {
+    float f[EPV];
+    Elt<T>::unpack(((const u32x4*)x)[i], f);
+#pragma unroll
+    for (int e = 0; e < EPV; ++e) f[e] = mask[i * EPV + e] ? f[e] * scale : 0.f;
+    ((u32x4*)out)[i] = Elt<T>::pack(f);
+  }
+}
+
+// d loss / d out for loss = sum_n w[n] * mean_n((target - out)^2):  g = 2 (out - target) * w[n] / per
+__global__ __launch_bounds__(256) void mse_grad_kernel(const float* __restrict__ out, const float* __restrict__ target,
+                                                       const float* __restrict__ w, float* __restrict__ g, int64_t per, int64_t total) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256)
+    g[i] = 2.f * (out[i] - target[i]) * w[i / per] / (float)per;
+}
+
+// out = silu(x) (dy == NULL) or dy * silu'(x); contiguous buffers of n elements (n % (16/elsize) == 0)
+extern "C" int mmd_silu(int dtype, const void* x, const void* dy, void* out, int64_t n, void* stream) {
+  const int epv = dtype == MMD_BF16 ? 8 : 4;
+  MMD_REQUIRE((dtype == MMD_BF16 || dtype == MMD_F32) && x && out && n > 0 && n % epv == 0, "silu: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  return mmd_by_dtype(dtype, [&](auto t) {
+    return mmd_launch<silu_kernel<typename decltype(t)::type>>("silu", dim3(ew_grid(n / epv)), dim3(256), 0, st, (const char*)x, (const char*)dy, (char*)out,
+                                                               n / epv);
+  });
+}
+
+extern "C" int mmd_dropout(int dtype, const void* x, const uint8_t* mask, float scale, void* out, int64_t n, void* stream) {
+  const int epv = dtype == MMD_BF16 ? 8 : 4;
+  MMD_REQUIRE((dtype == MMD_BF16 || dtype == MMD_F32) && x && mask && out && n > 0 && n % epv == 0, "dropout: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  return mmd_by_dtype(dtype, [&](auto t) {
+    return mmd_launch<dropout_kernel<typename decltype(t)::type>>("dropout", dim3(ew_grid(n / epv)), dim3(256), 0, st, (const char*)x, mask, scale,
+                                                                  (char*)out, n / epv);
+  });
+}
+
+extern "C" int mmd_mse_grad(const float* out, const float* target, const float* w, float* g, int N, int64_t per_sample, void* stream) {
+  MMD_REQUIRE(out && target && w && g && N > 0 && per_sample > 0, "mse_grad: bad argument");
+  const int64_t total = per_sample * N;
+  return mmd_launch<mse_grad_kernel>("mse_grad", dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, out, target, w, g, per_sample, total);
 }

@@ -26,7 +26,7 @@
 #include "mmd_common.h"
 
 // Workgroup id for a grid whose neighbours in id should share an L2: hardware block bid runs on XCD bid & 7, so XCD x gets the
-// contiguous id range [start(x), start(x) + blocks on x) of the nwg ids.  (mmd_bwd.hip's weight-gradient order is another formula.)
+// contiguous id range [start(x), start(x) + blocks on x) of the nwg ids.  (mmd_wgrad.hip's weight-gradient order is another formula.)
 __device__ __forceinline__ int xcd_block_id(int bid, int nwg) {
   const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);

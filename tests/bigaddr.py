@@ -102,7 +102,7 @@ LIMITS += [
     _row("mmd_vconv2d1d", "", "X", "per-sample descriptor re-based per sample", "sample", B31 - 1, "refuses", "vconv_shape_ok",
          "mmd_vconv.hip:559 / :100; ops.vconv_shape_ok"),
     _row("mmd_conv_wgrad", "transposing kernel", "dY,X", "descriptors cast to int", "launch", B31 - 1, "computes", None,
-         "mmd_bwd.hip:886 gate M * ld * 2 < 2 GiB (the 128-tile kernel runs beyond), :283-284 (int) record counts, :301-315 32-bit row offsets"),
+         "mmd_wgrad.hip:539 gate M * ld * 2 < 2 GiB (the 128-tile kernel runs beyond), :306-307 (int) record counts, :324-338 32-bit row offsets"),
 ]
 for _e in ("mmd_gn_stats", "mmd_gn_apply", "mmd_gn_small", "mmd_gn_group", "mmd_gn_finalize_stats", "mmd_add_rowbias", "mmd_copy2d"):
     LIMITS.append(_row(_e, "", "all", "64-bit", "none", None, "computes", None, "mmd_norm.hip / mmd_misc.hip: int64 base * ld, int64 row strides"))
@@ -118,10 +118,10 @@ LIMITS += [
     _row("mmd_stem_conv", "", "y", _I64, "none", None, "computes", None, "mmd_edge.hip:28 / :120 / :234 m int64, :44 / :122 / :243 m * p.ldy"),
     _row("mmd_head_conv", "", "x", _I64, "none", None, "computes", None, "mmd_edge.hip:157 / :337 / :417 src int64, :158 / :338 / :421 src * p.ldx"),
     _row("mmd_head_gemm", "", "x", _I64, "none", None, "computes", None, "mmd_edge.hip:569-573 mc int64 * p.ldx"),
-    _row("mmd_colsum_slices", "", "dY", _I64, "none", None, "computes", None, "mmd_bwd.hip:431 / :442 (int64_t)m * ld, :928 (int64_t)s * Tn * lddy"),
-    _row("mmd_conv_wgrad", "128-tile and 64-tile kernels", "dY,X", _I64, "none", None, "computes", None, "mmd_bwd.hip:64-68, :153-157 (int64_t)m * p.lddy / p.ldx"),
-    _row("mmd_gn_bwd", "", "x,dy,dx", _I64, "none", None, "computes", None, "mmd_bwd.hip:516-526, :623-637 r0 int64 * ldx / lddy / lddx"),
-    _row("mmd_gn_bwd_ws0", "", "x,dy,dx", _I64, "none", None, "computes", None, "as mmd_gn_bwd (one implementation: gn_bwd_impl, mmd_bwd.hip:945)"),
+    _row("mmd_colsum_slices", "", "dY", _I64, "none", None, "computes", None, "mmd_wgrad.hip:437 / :448 (int64_t)m * ld, :560 (int64_t)s * Tn * lddy"),
+    _row("mmd_conv_wgrad", "128-tile and 64-tile kernels", "dY,X", _I64, "none", None, "computes", None, "mmd_wgrad.hip:101-103, :182-186 (int64_t)m * p.lddy / p.ldx"),
+    _row("mmd_gn_bwd", "", "x,dy,dx", _I64, "none", None, "computes", None, "mmd_gn_bwd.hip:40-50 (the row walk of reduce and apply), :178 r0 int64 * ldx / lddy / lddx"),
+    _row("mmd_gn_bwd_ws0", "", "x,dy,dx", _I64, "none", None, "computes", None, "as mmd_gn_bwd (one implementation: gn_bwd_impl, mmd_gn_bwd.hip:190)"),
     _row("mmd_attn_bwd", "", "Q,KV,O,dO,dQ,dKV", _I64, "none", None, "computes", None, "mmd_attn_bwd_body.inc:32-295 row * p.ld* with int64_t ld fields (mmd_attn_bwd.hip:15-20)"),
     _row("mmd_attn_bwd_mfma", "", "Q,KV,O,dO,dQ,dKV", _I64, "none", None, "computes", None, "mmd_attn_bwd_mfma.hip:84-299 row * p.ld* with int64_t ld fields (:13-18)"),
     _row("mmd_attn_small_bwd", "", "QKV,dO,dQKV", _I64, "none", None, "computes", None, "mmd_attn_bwd.hip:176-213 row * p.ld / lddo / ldd (int64_t, :141-143)"),
@@ -523,7 +523,7 @@ BWD_CASES = [
 ]
 
 
-# Launches whose outputs are sums of fp32 atomics (mmd_bwd.hip:103 / :230 / :407 dW, :217 / :395 db, :453 colsum, :535-536 and :562-563 the
+# Launches whose outputs are sums of fp32 atomics (mmd_wgrad.hip:67 / :259 dW, :246 / :414 db, :459 colsum, mmd_gn_bwd.hip:97-98 and :124-125 the
 # GroupNorm backward's partial sums): their last bit depends on the order of the run, so these are held to the bound - and, on the
 # exact-sum inputs (mode True), to exact equality - but not compared bitwise with the compact run.
 def atomic_sums(c, mode):
@@ -538,7 +538,7 @@ def fused_expect(c, views):
 
 
 def wgrad_kernel(c, views):
-    """Which weight-gradient kernel the launcher takes (mmd_bwd.hip:886): the transposing 9-tap kernel only while M * ld * 2 < 2 GiB on both
+    """Which weight-gradient kernel the launcher takes (mmd_wgrad.hip:539): the transposing 9-tap kernel only while M * ld * 2 < 2 GiB on both
     operands; the kernels are bitwise equal on exact-sum inputs only, so the comparison with the compact run uses those."""
     if c["dt"] != "bf16" or c["Cin"] < 64 or c["Cout"] < 64:
         return "64"

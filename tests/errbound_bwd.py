@@ -3,14 +3,14 @@ package under test).  The forward half and the notation are in tests/errbound.py
 first order in u, `check` admits zero violating elements.  The rule used throughout: a sum of n fp32 terms accumulated in ANY order -
 per-thread partials, LDS folds, atomics across row splits, the add onto a zeroed buffer - carries at most (n - 1) u sum|terms|.
 
-conv weight gradient (`wgrad_ref`, `wgrad_bound`; mmd_bwd.hip: wgrad_kernel<T>, wgrad128_bf16_kernel, wgrad_tr_bf16_kernel)
+conv weight gradient (`wgrad_ref`, `wgrad_bound`; mmd_wgrad.hip: wgrad_kernel<T>, wgrad128_bf16_kernel, wgrad_tr_bf16_kernel)
     dW[co, tap * Cin + ci] = sum_m dY[m, co] X[src(m, tap), ci], the gather of errbound.conv_gather (zero where the tap leaves
-    the frame); S = |dY|^T |gather(X)|.  The M products of one element are accumulated on the MFMA in fp32 (mmd_bwd.hip:84 / :92 /
-    :211 / :391), one partial per row split, and the partials meet in fp32 atomics on the buffer the caller zeroed (:103, :230, :407):
+    the frame); S = |dY|^T |gather(X)|.  The M products of one element are accumulated on the MFMA in fp32 (mmd_wgrad.hip:119 / :127 /
+    :240 / :410), one partial per row split, and the partials meet in fp32 atomics on the buffer the caller zeroed (wg_scatter, :67; wgrad128, :259):
     M + 1 terms with the zero, M roundings.  bf16 x bf16 products are exact in fp32; an fp32 product is rounded once more.
         bf16 inputs: (M + 1) u S        fp32 inputs: (M + 2) u S.
     The output is fp32 in both modes: no store rounding.
-    db[c] = sum_m dY[m, c] (colsum_kernel :414-455; in the 128-tiles the (tap 0, ci tile 0) blocks, :184-191 / :371-380): M terms and
+    db[c] = sum_m dY[m, c] (colsum_kernel :420-461; in the 128-tiles the (tap 0, ci tile 0) blocks, :213-220 / :390-399): M terms and
     the zero, no products: (M + 1) u Sb, Sb = sum_m |dY|.  `colsum_slices` is the same kernel per sample: (Tn + 1) u Sb.
 
 conv input gradient: no kernel of its own - mmd_conv_gemm on dY with the weight transposed to [Cin, ntaps * Cout] and the taps
@@ -23,7 +23,7 @@ exact-sum inputs (`grid_randn`)
     integer below 2**24 units, i.e. exactly representable in fp32: NO rounding happens anywhere and every legal kernel returns the
     same bits, float64 reference cast to fp32.  `exact_sum_ok(n)` asserts 49 n < 2**24 (the deepest n used is 2376: 116 424).
 
-GroupNorm backward (`gn_fwd_ref` with its bounds e_a / e_b / e_mean / e_rstd, `gn_bwd_ref`; mmd_bwd.hip: gn_bwd_reduce / params / apply, :472-639)
+GroupNorm backward (`gn_fwd_ref` with its bounds e_a / e_b / e_mean / e_rstd, `gn_bwd_ref`; mmd_gn_bwd.hip: gn_bwd_reduce / params / apply, :55-180)
     Forward (mmd_norm.hip:39-159, :161-235): per (slice, group) the sums of d = x - pivot and of d^2 (pivot = the group's first
     element of the slice's first row), per-thread in fp32 (:94), then in double; mean = pivot + sum d / cnt, var = sum d^2 / cnt -
     dm^2 and rstd = 1 / sqrt(var + eps) in double, each rounded once to fp32 (:134-135).  With Sd = sum |d|, Sq = sum d^2 over the
@@ -41,7 +41,7 @@ GroupNorm backward (`gn_fwd_ref` with its bounds e_a / e_b / e_mean / e_rstd, `g
         m1 = sum_{c in group} g_c P_c / cnt,  m2 = sum g_c Q_c / cnt
         dx = rstd (g_c dv - m1 - z m2),  dgamma = sum_s (1 + scale) Q,  dbeta = sum_s (1 + scale) P,
         dscale = gamma Q + beta P,  dshift = P.
-    Error of dv as the kernels compute it (:505-509 = :616-620), every operation rounded once, v_exp_f32 and v_rcp_f32 accurate to
+    Error of dv as the kernels compute it (:84-85 = :174-175, dsilu_f of mmd_common.h), every operation rounded once, v_exp_f32 and v_rcp_f32 accurate to
     1 ulp = 2 u relative, __expf's multiply by log2(e) one more rounding of the argument:
         e_v  = 2 u (|x a| + |b|)
         e_sg = sg ((1 - sg) (e_v + u |v| + 2 u) + 3 u)                       (exp, the add of 1, the reciprocal)
@@ -49,13 +49,13 @@ GroupNorm backward (`gn_fwd_ref` with its bounds e_a / e_b / e_mean / e_rstd, `g
         e_q  = |v| e_w + w e_v + u |v w| + u |1 + v w|                       q = 1 + v w
         e_r  = sg e_q + |q| e_sg + u |sg q|                                  r = sg q
         e_dv = |dy| e_r + u |dv|
-    Sums (:510-511, :532-536 atomics onto the zeroed workspace): Tn terms and the zero; a term of Q carries three more roundings:
+    Sums (:86-87, :94-98 atomics onto the zeroed workspace): Tn terms and the zero; a term of Q carries three more roundings:
         e_P = (Tn + 1) u sum |dv| + sum e_dv,   e_Q = (Tn + 4) u sum |dv z| + sum e_dv |z|
-    Parameter stage (:551-575): g_c two roundings, g_c P one, the group sum of cpg terms, the division:
+    Parameter stage (:113-137): g_c two roundings, g_c P one, the group sum of cpg terms, the division:
         e_m1 = (sum_c |g_c| e_P + (cpg + 4) u sum_c |g_c P_c|) / cnt,  e_m2 likewise with Q
-        e_dgamma = sum_s (|1 + scale| e_Q + 2 u |(1 + scale) Q|) + (S + 1) u sum_s |(1 + scale) Q|      (atomics over the slices, :562)
+        e_dgamma = sum_s (|1 + scale| e_Q + 2 u |(1 + scale) Q|) + (S + 1) u sum_s |(1 + scale) Q|      (atomics over the slices, :124)
         e_dscale = |gamma| e_Q + |beta| e_P + 3 u (|gamma Q| + |beta P|),  e_dshift = e_P
-    dx in the kernel's own form k1 dv + k2 x + k3 (:604-606, :621), k1 = rstd g_c, k2 = - rstd^2 m2, k3 = rstd (mean rstd m2 - m1):
+    dx in the kernel's own form k1 dv + k2 x + k3 (:164-166, :176), k1 = rstd g_c, k2 = - rstd^2 m2, k3 = rstd (mean rstd m2 - m1):
         e_k1 = 3 u |k1|,  e_k2 = rstd^2 e_m2 + 2 u |k2|,
         e_k3 = rstd (|mean rstd| e_m2 + e_m1) + 4 u rstd (|mean rstd m2| + |m1|)
         e_dx = |k1| e_dv + e_k1 |dv| + e_k2 |x| + e_k3 + 3 u (|k1 dv| + |k2 x| + |k3|)
@@ -146,7 +146,7 @@ def _cdiv(a, b):
 
 
 def wgrad_plan(M, Cin, Cout, ntaps, bf16):
-    """The launcher's arithmetic (mmd_bwd.hip: mmd_conv_wgrad, no MMD_WGRAD_* switch set): (kernel, splits, rows per split, xcd order).
+    """The launcher's arithmetic (mmd_wgrad.hip: mmd_conv_wgrad with wg_split, no MMD_WGRAD_* switch set): (kernel, splits, rows per split, xcd order).
     kernel 'tr' = the 128-tile (wgrad_tr_bf16_kernel, or wgrad128_bf16_kernel with MMD_WGRAD_TR=0: same splits), '64' = wgrad_kernel<T>."""
     if bf16 and Cout >= 64 and Cin >= 64:
         tiles = _cdiv(Cout, 128) * _cdiv(Cin, 128) * ntaps

@@ -17,7 +17,7 @@ Conditioning path (mmd_misc.hip)
         out = silu(raw)       E_out = L E_raw + e_silu(raw)
     linear_fwd: y = b + x W^T, K products and the bias in any order (64 strided chains and a butterfly): (K + 1) U (|x| |W|^T + |b|).
 
-Element-wise training kernels (mmd_bwd.hip)
+Element-wise training kernels (mmd_misc.hip, mmd_optim.hip)
     silu, forward x sg and `dy` form dy sg (1 + x (1 - sg)) with sg = rcp(1 + __expf(-x)): V.sigmoid_f / V.silu_f.  bf16: the inputs
     are the stored bf16 values, the output one round-to-nearest: U16 (|ref| + e) + e.
     dropout (x mask scale) and cast ((T)(x scale)): one fp32 product and one round-to-nearest-even store - the C expression fixes

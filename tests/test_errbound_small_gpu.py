@@ -2,9 +2,10 @@
 (tests/errbound_small.py: the references, the bounds and their derivation, the fp32 emulations, the case lists;
 tests/test_errbound_small_cpu.py: the bounds proven on the CPU and on seeded defects):
 
-    mmd_misc.hip        mmd_timestep_embedding, mmd_temb_fwd, mmd_linear_fwd (forward and the backward use with W^T), mmd_cast
-    mmd_bwd.hip         mmd_silu (forward and `dy` form), mmd_dropout, mmd_mse_grad, mmd_adamw_step, mmd_adamw_step_guarded (behind
-                        mmd_sumsq_chunks + mmd_step_control), mmd_pack_conv_weights, mmd_unpack_conv_grads, mmd_pack_blocks
+    mmd_misc.hip        mmd_timestep_embedding, mmd_temb_fwd, mmd_linear_fwd (forward and the backward use with W^T), mmd_cast,
+                        mmd_silu (forward and `dy` form), mmd_dropout, mmd_mse_grad
+    mmd_optim.hip       mmd_adamw_step, mmd_adamw_step_guarded (behind mmd_sumsq_chunks + mmd_step_control), mmd_pack_conv_weights,
+                        mmd_unpack_conv_grads, mmd_pack_blocks
     mmd_diffusion.hip   mmd_lincomb, mmd_lincomb_t
     mmd_dpm.hip         mmd_clamp_scale, mmd_dpm_err
 

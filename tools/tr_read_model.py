@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Lane-level numpy model of the row-major LDS tile + transposing reads that the DMA attention kernel (V operand) and the 9-tap weight
-gradient kernel (both operands) share (mmd_attn_common.h: read_vt_frags_tr, mmd_bwd.hip: wgrad_tr_bf16_kernel::frag).
+gradient kernel (both operands) share (mmd_attn_common.h: read_vt_frags_tr, mmd_wgrad.hip: wgrad_tr_bf16_kernel::frag).
 
 Tile: one plane = [64 rows][128 B] (64 bf16 channels per row), the 16-byte chunk c of row r stored at chunk c ^ (((r >> 1) & 1) << 2).
 The DMA writes lane-linear: lane L of wave-instruction g lands at byte g * 1024 + L * 16, i.e. row 8 g + L / 8, physical chunk L % 8, and
